@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json metric): audio channel-samples/sec of the 6-band parametric_eq
 forward + backward at (B, C, N) = (256, 2, 131072) fp32.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--launch eager|graph]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--launch eager|graph] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,20 +13,22 @@ data-path collective (the effect has no cross-item exchange).
   --scaling weak   (default) every rank processes its own (256, 2, 131072) batch; `value` = N * units / max-over-ranks time
   --scaling strong the one 256-item batch is partitioned 256/N items per GPU; `value` = units / max-over-ranks time
   --launch graph   the step (forward + backward, same kernels, same launches) is captured once into a HIP graph and replayed;
-                   eager issues it from Python every step. --launch both (default) times both: `launch_ms_per_step` has both,
-                   `value` / `ms_per_step` are the faster one and `config.launch` names it (the step is 0.40 ms of kernels behind ~0.3 ms of
-                   host work per eager step, so a slow or loaded host makes the eager figure a host measurement).
+                   eager issues it from Python every step. --launch both (default) runs the timed steps in the faster of the two, by an
+                   untimed probe block of each (`probe_ms_per_step`); `config.launch` names it (the step is 0.40 ms of kernels behind
+                   ~0.3 ms of host work per eager step, so a slow or loaded host makes the eager figure a host measurement).
   --gpus N         N ranks. Under torchrun (WORLD_SIZE set) the world size must equal N; without it and N > 1, bench.py re-launches
                    itself as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...`. `n_gpus` = ranks that joined the
                    process group.
 
-Timing. Each launch mode is measured on the product path as a user calls it (one C call per direction, no timers, no events): an
-untimed clock ramp issued in that mode (--ramp-seconds), W warm-up steps, then --blocks blocks of EXACTLY K steps, each bracketed by
-barrier + device synchronize on both sides, max over ranks; `value` / `ms_per_step` are the median block (`block_ms_per_step` has
-min / median / max). A 20-step block is 8 ms, shorter than the 0.2 s the shader clock needs to ramp and of the same order as a host
-hiccup: the ramp precedes every mode and the median keeps a single disturbed block out of `value`.
+Timing. The step is measured on the product path as a user calls it (one C call per direction, no timers, no events): an untimed
+clock ramp issued in each launch mode (--ramp-seconds; the shader clock needs 0.2 s to ramp) and, with two modes, an untimed probe
+block of --probe-steps steps behind it; then W warm-up steps and ONE block of EXACTLY K steps in the chosen mode, bracketed by
+barrier + device synchronize on both sides, max over ranks: `ms_per_step` = that block / K, `value` = channel-samples per second.
+--dump-outputs DIR writes what the last timed step computed (see its help).
 
-The JSON line also carries
+A plain run stops there and prints the line. --full then measures both modes again in --blocks blocks of EXACTLY K steps each, after
+their own ramp and W warm-up steps (`launch_ms_per_step` = the median block per mode, `block_ms_per_step` has min / median / max; a
+20-step block is 8 ms, of the same order as a host hiccup), and the line also carries
   roofline     -- HBM roofline of the dominant kernel (the backward cascade): algorithmic bytes per launch / average launch duration,
                   measured live with HIP events on the launch stream in a separate, untimed pass directly behind the timed blocks (the
                   events need the kernels as separate entry points, which is not how the product issues them, so they stay out of the
@@ -36,11 +38,14 @@ The JSON line also carries
                   `kernel_events_over_step` = the four kernels' event durations over the timed step (0.97 - 1.03 when consistent);
                   `traffic` = HBM bytes per launch from the PMC counters, read from profiles/<round>/hbm_traffic.json only if that
                   file was produced from the kernel sources now loaded
-  frames_per_s, step_algorithmic_GBps_per_gpu -- the same rate in frames (B N) and the whole step on its 20 B per channel-sample
   roofline_*   -- the same for the forward kernel and for forward+backward together
+  finite       -- every gradient of the last step is finite
+  secondary    -- short timings of the other hot-path ops at their BASELINE.json configs (--no-secondary drops them)
   cpu_baseline -- the reference itself (oracle/_ref, staged by __graft_entry__.build(); kind "reference") on the host cores on a
                   bounded sub-batch (its best-case batch size), or, when it is not staged, the numpy restatement
-                  (oracle/dasp_oracle.py, kind "port").
+                  (oracle/dasp_oracle.py, kind "port"); --no-cpu-baseline drops it.
+Every run's line carries frames_per_s and step_algorithmic_GBps_per_gpu: the same rate in frames (B N) and the whole step on its 20 B
+per channel-sample.
 
 --dry-run-cpu is a test hook (tests/test_distributed_cpu.py): rank wiring, sharding, barriers, timing reduction and the JSON contract
 on CPU tensors over gloo with the kernels replaced by a copy; its numbers mean nothing and the line says so.
@@ -557,6 +562,74 @@ def profiled_kernel_ms():
     return None
 
 
+def dump_outputs(directory, y, gx, gcols, k=1 << 22, seed=0):
+    """--dump-outputs: what a caller of the timed path receives from its last step - y, x.grad and the 18 control gradients - as float32
+    .npy files. The controls' gradients are written whole; y and x.grad (B C N elements each) as the same seeded sample of k elements, one
+    per stride of B C N / k at an offset drawn within it, in index order: 2 x 16 MiB at the default workload."""
+    os.makedirs(directory, exist_ok=True)
+    n = y.numel()
+    if n > k:
+        stride = n // k
+        idx = np.arange(k, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, k)
+        idx = torch.from_numpy(idx).to(y.device)
+    else:
+        idx = torch.arange(n, device=y.device)
+    for name, t in (("y_sample", y), ("grad_x_sample", gx)):
+        np.save(os.path.join(directory, name + ".npy"), t.detach().reshape(-1)[idx].float().cpu().numpy())
+    np.save(os.path.join(directory, "grad_controls.npy"), torch.stack([c.detach() for c in gcols], 1).float().cpu().numpy())
+
+
+def full_fields(args, blocks, ktimes, pass_ms, dt, units, shape, dry, finite):
+    """--full: both launch modes' blocks, the per-kernel figures and rooflines of the event passes, the counter files they are tied to."""
+    nan = float("nan")
+    t_fwd_iso = float(np.mean(ktimes.get("dasp_sosfilt_forward", [nan]))) * 1e-3        # events around the entry points of the instrumented step
+    t_bwd_iso = float(np.mean(ktimes.get("dasp_sosfilt_backward_ex", [nan]))) * 1e-3
+    t_small = sum(float(np.mean(v)) for k, v in ktimes.items() if k not in ("dasp_sosfilt_forward", "dasp_sosfilt_backward_ex")) * 1e-3
+    t_prep = float(np.mean(ktimes.get("dasp_peq_prepare_rows", [nan]))) * 1e-3
+    t_fin = float(np.mean(ktimes.get("dasp_sos_grad_finalize_ex", [nan]))) * 1e-3
+    if pass_ms is not None and t_prep == t_prep and t_fin == t_fin:
+        # the dominant kernels inside the product step: the pass they are the bulk of, minus the small kernel of that pass (design / finalize:
+        # latency-bound, so their isolated event durations hold); the launch gap inside the pass stays with the kernel (conservative)
+        t_fwd = pass_ms["forward_pass"] * 1e-3 - t_prep
+        t_bwd = pass_ms["backward_pass"] * 1e-3 - t_fin
+    else:
+        t_fwd, t_bwd = t_fwd_iso, t_bwd_iso
+    traffic, traffic_file = ({}, None) if dry else load_traffic(shape)
+
+    def roof(bytes_per_sample, t, which=None):
+        a = bytes_per_sample * units / t / 1e9
+        return {"bound": "hbm", "achieved": round(a, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(a / HBM_PEAK_GBS, 4),
+                "traffic": traffic.get(which)}
+
+    per_step = lambda v: round(v / args.steps * 1e3, 5)
+    return {
+        "launch_ms_per_step": {k: per_step(float(np.median(v))) for k, v in blocks.items()},
+        "block_ms_per_step": {k: {"min": per_step(min(v)), "median": per_step(float(np.median(v))), "max": per_step(max(v))}
+                              for k, v in blocks.items()},
+        "roofline": dict(roof(12, t_bwd, "bwd"), kernel="sos_bwd_gram_kernel<6>", ms=round(t_bwd * 1e3, 4),
+                         algorithmic_bytes=12 * units),
+        "roofline_fwd": dict(roof(8, t_fwd, "fwd"), kernel="sos_fwd_kernel<6>", ms=round(t_fwd * 1e3, 4), algorithmic_bytes=8 * units),
+        "roofline_fwd_bwd": dict(roof(20, t_fwd + t_bwd, "both"), ms=round((t_fwd + t_bwd) * 1e3, 4), algorithmic_bytes=20 * units),
+        "small_kernels_ms": round(t_small * 1e3, 4),
+        # how the two durations above were measured: in situ (the step as two graph replays with one event between them; roofline.ms =
+        # the backward pass minus the finalize kernel's isolated duration, launch gap included) - and, for comparison, the isolated
+        # per-entry-point event durations of the four-call instrumented step, which read power-limited kernels fast
+        "passes_ms": None if pass_ms is None else {k: round(v, 4) for k, v in pass_ms.items()},
+        "isolated_events_ms": {"fwd": round(t_fwd_iso * 1e3, 4), "bwd": round(t_bwd_iso * 1e3, 4), "design": round(t_prep * 1e3, 4), "finalize": round(t_fin * 1e3, 4)},
+        # the same kernels' average durations in the newest committed rocprofv3 summary of this command (another run, possibly another
+        # box; profiles/rNN/bench_kernel_stats.csv) and the roofline fractions they give on the same algorithmic bytes
+        "rocprofv3_committed": (lambda pk: None if pk is None or tuple(shape) != (256, 2, 131072) else {
+            "file": pk["file"], "bwd_ms": round(pk["bwd"], 4), "fwd_ms": round(pk["fwd"], 4),
+            "bwd_frac": round(12 * units / (pk["bwd"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+            "fwd_frac": round(8 * units / (pk["fwd"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})(profiled_kernel_ms()),
+        # consistency of the event pass with the timed step: the four kernels' event durations over the step (gaps between the kernels
+        # are the rest; a ratio well below ~0.97 means the instrumented pass ran the kernels at another clock than the timed step did)
+        "kernel_events_over_step": round(((pass_ms["forward_pass"] + pass_ms["backward_pass"]) * 1e-3 if pass_ms is not None else (t_fwd + t_bwd + t_small)) / (dt / args.steps), 4),
+        "traffic_file": traffic_file, "kernel_source_hash": kernel_source_hash(),
+        "finite": finite,
+    }
+
+
 def _respawn_under_torchrun(n):
     """`python bench.py --gpus N` outside a torchrun environment: re-launch this command line as N ranks on this node, one per GPU
     (the launch line the driver uses for N > 1), so that --gpus N cannot silently be a one-rank run."""
@@ -577,14 +650,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: both launch modes in --blocks blocks each, the per-kernel event passes and rooflines, "
+                         "the secondary ops, the CPU baseline, the finiteness check. Off: the run sets up, warms up, times the --steps steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's shard) as float32 .npy files in DIR: "
+                         "grad_controls (B, 18) whole, y_sample and grad_x_sample as the same seeded sample of 2^22 of y's and x.grad's "
+                         "elements (one per stride of B C N / 2^22, at a seeded offset within it)")
+    ap.add_argument("--probe-steps", type=int, default=500,
+                    help="--launch both: steps of the untimed probe block of each mode that picks the faster one for the timed steps")
     ap.add_argument("--blocks", type=int, default=5,
-                    help="timed blocks of exactly --steps steps each (every block bracketed by barrier + device sync, max over ranks); "
-                         "`value` / `ms_per_step` are the median block, `block_ms_per_step` has min / median / max per launch mode")
+                    help="--full: blocks of exactly --steps steps per launch mode (every block bracketed by barrier + device sync, max over "
+                         "ranks) for `launch_ms_per_step` / `block_ms_per_step` (min / median / max per mode)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --batch items per GPU; strong: --batch items in total, partitioned over the GPUs (SURVEY 8e)")
     ap.add_argument("--launch", choices=("eager", "graph", "both"), default="both",
                     help="how the step is issued: from Python every step, as a replayed HIP graph of the same launches, or both (default; "
-                         "value = the faster, config.launch names it, launch_ms_per_step has both)")
+                         "the timed steps run in the faster one by the probe, config.launch names it; --full: launch_ms_per_step has both)")
     ap.add_argument("--ramp-seconds", type=float, default=1.0,
                     help="untimed clock ramp before each launch mode's warmup steps, issued in that mode: the MI355X needs ~0.2 s of "
                          "sustained load to leave its idle clocks (measured: the same kernels run 1.28x slower in the first 10 ms)")
@@ -649,6 +732,7 @@ def main():
     x.requires_grad_(True)
     cols = [params[:, i].clone().requires_grad_(True) for i in range(18)]
     peq = (lambda x, sr, *c: x * 1.0 + 0.0 * sum(c)[:, None, None]) if dry else D.parametric_eq
+    last = {}                                   # the eager step's y (its gradients stay on x and cols)
 
     def step():
         x.grad = None
@@ -656,6 +740,7 @@ def main():
             c.grad = None
         y = peq(x, SR, *cols)
         y.backward(w)
+        last["y"] = y
 
     def fence():
         sync()
@@ -680,19 +765,30 @@ def main():
             sync()
 
     def measure(fn):
-        """Ramp, W warm-up steps, then --blocks blocks of exactly K steps; the product path only: no timers, no events, no extra calls."""
+        """--full: ramp, W warm-up steps, then --blocks blocks of exactly K steps; the product path only: no timers, no events, no extra calls."""
         ramp(fn, args.ramp_seconds)
         for _ in range(args.warmup):
             fn()
         return [timed(fn, args.steps) for _ in range(max(1, args.blocks))]
 
     assert not _lib.timers.enabled
-    blocks = {}
-    if args.launch in ("eager", "both") or dry:
-        blocks["eager"] = measure(step)
+    fns, probe_ms = {}, {}
+
+    def ramp_and_probe(mode, fn):
+        """The untimed ramp in this mode; with two modes to choose from, an untimed block of --probe-steps steps behind it (max over ranks,
+        so that every rank picks the same mode)."""
+        ramp(fn, args.ramp_seconds)
+        if args.launch == "both" and not dry:
+            probe_ms[mode] = timed(fn, args.probe_steps) / args.probe_steps * 1e3
+    graph = graph_out = None
     if args.launch in ("graph", "both") and not dry:
+        for _ in range(3):                     # lazy state (allocator pools, cached tables) in place before the capture
+            step()
         # the same step captured once (torch.cuda.graph: forward + backward on the capture stream, gradients land in static buffers)
-        # and replayed: no Python, ctypes or autograd time per step, launch gaps are the graph's
+        # and replayed: no Python, ctypes or autograd time per step, launch gaps are the graph's. No autograd graph of another step may be
+        # alive across the capture or behind it: its AccumulateGrad nodes (one per leaf, reused while alive) would carry the stream they
+        # were made on into the other mode - an eager step's y held through the capture breaks it
+        last.clear()
         x.grad = None
         for c in cols:
             c.grad = None
@@ -701,9 +797,25 @@ def main():
         with torch.cuda.graph(graph):
             y = peq(x, SR, *cols)
             y.backward(w)
-        blocks["graph"] = measure(graph.replay)
+        graph_out = (y.detach(), x.grad, [c.grad for c in cols])
+        del y
+        fns["graph"] = graph.replay
+        ramp_and_probe("graph", graph.replay)
+    if args.launch in ("eager", "both") or dry:
+        # probed last: eager, the faster mode on every box measured so far, is then timed behind its own ramp (a 20-step eager block
+        # straight behind graph replays read 3 % slow)
+        fns["eager"] = step
+        ramp_and_probe("eager", step)
+    # the headline: W warm-up steps, then exactly K timed steps in the faster mode
+    mode = min(probe_ms, key=probe_ms.get) if probe_ms else next(iter(fns))
+    for _ in range(args.warmup):
+        fns[mode]()
+    dt = timed(fns[mode], args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *(graph_out if mode == "graph" else (last["y"], x.grad, [c.grad for c in cols])))
+    blocks = {m: measure(f) for m, f in fns.items()} if args.full else {}
     ktimes = {}
-    if not args.no_kernel_events and not dry:
+    if args.full and not args.no_kernel_events and not dry:
         # per-kernel durations: a separate, untimed pass right behind the timed blocks (warm clocks) with HIP events on the launch stream
         # around every C entry point. With the timers on, the ops issue design / cascade / adjoint / finalize as separate entry points
         # (the same kernels the one-call product path launches), so that each kernel gets its own pair of events.
@@ -735,7 +847,7 @@ def main():
         ktimes = _lib.timers.stop()
         print(f"[bench] event pass: {1e3 * host_per_step:.3f} ms of host time per instrumented step, {1e3 * gpu_per_step:.3f} ms of GPU time; "
               f"{n_rep} graph replays queued in front", file=sys.stderr)
-    finite = bool(torch.isfinite(x.grad).all().item()) and all(bool(torch.isfinite(c.grad).all().item()) for c in cols)
+    finite = args.full and bool(torch.isfinite(x.grad).all().item()) and all(bool(torch.isfinite(c.grad).all().item()) for c in cols)
     # In-situ durations of the two passes of the step (round 4). The per-entry-point events above sit inside a four-call instrumented step
     # issued through autograd, whose extra launches and records leave the power-limited kernels a cooler chip: they read the backward kernel
     # 2 - 8 % faster than rocprofv3 sees it in the product step (kernel_events_over_step says so). Here the step is the product's own two C
@@ -744,7 +856,7 @@ def main():
     # between the two calls and one at either end of every 4th step: nothing sits between the kernels of a pass, and the two intervals add
     # up to the step.
     pass_ms = None
-    if not dry and not args.no_kernel_events:
+    if args.full and not dry and not args.no_kernel_events:
         import ctypes
         from dasp_pytorch_amd import ops as _ops
         from dasp_pytorch_amd._lib import call as _call, ptr as _ptr, stream as _stream
@@ -781,32 +893,8 @@ def main():
     if rank == 0:
         units = B * C * N                       # channel-samples per step on this GPU
         total_units = global_batch * C * N      # ... over the whole job (weak: N x units; strong: the one batch)
-        med = {k: float(np.median(v)) for k, v in blocks.items()}
-        mode = min(med, key=med.get)
-        dt = med[mode]
         ms = dt / args.steps * 1e3
         value = total_units / (dt / args.steps)
-        nan = float("nan")
-        t_fwd_iso = float(np.mean(ktimes.get("dasp_sosfilt_forward", [nan]))) * 1e-3        # events around the entry points of the instrumented step
-        t_bwd_iso = float(np.mean(ktimes.get("dasp_sosfilt_backward_ex", [nan]))) * 1e-3
-        t_small = sum(float(np.mean(v)) for k, v in ktimes.items() if k not in ("dasp_sosfilt_forward", "dasp_sosfilt_backward_ex")) * 1e-3
-        t_prep = float(np.mean(ktimes.get("dasp_peq_prepare_rows", [nan]))) * 1e-3
-        t_fin = float(np.mean(ktimes.get("dasp_sos_grad_finalize_ex", [nan]))) * 1e-3
-        if pass_ms is not None and t_prep == t_prep and t_fin == t_fin:
-            # the dominant kernels inside the product step: the pass they are the bulk of, minus the small kernel of that pass (design / finalize:
-            # latency-bound, so their isolated event durations hold); the launch gap inside the pass stays with the kernel (conservative)
-            t_fwd = pass_ms["forward_pass"] * 1e-3 - t_prep
-            t_bwd = pass_ms["backward_pass"] * 1e-3 - t_fin
-        else:
-            t_fwd, t_bwd = t_fwd_iso, t_bwd_iso
-        traffic, traffic_file = ({}, None) if dry else load_traffic((B, C, N))
-
-        def roof(bytes_per_sample, t, which=None):
-            a = bytes_per_sample * units / t / 1e9
-            return {"bound": "hbm", "achieved": round(a, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(a / HBM_PEAK_GBS, 4),
-                    "traffic": traffic.get(which)}
-
-        per_step = lambda v: round(v / args.steps * 1e3, 5)
         out = {
             "metric": "audio-samples/sec fwd+bwd, 6-band parametric_eq @ (256,2,131072)",
             "value": value, "unit": "channel-samples/s", "n_gpus": joined, "steps": args.steps, "warmup": args.warmup,
@@ -816,40 +904,21 @@ def main():
                                    "controls ~ U(ParametricEQ ranges)", "global_batch": global_batch,
                        "parallelism": f"batch-shard x{world}, no collective", "launch": mode, "world_size": joined, "shard_items": shard_items,
                        "process_group": (dist.get_backend() if dist is not None else None),
-                       "timing": f"median of {len(blocks[mode])} blocks of {args.steps} steps, product path (no timers / events in the timed region)"},
-            "launch_ms_per_step": {k: per_step(v) for k, v in med.items()},
-            "block_ms_per_step": {k: {"min": per_step(min(v)), "median": per_step(float(np.median(v))), "max": per_step(max(v))}
-                                  for k, v in blocks.items()},
-            "roofline": dict(roof(12, t_bwd, "bwd"), kernel="sos_bwd_gram_kernel<6>", ms=round(t_bwd * 1e3, 4),
-                             algorithmic_bytes=12 * units),
-            "roofline_fwd": dict(roof(8, t_fwd, "fwd"), kernel="sos_fwd_kernel<6>", ms=round(t_fwd * 1e3, 4), algorithmic_bytes=8 * units),
-            "roofline_fwd_bwd": dict(roof(20, t_fwd + t_bwd, "both"), ms=round((t_fwd + t_bwd) * 1e3, 4), algorithmic_bytes=20 * units),
-            "small_kernels_ms": round(t_small * 1e3, 4),
-            # how the two durations above were measured: in situ (the step as two graph replays with one event between them; roofline.ms =
-            # the backward pass minus the finalize kernel's isolated duration, launch gap included) - and, for comparison, the isolated
-            # per-entry-point event durations of the four-call instrumented step, which read power-limited kernels fast
-            "passes_ms": None if pass_ms is None else {k: round(v, 4) for k, v in pass_ms.items()},
-            "isolated_events_ms": {"fwd": round(t_fwd_iso * 1e3, 4), "bwd": round(t_bwd_iso * 1e3, 4), "design": round(t_prep * 1e3, 4), "finalize": round(t_fin * 1e3, 4)},
-            # the same kernels' average durations in the newest committed rocprofv3 summary of this command (another run, possibly another
-            # box; profiles/rNN/bench_kernel_stats.csv) and the roofline fractions they give on the same algorithmic bytes
-            "rocprofv3_committed": (lambda pk: None if pk is None or (B, C, N) != (256, 2, 131072) else {
-                "file": pk["file"], "bwd_ms": round(pk["bwd"], 4), "fwd_ms": round(pk["fwd"], 4),
-                "bwd_frac": round(12 * units / (pk["bwd"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                "fwd_frac": round(8 * units / (pk["fwd"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})(profiled_kernel_ms()),
-            # consistency of the event pass with the timed step: the four kernels' event durations over the step (gaps between the kernels
-            # are the rest; a ratio well below ~0.97 means the instrumented pass ran the kernels at another clock than the timed step did)
-            "kernel_events_over_step": round(((pass_ms["forward_pass"] + pass_ms["backward_pass"]) * 1e-3 if pass_ms is not None else (t_fwd + t_bwd + t_small)) / (dt / args.steps), 4),
+                       "timing": f"one block of {args.steps} steps in the {mode} launch mode"
+                                 + (f" (the faster by a {args.probe_steps}-step probe of each)" if probe_ms else "")
+                                 + ", product path (no timers / events in the timed region)"},
+            "probe_ms_per_step": {k: round(v, 5) for k, v in probe_ms.items()},
             # the same rate in frames (B N per step over all ranks) and the step as achieved HBM rate on its algorithmic bytes
             "frames_per_s": value / C,
             "step_algorithmic_GBps_per_gpu": round(20 * units / (dt / args.steps) / 1e9, 1),
-            "traffic_file": traffic_file, "kernel_source_hash": kernel_source_hash(),
-            "finite": finite,
         }
+        if args.full:
+            out.update(full_fields(args, blocks, ktimes, pass_ms, dt, units, (B, C, N), dry, finite))
         if dry:
             out["dry_run"] = "CPU wiring test: kernels replaced by a copy, numbers are meaningless"
-        if world == 1 and not args.no_secondary and not dry:
+        if args.full and world == 1 and not args.no_secondary and not dry:
             out["secondary"] = secondary(dev, skip_default_noise=args.no_default_noise_rows)
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             out["cpu_baseline"] = cpu_baseline(full=args.cpu_baseline_full)
         print(json.dumps(out))
     if dist is not None:

@@ -10,7 +10,7 @@ cp $(find $out/rprof -name "*kernel_stats.csv" | head -1) $out/mtrand_kernel_sta
 done
 timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -8 | tee $out/pytest_gpu.log
 timeout 900 bash scripts/ops_traffic.sh $out/hbm_traffic_ops.json 2>&1 | tail -3
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_c.json 2> $out/bench_c.err; tail -3 $out/bench_c.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_c.json 2> $out/bench_c.err; tail -3 $out/bench_c.err
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r06/bench_c.json").read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ for b in 8 128; do
 cp $(find $out/rprof -name "*kernel_stats.csv" | head -1) $out/mtrand_kernel_stats_b$b.csv; rm -rf $out/rprof; head -4 $out/mtrand_kernel_stats_b$b.csv | cut -c1-200
 done
 timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -5 | tee $out/pytest_gpu.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_g.json 2> $out/bench_g.err; tail -2 $out/bench_g.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_g.json 2> $out/bench_g.err; tail -2 $out/bench_g.err
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r06/bench_g.json").read().strip().splitlines()[-1])

@@ -214,7 +214,7 @@ def test_bench_rank_wiring_under_torchrun(scaling):
     import json
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--scaling", scaling, "--dry-run-cpu", "--batch", "6", "--samples", "2048"]
+           "--scaling", scaling, "--dry-run-cpu", "--batch", "6", "--samples", "2048", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -261,7 +261,7 @@ def test_bench_gpus_flag_means_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "2", "--dry-run-cpu",
-           "--batch", "4", "--samples", "1024"]
+           "--batch", "4", "--samples", "1024", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -274,3 +274,37 @@ def test_bench_gpus_flag_means_ranks():
                          capture_output=True, text=True, timeout=120,
                          env=dict(env, RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port())))
     assert bad.returncode != 0 and "refusing" in (bad.stderr + bad.stdout)
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline keys only; --dump-outputs writes the last step's
+    y / x.grad sample and the control gradients as float32 .npy, identical from run to run with the same arguments."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "1"
+    dumps = []
+    for i in range(2):
+        d = str(tmp_path / f"run{i}")
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dry-run-cpu",
+               "--batch", "4", "--samples", str(1 << 20), "--dump-outputs", d]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+            assert key in out, key
+        for key in ("roofline", "block_ms_per_step", "launch_ms_per_step", "secondary", "cpu_baseline", "finite"):
+            assert key not in out, key
+        assert out["steps"] == 3 and out["config"]["timing"].startswith("one block of 3 steps")
+        assert abs(out["value"] - 4 * 2 * (1 << 20) / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        files = {n: np.load(os.path.join(d, n + ".npy")) for n in ("y_sample", "grad_x_sample", "grad_controls")}
+        assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in files)
+        assert files["y_sample"].shape == files["grad_x_sample"].shape == (1 << 22,) and files["grad_controls"].shape == (4, 18)
+        assert all(a.dtype == np.float32 for a in files.values())
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 << 20
+        dumps.append(files)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

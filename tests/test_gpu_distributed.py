@@ -86,7 +86,7 @@ def test_bench_under_torchrun_one_process():
     through the backend), one JSON line with n_gpus = ranks that joined = 1."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port",
            str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--blocks", "2", "--no-secondary",
-           "--no-cpu-baseline", "--ramp-seconds", "0.2"]
+           "--no-cpu-baseline", "--ramp-seconds", "0.2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=560, env=_env())
     _log("rccl_bench_torchrun1.log", r.stdout + "\n--- stderr ---\n" + r.stderr[-4000:])
     assert r.returncode == 0, r.stderr[-3000:]
