@@ -95,6 +95,9 @@ SIGNATURES = {
     "dasp_lfilter_work_doubles": (_l, [_i, _l, _i, _l]),
     "dasp_lfilter_forward": (_i, [_p, _p, _p, _i, _p, _p, _p, _l, _i, _l, _i, _i, _l, _p]),
     "dasp_lfilter_backward": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l, _i, _i, _l, _p]),
+    "dasp_freqz_work_doubles": (_l, [_i, _i, _i, _i, _l]),
+    "dasp_freqz_forward": (_i, [_p, _p, _i, _i, _i, _i, _l, _i, _p, _p]),
+    "dasp_freqz_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _i, _p, _l, _p, _p, _p]),
     "dasp_sos64_normalize": (_i, [_p, _i, _i, _p, _p]),
     "dasp_sos64_forward": (_i, [_p, _i, _p, _p, _p, _i, _i, _l, _i, _p]),
     "dasp_sos64_backward": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _l, _i, _p]),

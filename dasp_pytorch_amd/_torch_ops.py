@@ -176,6 +176,15 @@ def _register_fakes():
             nA, nH, nir = (ctx.new_dynamic_size() if save else 0), ctx.new_dynamic_size(), ctx.new_dynamic_size()
         return f32(x, B, 2, N), f32(x, nA), f32(x, nH), f32(x, nir)
 
+    # ---- frequency responses (signal.fft_freqz / fft_sosfreqz)
+    @torch.library.register_fake("dasp::freqz")
+    def _(b, a, n_fft):
+        return b.new_empty((b.shape[0], n_fft // 2 + 1), dtype=torch.complex128 if b.dtype == torch.float64 else torch.complex64)
+
+    @torch.library.register_fake("dasp::_freqz_backward")
+    def _(b, a, grad_H, n_fft):
+        return like(b), like(a)
+
     @torch.library.register_fake("dasp::_reverb_backward")
     def _(grad_y, ir, A, H, noise, fspec, gains, decays, mix, Cx, num_samples, taps, bands, seed, seed_offset, decay_bound):
         B, _, N = grad_y.shape

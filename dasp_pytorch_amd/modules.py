@@ -375,6 +375,34 @@ class ParametricEQ(Processor):
         self._check_range(param_tensor)
         return parametric_eq_norm(x, param_tensor, float(self.sample_rate), F._PEQ_TYPES, lo, span, _range_flag)
 
+    def frequency_response(self, param_tensor: torch.Tensor, n_fft: int = 16384):
+        """Complex frequency response (bs, n_fft // 2 + 1) of the EQ that process_normalized(x, param_tensor) applies, differentiable
+        w.r.t. `param_tensor` (bs, 18) on [0, 1]: de-normalised and range-checked as process_normalized does (validate_range in any of
+        its modes), the six sections designed by signal.biquad (low shelf, four peaking bands, high shelf; fp64 on the device) and
+        evaluated by signal.fft_sosfreqz. Bin k is at k * sample_rate / n_fft Hz: torch.fft.rfftfreq(n_fft, 1 / sample_rate) gives the
+        frequencies; they are left to the caller. A response-matching loss is e.g. 20 * torch.log10(H.abs()) against a target curve.
+        A processor whose process_fn was replaced, or whose parameter ranges were renamed, raises NotImplementedError: its filter is not
+        the one designed here."""
+        from . import signal
+        if self.process_fn is not F.parametric_eq or list(self.param_ranges) != _EQ_NAMES:
+            # the six RBJ sections below are what functional.parametric_eq applies, in its column order: another process_fn or renamed
+            # ranges would make this the response of some other filter than the one process_normalized runs
+            raise NotImplementedError("ParametricEQ.frequency_response: the response is designed as functional.parametric_eq's six sections "
+                                      f"({', '.join(_EQ_NAMES[::3])}...); this processor has process_fn = {getattr(self.process_fn, '__name__', self.process_fn)} "
+                                      f"and parameters {list(self.param_ranges)[:3]}...")
+        if param_tensor.shape[1] != len(self.param_ranges):
+            raise ValueError(
+                f"Parameter tensor has {param_tensor.shape[1]} parameters, but processor has {len(self.param_ranges)} parameters.")
+        self._check_range(param_tensor)
+        lo, span = self._affine(param_tensor)
+        d = param_tensor * span + lo
+        kinds = ("low_shelf", "peaking", "peaking", "peaking", "peaking", "high_shelf")
+        sections = []
+        for i, kind in enumerate(kinds):
+            b, a = signal.biquad(d[:, 3 * i], d[:, 3 * i + 1], d[:, 3 * i + 2], self.sample_rate, kind)
+            sections.append(torch.cat([b, a], -1))
+        return signal.fft_sosfreqz(torch.stack(sections, 1), n_fft)
+
 
 class _Dynamics(Processor):
     def __init__(self, fn, sample_rate: int, min_threshold_db: float = -60.0, max_threshold_db: float = 0.0, min_ratio: float = 1.0,

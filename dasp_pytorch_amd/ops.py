@@ -5,6 +5,9 @@ registered with TORCH_LIBRARY, forward + hand-derived adjoint as C++ torch::auto
 torch.compile, opcheck-clean. Everything else - float64, the ops the extension does not register, config.plan.torch_ops = False, a tree
 without libdasp_torch.so - takes the ctypes autograd.Functions of _ctypes_ops.py (same kernels, same C entry points; what changes is
 the host side: ctypes marshalling and Python in the backward pass), which also own the dtype / device error messages.
+
+The exception is `freqz` (signal.fft_freqz / fft_sosfreqz): it exists only as torch.ops.dasp.freqz, for float32 and float64 alike and
+whatever config.plan.torch_ops says (there is no second binding to compare it with). Without libdasp_torch.so it raises DaspHipError.
 """
 import ctypes
 
@@ -155,3 +158,14 @@ def noise_shaped_reverb(x, noise, filters, band_gains, band_decays, mix, L_ir, s
     taps = filters.shape[1]
     return torch.ops.dasp.noise_shaped_reverb(x, list(band_gains), list(band_decays), mix, noise, _reverb_fspec(x, filters, L_ir), int(L_ir), int(taps),
                                               _signed64(seed), _seed_offset(seed_offset, x.device) if noise is None else None, float(decay_bound))
+
+
+def freqz(b, a, n_fft):
+    """torch.ops.dasp.freqz: H (rows, n_fft // 2 + 1) of the cascades b (rows, S, Kb) / a (rows, S, Ka), complex64 for float32 and
+    complex128 for float64, differentiable w.r.t. b and a (csrc/freqz.hip). No ctypes binding: without the extension this raises."""
+    from . import _torch_ops
+    loaded = _torch_ops._state["loaded"] is True if torch.compiler.is_compiling() else _torch_ops.load()
+    if not loaded:
+        raise _lib.DaspHipError(f"{_torch_ops.EXT_PATH} (libdasp_torch.so) is not built or does not load: fft_freqz / fft_sosfreqz run only "
+                                "through torch.ops.dasp.freqz. Build it with `python -m dasp_pytorch_amd.csrc.build` (or __graft_entry__.build())")
+    return torch.ops.dasp.freqz(b, a, int(n_fft))

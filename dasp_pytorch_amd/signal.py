@@ -5,13 +5,18 @@ recurrence (chunked parallel scan, csrc/sosfilt.hip) instead of the reference's 
 approximation; the two agree to <= 1e-13 in fp64 for stable filters whose impulse response has
 decayed within the signal length. float64 input takes the double-precision
 kernels of csrc/ref64.hip (ops64.py): float64 in, float64 arithmetic, as in the reference.
+
+`fft_freqz` / `fft_sosfreqz` keep the reference's frequency responses: evaluated per bin in fp64 (csrc/freqz.hip) instead of through
+zero-padded FFTs, for float32 and float64 alike, with a hand-written adjoint. `freqdomain_fir` still raises (it needs an FFT of any length).
 """
 import functools
+import operator
 
 import numpy as np
 import scipy.signal
 import torch
 
+from . import _lib
 from . import ops as _ops
 from .ops import FILTER_TYPES, BiquadFunction, SosFiltFunction
 from .ops64 import LFilterFunction, SosFilt64Function, is_f64
@@ -88,11 +93,75 @@ def _frequency_domain_helper(name, line):
 # The reference's L1 helpers of the frequency-sampling method are not part of this package's boundary; they exist as names
 # so that `from dasp_pytorch_amd.signal import *` fails loudly at the call, not at import. one_pole_butter_lowpass / one_pole_filter
 # are dead code in the reference (they print to stdout).
-fft_freqz = _frequency_domain_helper("fft_freqz", "7-11")
-fft_sosfreqz = _frequency_domain_helper("fft_sosfreqz", "14-32")
 freqdomain_fir = _frequency_domain_helper("freqdomain_fir", "35-39")
 one_pole_butter_lowpass = _frequency_domain_helper("one_pole_butter_lowpass", "169-198")
 one_pole_filter = _frequency_domain_helper("one_pole_filter", "201-239")
+
+
+FREQZ_MAX_TAPS = 32           # per polynomial of fft_freqz (csrc/freqz.hip evaluates every bin directly)
+FREQZ_MAX_SECTIONS = 16       # of fft_sosfreqz
+
+
+def _freqz_n(n_fft):
+    """n_fft as a Python int: an integer or a 0-dim integer tensor (the reference's sosfilt_via_fsm passes one, signal.py:150-151)."""
+    if isinstance(n_fft, torch.Tensor):
+        if n_fft.dim() != 0 or n_fft.is_floating_point() or n_fft.is_complex():
+            raise TypeError(f"n_fft must be an integer or a 0-dim integer tensor, got a {n_fft.dtype} tensor of shape {tuple(n_fft.shape)}")
+        n_fft = n_fft.item()
+    n = operator.index(n_fft)
+    if n < 1:
+        raise ValueError(f"n_fft must be >= 1, got {n}")
+    return n
+
+
+def _freqz_dtype(*tensors):
+    """float64 if the inputs promote to float64, else float32 (the kernels compute in fp64 either way and store in this precision)."""
+    dt = functools.reduce(torch.promote_types, [t.dtype for t in tensors])
+    if not dt.is_floating_point:
+        raise TypeError(f"filter coefficients must be real floating-point tensors, got {', '.join(str(t.dtype) for t in tensors)}")
+    return torch.float64 if dt == torch.float64 else torch.float32
+
+
+def fft_freqz(b: torch.Tensor, a: torch.Tensor, n_fft: int = 512):
+    """Complex frequency response H = rfft(b, n_fft) / rfft(a, n_fft) (reference: dasp_pytorch/signal.py:7-11), shape (..., n_fft // 2 + 1).
+
+    b (..., Kb) and a (..., Ka) are real; their leading shapes broadcast. a0 is not normalised. Taps beyond n_fft are cropped, as
+    torch.fft.rfft crops its input; n_fft is any integer >= 1 or a 0-dim integer tensor. Evaluated per bin in fp64 (csrc/freqz.hip,
+    through torch.ops.dasp.freqz) instead of two FFTs: complex64 out for float32 in, complex128 for float64. Differentiable w.r.t. b
+    and a. At most 32 taps each: a longer FIR wants an FFT, not a per-bin polynomial (NotImplementedError)."""
+    _lib.require_device(b, "b")
+    _lib.require_device(a, "a")
+    _lib.require_same_device(b, a=a)
+    n = _freqz_n(n_fft)
+    dt = _freqz_dtype(b, a)
+    if b.dim() < 1 or a.dim() < 1 or b.shape[-1] < 1 or a.shape[-1] < 1:
+        raise ValueError(f"fft_freqz: b and a need at least one tap, got shapes {tuple(b.shape)} and {tuple(a.shape)}")
+    b, a = b[..., :n], a[..., :n]
+    Kb, Ka = b.shape[-1], a.shape[-1]
+    if max(Kb, Ka) > FREQZ_MAX_TAPS:
+        raise NotImplementedError(f"fft_freqz: {Kb} numerator / {Ka} denominator taps (after cropping to n_fft = {n}); polynomials of up to "
+                                  f"{FREQZ_MAX_TAPS} taps are evaluated per bin. A longer FIR wants an FFT, not a per-bin polynomial: "
+                                  "torch.fft.rfft(b, n_fft), or factor the filter into second-order sections and call fft_sosfreqz")
+    lead = torch.broadcast_shapes(b.shape[:-1], a.shape[:-1])
+    bb = b.to(dt).expand(*lead, Kb).reshape(-1, 1, Kb)
+    aa = a.to(dt).expand(*lead, Ka).reshape(-1, 1, Ka)
+    return _ops.freqz(bb, aa, n).reshape(*lead, n // 2 + 1)
+
+
+def fft_sosfreqz(sos: torch.Tensor, n_fft: int = 512):
+    """Complex frequency response of a cascade of biquads, H = prod_s B_s / A_s (reference: dasp_pytorch/signal.py:14-32).
+
+    sos: (bs, n_sections, 6) rows [b0 b1 b2 a0 a1 a2], 1 to 16 sections -> H (bs, n_fft // 2 + 1), complex64 for float32 and complex128
+    for float64. One kernel evaluates every section per bin in fp64 (csrc/freqz.hip); differentiable w.r.t. sos."""
+    bs, n_sections, n_coeffs = sos.size()
+    assert n_coeffs == 6  # must be second order (signal.py:24)
+    _lib.require_device(sos, "sos")
+    n = _freqz_n(n_fft)
+    if not 1 <= n_sections <= FREQZ_MAX_SECTIONS:
+        raise NotImplementedError(f"fft_sosfreqz: {n_sections} sections; 1 to {FREQZ_MAX_SECTIONS} are evaluated in one call "
+                                  "(multiply the responses of successive calls for a longer cascade)")
+    s = sos.to(_freqz_dtype(sos))
+    return _ops.freqz(s[..., :3], s[..., 3:], n)
 
 
 def sosfilt_via_fsm(sos: torch.Tensor, x: torch.Tensor):

@@ -438,6 +438,22 @@ int dasp_lfilter_backward(const void* gy, const double* bn, const double* an, in
                           double* ga, double* work, long work_doubles, int rows, long N, int K, int f64, long chunk, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Frequency responses.  Replaces dasp_pytorch.signal.fft_freqz (dasp_pytorch/signal.py:7-11) and fft_sosfreqz (:14-32): the response of
+ * a cascade of S rational sections on the rFFT grid, H_k = prod_s B_s(z_k) / A_s(z_k), z_k = e^{-2 pi i k / n}, k = 0 .. n/2, evaluated
+ * per bin in fp64 (csrc/freqz.hip) instead of two zero-padded FFTs per section. a0 is not normalised; taps j >= n_fft are cropped, as
+ * torch.fft.rfft crops its input.
+ *   b: (rows, S, Kb), a: (rows, S, Ka) contiguous, float (f64 = 0) or double (f64 = 1);  H, gH: (rows, n_fft/2 + 1) interleaved complex
+ *   of the same precision;  gb, ga: like b, a (gradient sum_k Re(conj(dH_k/dc) gH_k));  1 <= S <= 16, 1 <= Kb, Ka <= 32 and at most 96
+ *   terms S (min(Kb, n) + min(Ka, n)), else DASP_ERR_UNSUPPORTED;  work: dasp_freqz_work_doubles(...) doubles of scratch, its size passed
+ *   as work_doubles (checked: DASP_ERR_ARG). The backward call is two launches (partials per workgroup, then a finalize that sums them in
+ *   a fixed order): no float atomics, bit-identical results run to run.
+ * ------------------------------------------------------------------------------------------- */
+long dasp_freqz_work_doubles(int rows, int S, int Kb, int Ka, long n_fft);
+int dasp_freqz_forward(const void* b, const void* a, int rows, int S, int Kb, int Ka, long n_fft, int f64, void* H, void* stream);
+int dasp_freqz_backward(const void* b, const void* a, const void* gH, int rows, int S, int Kb, int Ka, long n_fft, int f64, double* work,
+                        long work_doubles, void* gb, void* ga, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Double precision.  The reference follows the dtype of its input (`.type_as(x)`, dasp_pytorch/signal.py:113,119,
  * functional.py:211), so float64 tensors mean float64 arithmetic. These entry points are that path for the recurrences and the
  * elementwise effects - the same maps as above evaluated plainly, one thread per row / batch item, sequential in time: meant for
