@@ -310,16 +310,29 @@ template <int DIR> __device__ __forceinline__ void cmul_dir(float& re, float& im
     re = t;
 #endif
 }
+// w_P^e from the 4096-entry table. MAXLOG = 13 adds P = 8192 (col_config<13>, 1024 threads): an even exponent is an entry of the table,
+// an odd one (only the closing radix-2 pass has them) the entry below times w_8192 (one complex product, ~1 ulp)
+template <int MAXLOG> __device__ __forceinline__ f2 col_twiddle(const f2* __restrict__ tw, int e, int logP) {
+    if constexpr (MAXLOG <= 12) {
+        return tw[e * (FFT_N >> logP)];
+    } else {
+        if (logP <= 12) return tw[e * (FFT_N >> logP)];
+        const f2 w = tw[e >> 1];
+        if (!(e & 1)) return w;
+        constexpr float c = 0.99999970586288224f, s = -7.669903187427045e-4f;     // w_8192 = exp(-2 pi i / 8192)
+        return f2{w.x * c - w.y * s, w.x * s + w.y * c};
+    }
+}
 // tw = the 4096-entry forward table; the twiddles of a pass are formed right before it (workgroups that run one transform per
 // thread have nothing to amortise them over, and keeping all of them live costs ~50 VGPRs)
-template <int DIR>
+template <int DIR, int MAXLOG = 12>
 __device__ __forceinline__ void col_fft(float (&r)[8], float (&i)[8], const ColCfg& g, const f2* __restrict__ tw, f2* lds) {
-    const int a = g.logP / 3, mul = FFT_N >> g.logP;          // w_P^e = tw[e * mul]
+    const int a = g.logP / 3;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (k < a) {                                   // workgroup-uniform
             const int Ns = 1 << (3 * k);
-            if (k > 0) twiddle8<DIR>(r, i, tw_powers(tw[((g.j & (Ns - 1)) * (g.P >> (3 * k + 3))) * mul]));
+            if (k > 0) twiddle8<DIR>(r, i, tw_powers(col_twiddle<MAXLOG>(tw, (g.j & (Ns - 1)) * (g.P >> (3 * k + 3)), g.logP)));
             radix8<DIR>(r, i);
             if (Ns * 8 < g.P) col_exchange(r, i, lds, g, ((g.j >> (3 * k)) << (3 * k + 3)) + (g.j & (Ns - 1)), Ns);
         }
@@ -330,7 +343,7 @@ __device__ __forceinline__ void col_fft(float (&r)[8], float (&i)[8], const ColC
         for (int m = 0; m < 2; ++m) {
 #pragma unroll
             for (int k = 1; k < 4; ++k) {
-                const f2 w = tw[(((g.j + g.T * m) * k) & (g.P - 1)) * mul];
+                const f2 w = col_twiddle<MAXLOG>(tw, ((g.j + g.T * m) * k) & (g.P - 1), g.logP);
                 cmul_dir<DIR>(r[m + 2 * k], i[m + 2 * k], w.x, w.y);
             }
             dft4<DIR>(r[m], i[m], r[m + 2], i[m + 2], r[m + 4], i[m + 4], r[m + 6], i[m + 6]);
@@ -338,7 +351,7 @@ __device__ __forceinline__ void col_fft(float (&r)[8], float (&i)[8], const ColC
     } else if (R == 2) {                               // four radix-2 butterflies on registers (m, m+4), u = j + T m
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            const f2 w = tw[(g.j + g.T * m) * mul];
+            const f2 w = col_twiddle<MAXLOG>(tw, g.j + g.T * m, g.logP);
             cmul_dir<DIR>(r[m + 4], i[m + 4], w.x, w.y);
             const float ar = r[m], ai = i[m];
             r[m] = ar + r[m + 4]; i[m] = ai + i[m + 4];

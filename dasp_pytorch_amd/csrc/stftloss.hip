@@ -9,21 +9,28 @@
 // one signal row. The frames of the two signals are gathered (reflect padding, periodic Hann window zero-padded to n_fft) as ONE
 // complex signal p + i t and transformed - frames of 512 / 1024 / 2048 points (the default resolutions) as 1 / 2 / 4 interleaved
 // 512-point transforms, one per wave, with at most one workgroup barrier (split kernels, below); any other power of two with col_fft
-// (fft_lds.hpp: frames side by side in registers + LDS) -, split into the two
-// one-sided spectra through the mirrored bin, reduced to the three sums of a resolution
-//   S1 = sum (|T| - |P|)^2,  S2 = sum |T|^2,  S3 = sum |log|P| - log|T||       (|.| = sqrt(max(re^2 + im^2, eps)))
-// per workgroup; a finalize kernel adds them in fp64:  loss = mean_r( sqrt(S1)/sqrt(S2) + S3 / count ).
+// (fft_lds.hpp: frames side by side in registers + LDS; 8192 points: one frame per 1024-thread workgroup) -, split into the two
+// one-sided spectra through the mirrored bin, reduced to the four sums of a resolution
+//   S1 = sum (|T| - |P|)^2,  S2 = sum |T|^2,  S3 = sum |log|P| - log|T||,  S4 = sum ||T| - |P||       (|.| = sqrt(max(re^2 + im^2, eps)))
+// per workgroup; a finalize kernel adds them in fp64:  loss = mean_r( w_sc sqrt(S1)/sqrt(S2) + w_lm S3 / count + w_lin S4 / count ),
+// weights (1, 1, 0) by default. The A-weighting FIR of auraloss's perceptual weighting has kernels of its own (end of the file).
 // Backward recomputes the spectra, forms dL/d|P| * P/|P| on the one-sided bins, runs the inverse transform of that half spectrum and
 // scatters window * Re(.) back through the frame overlap and the reflect padding with float atomics (each sample receives
 // ~n_fft/hop contributions; the summation order, and only that, is not deterministic). Spectrograms never exist in HBM.
 #include "common.hpp"
 #include "fft_lds.hpp"
 
+#include <cmath>
+
 namespace dasp {
 
 constexpr int SL_MAXRES = 8;
 struct StftRes { int logF, hop, win, frames; };
-struct StftSpec { StftRes r[SL_MAXRES]; int nres, groups; float eps; };
+// w_sc, w_lm, w_lin: the term weights of auraloss (spectral convergence, log-magnitude L1, linear-magnitude L1); a weight of exactly 0
+// drops its term from the loss and from the gradient (auraloss: `... if self.w_sc else 0.0`), so w_sc = 0 with a silent target stays finite
+struct StftSpec { StftRes r[SL_MAXRES]; int nres, groups; float eps, w_sc, w_lm, w_lin; };
+// frames of one resolution per workgroup: 4096 / n_fft up to 4096 points, one 8192-point frame per 1024-thread workgroup
+__host__ __device__ __forceinline__ int frames_per_group(int logF) { return FFT_N >> (logF < 12 ? logF : 12); }
 
 __global__ void stft_twiddle_kernel(f2* __restrict__ tw) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -47,37 +54,57 @@ __device__ __forceinline__ Bin split_bin(float zr, float zi, float mr, float mi)
     return Bin{0.5f * (zr + mr), 0.5f * (zi - mi), 0.5f * (zi + mi), -0.5f * (zr - mr)};
 }
 
-// one bin's contribution to the three sums of a resolution
-__device__ __forceinline__ void loss_terms(const Bin& b, float eps, float& s1, float& s2, float& s3) {
+// one bin's contribution to the four sums of a resolution
+__device__ __forceinline__ void loss_terms(const Bin& b, float eps, float& s1, float& s2, float& s3, float& s4) {
     const float p2 = fmaxf(b.pr * b.pr + b.pi * b.pi, eps), t2 = fmaxf(b.tr * b.tr + b.ti * b.ti, eps);
     const float pm = __builtin_amdgcn_sqrtf(p2), tm = __builtin_amdgcn_sqrtf(t2);      // operands in [eps, ~1e6]: the plain instructions are exact enough (1 ulp)
     s1 = fmaf(tm - pm, tm - pm, s1);
     s2 += t2;
     s3 += 0.5f * fabsf(__logf(__fdividef(p2, t2)));       // |log pm - log tm| = |log(p2 / t2)| / 2; the ratio stays within 1e-14 .. 1e14
+    s4 += fabsf(tm - pm);
 }
 // one bin of the gradient spectrum: dL/d|P| * P / |P|
 // k_self: the gradient w.r.t. the SECOND signal of the loss (the kernels are then called with the two signals swapped): the spectral
 // convergence term is normalised by that signal's own norm, d/d|T| (s1 / s2) = (|T| - |P|) / (s1 s2) - s1 |T| / s2^3 - the first part is what
-// the swapped call computes anyway, the second is k_self = - s1 / s2^3 times the spectrum itself; the log-magnitude term is symmetric.
-__device__ __forceinline__ void grad_bin(const Bin& b, float eps, float k_sc, float k_lm, float k_self, float& hr, float& hi) {
+// the swapped call computes anyway, the second is k_self = - s1 / s2^3 times the spectrum itself; the two magnitude terms are symmetric.
+// Linear-magnitude L1: d/d|P| |(|T| - |P|)| = -sign(|T| - |P|), times k_lin = w_lin gl / count. Each constant carries its term's weight.
+struct GradK { float sc, lm, lin, self; };
+__device__ __forceinline__ GradK grad_consts(const StftSpec& spec, const float* __restrict__ stats, const float* __restrict__ gloss, int res, int wrt_second) {
+    const float s1 = stats[res * 4], s2 = stats[res * 4 + 1], count = stats[res * 4 + 2];
+    const float gl = gloss[0] / (float)spec.nres;
+    GradK k;
+    k.sc = spec.w_sc != 0.f && s1 > 0.f ? spec.w_sc * gl / (s1 * s2) : 0.f;
+    k.lm = spec.w_lm * gl / count;
+    k.lin = spec.w_lin * gl / count;
+    k.self = wrt_second && spec.w_sc != 0.f ? -(spec.w_sc * gl) * s1 / (s2 * s2 * s2) : 0.f;
+    return k;
+}
+// LIN: the linear-magnitude term is compiled in only where w_lin != 0 (the launch selects the instance): without it the default loss's
+// backward kernels keep their register count (mrstft_bwd_split_kernel<1>: 80 VGPRs, 6 waves per SIMD; with it 82, 5 waves, 1.6 % slower)
+template <bool LIN>
+__device__ __forceinline__ void grad_bin(const Bin& b, float eps, const GradK& k, float& hr, float& hi) {
     hr = 0.f; hi = 0.f;
     const float praw = b.pr * b.pr + b.pi * b.pi;
     if (praw > eps) {                                            // the clamp has zero slope below eps
         const float tm = sqrtf(fmaxf(b.tr * b.tr + b.ti * b.ti, eps)), pm = sqrtf(praw);
         const float sgn = tm > pm ? 1.f : (tm < pm ? -1.f : 0.f);            // sign(log tm - log pm)
-        const float gm = (k_sc * (pm - tm) - k_lm * sgn / pm) / pm + k_self;  // dL/d|P| / |P|
+        float d = k.sc * (pm - tm) - k.lm * sgn / pm;
+        if constexpr (LIN) d -= k.lin * sgn;
+        const float gm = d / pm + k.self;                                    // dL/d|P| / |P|
         hr = gm * b.pr; hi = gm * b.pi;
     }
 }
 
 // gather + window + forward transform of this thread's 8 samples of its frame; afterwards r/i = Z[j + T q] and mr/mi = Z[F - (j + T q)]
 // the window of a resolution, once per workgroup (all its frames share it): wlds[n] = hann_in_frame(n), n < F; a barrier follows in the caller's path
+template <int NT = 512>
 __device__ __forceinline__ void window_to_lds(float* wlds, const StftRes& R) {
     const int F = 1 << R.logF;
-    for (int n = threadIdx.x; n < F; n += 512) wlds[n] = hann_in_frame(n, F, R.win);
+    for (int n = threadIdx.x; n < F; n += NT) wlds[n] = hann_in_frame(n, F, R.win);
     __syncthreads();
 }
 
+template <int LOGN>
 __device__ __forceinline__ void frames_to_spectra(const float* __restrict__ prow, const float* __restrict__ trow, int N, int frame, bool live,
                                                   const StftRes& R, const ColCfg& g, const f2* __restrict__ tw, f2* lds, const float* wlds,
                                                   float (&r)[8], float (&i)[8], float (&mr)[8], float (&mi)[8]) {
@@ -95,7 +122,7 @@ __device__ __forceinline__ void frames_to_spectra(const float* __restrict__ prow
         const float w = live ? wlds[g.j + g.T * q] : 0.f;
         r[q] *= w; i[q] *= w;
     }
-    col_fft<-1>(r, i, g, tw, lds);
+    col_fft<-1, LOGN>(r, i, g, tw, lds);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 8; ++q) lds[fft_pad(g.j + g.T * q) * g.TC + g.c] = f2{r[q], i[q]};
@@ -108,39 +135,43 @@ __device__ __forceinline__ void frames_to_spectra(const float* __restrict__ prow
     __syncthreads();       // the caller may reuse lds for another transform
 }
 
-// One launch per resolution. These two kernels take any power of two 8 .. 4096 (col_fft with run-time geometry); frames of 512, 1024 and
-// 2048 points - the default resolutions - run the split kernels further down.
-// partials[((res * rows + row) * groups + group) * 3 + {0, 1, 2}]
-__global__ void __launch_bounds__(512)
+// One launch per resolution. These two kernels take any power of two 8 .. 4096 (LOGN = 12: col_fft with run-time geometry in a
+// 512-thread workgroup) and 8192 (LOGN = 13: one frame per 1024-thread workgroup, 8 points per thread, four radix-8 passes and a radix-2
+// pass); frames of 512, 1024 and 2048 points - the default resolutions - run the split kernels further down.
+// partials[((res * rows + row) * groups + group) * 4 + {0, 1, 2, 3}]
+template <int LOGN>
+__global__ void __launch_bounds__(ColGeom<LOGN>::T)
 mrstft_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, const f2* __restrict__ tw, float* __restrict__ partials,
                   StftSpec spec, int N, int res) {
-    __shared__ f2 lds[ColGeom<12>::LDS];
-    __shared__ float wlds[FFT_N];
-    __shared__ float red[8][3];
-    const StftRes R = spec.r[res];
-    const ColCfg g = col_config<12>(R.logF, threadIdx.x);
+    constexpr int NT = ColGeom<LOGN>::T, NW = NT / 64;
+    __shared__ f2 lds[ColGeom<LOGN>::LDS];
+    __shared__ float wlds[1 << LOGN];
+    __shared__ float red[NW][4];
+    StftRes R = spec.r[res];
+    if constexpr (LOGN == 13) R.logF = 13;                  // the only size this instance runs: compile-time geometry
+    const ColCfg g = col_config<LOGN>(R.logF, threadIdx.x);
     const int row = blockIdx.y, F = 1 << R.logF;
     if ((int)blockIdx.x * g.TC >= R.frames) return;          // uniform: this resolution has fewer frame groups than the grid
     const int frame = blockIdx.x * g.TC + g.c;
     const bool live = frame < R.frames;
-    window_to_lds(wlds, R);
+    window_to_lds<NT>(wlds, R);
     float r[8], i[8], mr[8], mi[8];
-    frames_to_spectra(pred + (size_t)row * N, target + (size_t)row * N, N, frame, live, R, g, tw, lds, wlds, r, i, mr, mi);
-    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    frames_to_spectra<LOGN>(pred + (size_t)row * N, target + (size_t)row * N, N, frame, live, R, g, tw, lds, wlds, r, i, mr, mi);
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int k = g.j + g.T * q;
         if (live && k <= F / 2) {
-            loss_terms(split_bin(r[q], i[q], mr[q], mi[q]), spec.eps, s1, s2, s3);
+            loss_terms(split_bin(r[q], i[q], mr[q], mi[q]), spec.eps, s1, s2, s3, s4);
         }
     }
-    s1 = wave_sum_uniform(s1); s2 = wave_sum_uniform(s2); s3 = wave_sum_uniform(s3);
-    if (lane_id() == 0) { red[wave_id()][0] = s1; red[wave_id()][1] = s2; red[wave_id()][2] = s3; }
+    s1 = wave_sum_uniform(s1); s2 = wave_sum_uniform(s2); s3 = wave_sum_uniform(s3); s4 = wave_sum_uniform(s4);
+    if (lane_id() == 0) { red[wave_id()][0] = s1; red[wave_id()][1] = s2; red[wave_id()][2] = s3; red[wave_id()][3] = s4; }
     __syncthreads();
-    if (threadIdx.x < 3) {
+    if (threadIdx.x < 4) {
         float a = 0.f;
-        for (int v = 0; v < 8; ++v) a += red[v][threadIdx.x];
-        partials[(((size_t)res * gridDim.y + row) * spec.groups + blockIdx.x) * 3 + threadIdx.x] = a;
+        for (int v = 0; v < NW; ++v) a += red[v][threadIdx.x];
+        partials[(((size_t)res * gridDim.y + row) * spec.groups + blockIdx.x) * 4 + threadIdx.x] = a;
     }
 }
 // step 1, one workgroup per (resolution, sum): stats[res * 4 + c] = S_c, added up in fp64. 16 waves walk the rows, the lanes the
@@ -148,15 +179,15 @@ mrstft_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ targ
 __global__ void __launch_bounds__(1024)
 mrstft_reduce_kernel(const float* __restrict__ partials, StftSpec spec, int rows, float* __restrict__ stats) {
     __shared__ double red[16];
-    const int res = blockIdx.x / 3, c = blockIdx.x % 3, l = lane_id(), wv = wave_id();
-    const int TC = FFT_N >> spec.r[res].logF, ng = (spec.r[res].frames + TC - 1) / TC;
+    const int res = blockIdx.x / 4, c = blockIdx.x % 4, l = lane_id(), wv = wave_id();
+    const int TC = frames_per_group(spec.r[res].logF), ng = (spec.r[res].frames + TC - 1) / TC;
     double s = 0.0;
     for (int row = wv; row < rows; row += 16) {
-        const float* p = partials + ((size_t)res * rows + row) * spec.groups * 3 + c;
+        const float* p = partials + ((size_t)res * rows + row) * spec.groups * 4 + c;
         for (int g0 = l; g0 < ng; g0 += 256) {
             float v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { const int gi = g0 + 64 * u; v[u] = p[(size_t)(gi < ng ? gi : ng - 1) * 3]; }
+            for (int u = 0; u < 4; ++u) { const int gi = g0 + 64 * u; v[u] = p[(size_t)(gi < ng ? gi : ng - 1) * 4]; }
 #pragma unroll
             for (int u = 0; u < 4; ++u) s += g0 + 64 * u < ng ? (double)v[u] : 0.0;
         }
@@ -170,45 +201,51 @@ mrstft_reduce_kernel(const float* __restrict__ partials, StftSpec spec, int rows
         stats[res * 4 + c] = (float)t;
     }
 }
-// step 2: stats[res] = (sqrt S1, sqrt S2, count, S3); loss[0] = mean over resolutions of sqrt(S1)/sqrt(S2) + S3/count
+// step 2: stats[res] = (sqrt S1, sqrt S2, count, S3); loss[0] = mean over resolutions of
+// w_sc sqrt(S1)/sqrt(S2) + w_lm S3/count + w_lin S4/count, a term with weight 0 left out (weights 1, 1, 0: the sum of the first two as before)
 __global__ void mrstft_finalize_kernel(StftSpec spec, int rows, float* __restrict__ stats, float* __restrict__ loss) {
     if (threadIdx.x != 0) return;
     double total = 0.0;
     for (int res = 0; res < spec.nres; ++res) {
         const double F = (double)(1 << spec.r[res].logF), count = (double)rows * spec.r[res].frames * (F / 2 + 1);
         const double s1 = sqrt((double)stats[res * 4 + 0]), s2 = sqrt((double)stats[res * 4 + 1]), s3 = (double)stats[res * 4 + 2];
+        const double s4 = (double)stats[res * 4 + 3];
         stats[res * 4 + 0] = (float)s1; stats[res * 4 + 1] = (float)s2; stats[res * 4 + 2] = (float)count; stats[res * 4 + 3] = (float)s3;
-        total += s1 / s2 + s3 / count;
+        double l = 0.0;
+        if (spec.w_sc != 0.f) l += (double)spec.w_sc * (s1 / s2);
+        if (spec.w_lm != 0.f) l += (double)spec.w_lm * (s3 / count);
+        if (spec.w_lin != 0.f) l += (double)spec.w_lin * (s4 / count);
+        total += l;
     }
     loss[0] = (float)(total / spec.nres);
 }
 
 // gpred (rows, N) must be zero on entry; gloss = d(objective)/d(loss), a device scalar
-__global__ void __launch_bounds__(512)
+template <int LOGN, bool LIN>
+__global__ void __launch_bounds__(ColGeom<LOGN>::T)
 mrstft_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, const f2* __restrict__ tw, const float* __restrict__ stats,
                   const float* __restrict__ gloss, float* __restrict__ gpred, StftSpec spec, int N, int res, int wrt_second) {
-    __shared__ f2 lds[ColGeom<12>::LDS];
-    __shared__ float wlds[FFT_N];
-    const StftRes R = spec.r[res];
-    const ColCfg g = col_config<12>(R.logF, threadIdx.x);
+    __shared__ f2 lds[ColGeom<LOGN>::LDS];
+    __shared__ float wlds[1 << LOGN];
+    StftRes R = spec.r[res];
+    if constexpr (LOGN == 13) R.logF = 13;
+    const ColCfg g = col_config<LOGN>(R.logF, threadIdx.x);
     const int row = blockIdx.y, F = 1 << R.logF;
     if ((int)blockIdx.x * g.TC >= R.frames) return;
     const int frame = blockIdx.x * g.TC + g.c;
     const bool live = frame < R.frames;
-    window_to_lds(wlds, R);
+    window_to_lds<ColGeom<LOGN>::T>(wlds, R);
     float r[8], i[8], mr[8], mi[8];
-    frames_to_spectra(pred + (size_t)row * N, target + (size_t)row * N, N, frame, live, R, g, tw, lds, wlds, r, i, mr, mi);
-    const float s1 = stats[res * 4], s2 = stats[res * 4 + 1], count = stats[res * 4 + 2];
-    const float gl = gloss[0] / (float)spec.nres;
-    const float k_sc = s1 > 0.f ? gl / (s1 * s2) : 0.f, k_lm = gl / count, k_self = wrt_second ? -gl * s1 / (s2 * s2 * s2) : 0.f;
+    frames_to_spectra<LOGN>(pred + (size_t)row * N, target + (size_t)row * N, N, frame, live, R, g, tw, lds, wlds, r, i, mr, mi);
+    const GradK kk = grad_consts(spec, stats, gloss, res, wrt_second);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int k = g.j + g.T * q;
         float hr = 0.f, hi = 0.f;
-        if (live && k <= F / 2) grad_bin(split_bin(r[q], i[q], mr[q], mi[q]), spec.eps, k_sc, k_lm, k_self, hr, hi);
+        if (live && k <= F / 2) grad_bin<LIN>(split_bin(r[q], i[q], mr[q], mi[q]), spec.eps, kk, hr, hi);
         r[q] = hr; i[q] = hi;
     }
-    col_fft<1>(r, i, g, tw, lds);                                    // sum_k H[k] e^{+2 pi i k n / F}, H = 0 on the upper half
+    col_fft<1, LOGN>(r, i, g, tw, lds);                                    // sum_k H[k] e^{+2 pi i k n / F}, H = 0 on the upper half
     float* grow = gpred + (size_t)row * N;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -311,7 +348,7 @@ mrstft_fwd_split_kernel(const float* __restrict__ pred, const float* __restrict_
                         StftSpec spec, int N, int res) {
     __shared__ f2 lds[8 * FFT512_LDS];
     __shared__ float wlds[512 * R];
-    __shared__ float red[8][3];
+    __shared__ float red[8][4];
     const StftRes Rs = spec.r[res];
     const SplitCfg<R> g;
     const int row = blockIdx.y;
@@ -321,23 +358,23 @@ mrstft_fwd_split_kernel(const float* __restrict__ pred, const float* __restrict_
     const Fft512Tw t5 = fft512_twiddles(g.l, tw);
     float r[8], i[8], mr[4], mi[4];
     split_frame_spectrum<R>(pred + (size_t)row * N, target + (size_t)row * N, N, frame, live, Rs, g, tw, t5, lds, wlds, r, i, mr, mi);
-    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
     if (live) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s) loss_terms(split_bin(r[s], i[s], mr[s], mi[s]), spec.eps, s1, s2, s3);
-        if (g.rp == 0 && g.l == 0) loss_terms(split_bin(r[4], i[4], r[4], i[4]), spec.eps, s1, s2, s3);       // bin F / 2 mirrors onto itself
+        for (int s = 0; s < 4; ++s) loss_terms(split_bin(r[s], i[s], mr[s], mi[s]), spec.eps, s1, s2, s3, s4);
+        if (g.rp == 0 && g.l == 0) loss_terms(split_bin(r[4], i[4], r[4], i[4]), spec.eps, s1, s2, s3, s4);       // bin F / 2 mirrors onto itself
     }
-    s1 = wave_sum_uniform(s1); s2 = wave_sum_uniform(s2); s3 = wave_sum_uniform(s3);
-    if (g.l == 0) { red[g.wv][0] = s1; red[g.wv][1] = s2; red[g.wv][2] = s3; }
+    s1 = wave_sum_uniform(s1); s2 = wave_sum_uniform(s2); s3 = wave_sum_uniform(s3); s4 = wave_sum_uniform(s4);
+    if (g.l == 0) { red[g.wv][0] = s1; red[g.wv][1] = s2; red[g.wv][2] = s3; red[g.wv][3] = s4; }
     __syncthreads();
-    if (threadIdx.x < 3) {
+    if (threadIdx.x < 4) {
         float a = 0.f;
         for (int v = 0; v < 8; ++v) a += red[v][threadIdx.x];
-        partials[(((size_t)res * gridDim.y + row) * spec.groups + blockIdx.x) * 3 + threadIdx.x] = a;
+        partials[(((size_t)res * gridDim.y + row) * spec.groups + blockIdx.x) * 4 + threadIdx.x] = a;
     }
 }
 
-template <int R>
+template <int R, bool LIN>
 __global__ void __launch_bounds__(512)
 mrstft_bwd_split_kernel(const float* __restrict__ pred, const float* __restrict__ target, const f2* __restrict__ tw, const float* __restrict__ stats,
                         const float* __restrict__ gloss, float* __restrict__ gpred, StftSpec spec, int N, int res, int wrt_second) {
@@ -354,15 +391,13 @@ mrstft_bwd_split_kernel(const float* __restrict__ pred, const float* __restrict_
     float r[8], i[8], mr[4], mi[4];
     f2* rowbuf = lds + g.wv * FFT512_LDS;
     split_frame_spectrum<R>(pred + (size_t)row * N, target + (size_t)row * N, N, frame, live, Rs, g, tw, t5, lds, wlds, r, i, mr, mi);
-    const float s1 = stats[res * 4], s2 = stats[res * 4 + 1], count = stats[res * 4 + 2];
-    const float gl = gloss[0] / (float)spec.nres;
-    const float k_sc = s1 > 0.f ? gl / (s1 * s2) : 0.f, k_lm = gl / count, k_self = wrt_second ? -gl * s1 / (s2 * s2 * s2) : 0.f;
+    const GradK kk = grad_consts(spec, stats, gloss, res, wrt_second);
     float h4r = 0.f, h4i = 0.f;
-    if (live && g.rp == 0 && g.l == 0) grad_bin(split_bin(r[4], i[4], r[4], i[4]), spec.eps, k_sc, k_lm, k_self, h4r, h4i);
+    if (live && g.rp == 0 && g.l == 0) grad_bin<LIN>(split_bin(r[4], i[4], r[4], i[4]), spec.eps, kk, h4r, h4i);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         float hr = 0.f, hi = 0.f;
-        if (live) grad_bin(split_bin(r[s], i[s], mr[s], mi[s]), spec.eps, k_sc, k_lm, k_self, hr, hi);
+        if (live) grad_bin<LIN>(split_bin(r[s], i[s], mr[s], mi[s]), spec.eps, kk, hr, hi);
         r[s] = hr; i[s] = hi;
     }
     r[4] = h4r; i[4] = h4i;
@@ -404,6 +439,54 @@ mrstft_bwd_split_kernel(const float* __restrict__ pred, const float* __restrict_
         if (live && w != 0.f) atomicAdd(grow + reflect_index(frame * Rs.hop - F / 2 + n, N), w * r[q]);
     }
 }
+
+// ---- perceptual weighting: the A-weighting FIR of auraloss (FIRFilter(filter_type="aw", ntaps=101)) -------------------------------------
+// y[n] = sum_{k=0}^{K-1} h[k] x[n + k - K/2], zeros outside [0, N) (conv1d(x, h, padding=K/2)); K odd, <= 101. The taps sit centred in
+// 101 LDS slots (zeros around a shorter filter), so every output is the same 101 fmas in the same order: the result does not depend on
+// the tile it falls in, and is bit-identical run to run. flip = 1 reverses the taps: the adjoint, gx[m] = sum_k h[k] gy[m - k + K/2],
+// is the same sum over h[K-1-k] (no symmetry of the taps is assumed). A workgroup of 256 threads owns FIR_TILE consecutive outputs of one
+// row of one of the two signals (blockIdx.z): the tile plus a 50-sample halo on each side goes to LDS, each thread computes 8 consecutive
+// outputs from its 108-sample window, the taps are LDS broadcasts.
+constexpr int FIR_MAXTAPS = 101, FIR_HALO = FIR_MAXTAPS / 2, FIR_NT = 256, FIR_Q = 8, FIR_TILE = FIR_NT * FIR_Q;
+__global__ void __launch_bounds__(FIR_NT)
+fir_same_kernel(const float* __restrict__ x0, const float* __restrict__ x1, float* __restrict__ y0, float* __restrict__ y1,
+                const float* __restrict__ taps, int ntaps, int flip, int N) {
+    __shared__ float xs[FIR_TILE + 2 * FIR_HALO + 4];
+    __shared__ float hs[FIR_MAXTAPS + 3];
+    const int t = threadIdx.x;
+    const float* x = (blockIdx.z ? x1 : x0) + (size_t)blockIdx.y * N;
+    float* y = (blockIdx.z ? y1 : y0) + (size_t)blockIdx.y * N;
+    const long n0 = (long)blockIdx.x * FIR_TILE;
+    if (t < FIR_MAXTAPS + 3) {
+        const int k = t - (FIR_HALO - ntaps / 2);
+        hs[t] = (t < FIR_MAXTAPS && k >= 0 && k < ntaps) ? taps[flip ? ntaps - 1 - k : k] : 0.f;
+    }
+    for (int e = t; e < FIR_TILE + 2 * FIR_HALO; e += FIR_NT) {
+        const long s = n0 - FIR_HALO + e;
+        xs[e] = (s >= 0 && s < N) ? x[s] : 0.f;
+    }
+    __syncthreads();
+    const float* xw = xs + FIR_Q * t;
+    float acc[FIR_Q];
+#pragma unroll
+    for (int q = 0; q < FIR_Q; ++q) acc[q] = 0.f;
+#pragma unroll
+    for (int k = 0; k < FIR_MAXTAPS; ++k) {
+        const float h = hs[k];
+#pragma unroll
+        for (int q = 0; q < FIR_Q; ++q) acc[q] = fmaf(h, xw[q + k], acc[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < FIR_Q; ++q) {
+        const long n = n0 + FIR_Q * t + q;
+        if (n < N) y[n] = acc[q];
+    }
+}
+// the taps by value (kernel arguments), so that writing them to device memory is one kernel node of a captured graph, not a copy from host memory
+struct FirTaps { float h[FIR_MAXTAPS]; int n; };
+__global__ void fir_taps_kernel(float* __restrict__ dst, FirTaps taps) {
+    if ((int)threadIdx.x < taps.n) dst[threadIdx.x] = taps.h[threadIdx.x];
+}
 }  // namespace dasp
 
 // ================================================================================================
@@ -415,20 +498,36 @@ inline int sl_check() {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? DASP_OK : (int)e;
 }
-bool sl_spec(int N, int nres, const int* fft, const int* hop, const int* win, float eps, StftSpec* out) {
+// maxlog: 12 for the entry points of the default loss (n_fft <= 4096), 13 for the weighted ones (n_fft <= 8192)
+bool sl_spec(int N, int nres, const int* fft, const int* hop, const int* win, float eps, StftSpec* out, int maxlog = 12,
+             float w_sc = 1.f, float w_lm = 1.f, float w_lin = 0.f) {
     if (nres <= 0 || nres > SL_MAXRES || !fft || !hop || !win) return false;
+    if (!std::isfinite(w_sc) || !std::isfinite(w_lm) || !std::isfinite(w_lin)) return false;
     StftSpec s = {};
-    s.nres = nres; s.eps = eps; s.groups = 0;
+    s.nres = nres; s.eps = eps; s.groups = 0; s.w_sc = w_sc; s.w_lm = w_lm; s.w_lin = w_lin;
     for (int r = 0; r < nres; ++r) {
         int lg = 0;
-        while ((1 << lg) < fft[r]) ++lg;
-        if ((1 << lg) != fft[r] || lg < 3 || lg > 12 || hop[r] <= 0 || win[r] <= 0 || win[r] > fft[r] || fft[r] / 2 >= N) return false;
+        while (lg < 30 && (1 << lg) < fft[r]) ++lg;
+        if ((1 << lg) != fft[r] || lg < 3 || lg > maxlog || hop[r] <= 0 || win[r] <= 0 || win[r] > fft[r] || fft[r] / 2 >= N) return false;
         s.r[r] = StftRes{lg, hop[r], win[r], 1 + N / hop[r]};
-        const int TC = FFT_N >> lg, ng = (s.r[r].frames + TC - 1) / TC;
+        const int TC = frames_per_group(lg), ng = (s.r[r].frames + TC - 1) / TC;
         if (ng > s.groups) s.groups = ng;
     }
     *out = s;
     return true;
+}
+template <bool LIN>
+void mrstft_bwd_launch(const float* first, const float* second, const void* tw, const float* stats, const float* gloss, float* gfirst,
+                              const StftSpec& s, int rows, int N, int r, int wrt_second, hipStream_t st) {
+    const int TC = frames_per_group(s.r[r].logF);
+    const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
+    switch (s.r[r].logF) {
+        case 9: hipLaunchKernelGGL((mrstft_bwd_split_kernel<1, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
+        case 10: hipLaunchKernelGGL((mrstft_bwd_split_kernel<2, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
+        case 11: hipLaunchKernelGGL((mrstft_bwd_split_kernel<4, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
+        case 13: hipLaunchKernelGGL((mrstft_bwd_kernel<13, LIN>), grid, dim3(1024), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
+        default: hipLaunchKernelGGL((mrstft_bwd_kernel<12, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second);
+    }
 }
 }  // namespace
 
@@ -439,7 +538,13 @@ extern "C" {
 long dasp_mrstft_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win) {
     StftSpec s;
     if (!sl_spec(N, nres, fft, hop, win, 0.f, &s)) return -1;
-    return (long)nres * rows * s.groups * 3;
+    return (long)nres * rows * s.groups * 4;
+}
+/* the same for the weighted entry points: n_fft a power of two in 8..8192 */
+long dasp_mrstft_weighted_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win) {
+    StftSpec s;
+    if (!sl_spec(N, nres, fft, hop, win, 0.f, &s, 13)) return -1;
+    return (long)nres * rows * s.groups * 4;
 }
 /* tw: 4096 complex (8192 floats), the twiddle table the transforms read */
 int dasp_mrstft_table(void* tw, void* stream) {
@@ -447,48 +552,53 @@ int dasp_mrstft_table(void* tw, void* stream) {
     hipLaunchKernelGGL(stft_twiddle_kernel, dim3(FFT_N / 256), dim3(256), 0, (hipStream_t)stream, (f2*)tw);
     return sl_check();
 }
-/* pred, target (rows, N); stats (4 * nres floats, kept for the backward); loss: 1 float */
-int dasp_mrstft_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int rows, int N,
-                        int nres, const int* fft, const int* hop, const int* win, float eps, void* stream) {
+static int mrstft_forward_impl(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int rows,
+                               int N, int nres, const int* fft, const int* hop, const int* win, float eps, int maxlog, float w_sc, float w_lm,
+                               float w_lin, void* stream) {
     if (!pred || !target || !tw || !partials || !stats || !loss || rows <= 0 || N <= 0) return DASP_ERR_ARG;
     StftSpec s;
-    if (!sl_spec(N, nres, fft, hop, win, eps, &s)) return DASP_ERR_UNSUPPORTED;
+    if (!sl_spec(N, nres, fft, hop, win, eps, &s, maxlog, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
     if (rows > 65535) return DASP_ERR_UNSUPPORTED;
     for (int r = 0; r < nres; ++r) {
-        const int TC = FFT_N >> s.r[r].logF;
+        const int TC = frames_per_group(s.r[r].logF);
         const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
         hipStream_t st = (hipStream_t)stream;
-        switch (s.r[r].logF) {          // 512 / 1024 / 2048-point frames: 1 / 2 / 4 waves per frame; any other power of two: col_fft
+        switch (s.r[r].logF) {          // 512 / 1024 / 2048-point frames: 1 / 2 / 4 waves per frame; 8192: 16 waves; any other power of two: col_fft
             case 9: hipLaunchKernelGGL(mrstft_fwd_split_kernel<1>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
             case 10: hipLaunchKernelGGL(mrstft_fwd_split_kernel<2>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
             case 11: hipLaunchKernelGGL(mrstft_fwd_split_kernel<4>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
-            default: hipLaunchKernelGGL(mrstft_fwd_kernel, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
+            case 13: hipLaunchKernelGGL(mrstft_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
+            default: hipLaunchKernelGGL(mrstft_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
         }
     }
-    hipLaunchKernelGGL(mrstft_reduce_kernel, dim3((unsigned)(nres * 3)), dim3(1024), 0, (hipStream_t)stream, (const float*)partials, s, rows, stats);
+    hipLaunchKernelGGL(mrstft_reduce_kernel, dim3((unsigned)(nres * 4)), dim3(1024), 0, (hipStream_t)stream, (const float*)partials, s, rows, stats);
     hipLaunchKernelGGL(mrstft_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, s, rows, stats, loss);
     return sl_check();
+}
+/* pred, target (rows, N); stats (4 * nres floats, kept for the backward); loss: 1 float */
+int dasp_mrstft_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int rows, int N,
+                        int nres, const int* fft, const int* hop, const int* win, float eps, void* stream) {
+    return mrstft_forward_impl(pred, target, tw, partials, stats, loss, rows, N, nres, fft, hop, win, eps, 12, 1.f, 1.f, 0.f, stream);
+}
+int dasp_mrstft_weighted_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int rows,
+                                 int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_log_mag,
+                                 float w_lin_mag, void* stream) {
+    return mrstft_forward_impl(pred, target, tw, partials, stats, loss, rows, N, nres, fft, hop, win, eps, 13, w_sc, w_log_mag, w_lin_mag, stream);
 }
 /* gpred (rows, N) is overwritten with gloss * d loss / d pred (gloss: device scalar); dasp_mrstft_backward_target: the same for the
  * second signal, gtarget = gloss * d loss / d target (auraloss differentiates both arguments: a consistency loss between two model
  * outputs needs it; the reference's call sites pass the reference signal there and never ask) */
 static int mrstft_backward_impl(const float* first, const float* second, const void* tw, const float* stats, const float* gloss, float* gfirst,
-                                int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, int wrt_second, void* stream) {
+                                int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, int wrt_second, void* stream,
+                                int maxlog = 12, float w_sc = 1.f, float w_lm = 1.f, float w_lin = 0.f) {
     if (!first || !second || !tw || !stats || !gloss || !gfirst || rows <= 0 || N <= 0) return DASP_ERR_ARG;
     StftSpec s;
-    if (!sl_spec(N, nres, fft, hop, win, eps, &s)) return DASP_ERR_UNSUPPORTED;
+    if (!sl_spec(N, nres, fft, hop, win, eps, &s, maxlog, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
     if (rows > 65535) return DASP_ERR_UNSUPPORTED;
     if (zero_async(gfirst, (size_t)rows * N * sizeof(float), (hipStream_t)stream) != hipSuccess) return sl_check();
     for (int r = 0; r < nres; ++r) {
-        const int TC = FFT_N >> s.r[r].logF;
-        const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
-        hipStream_t st = (hipStream_t)stream;
-        switch (s.r[r].logF) {
-            case 9: hipLaunchKernelGGL(mrstft_bwd_split_kernel<1>, grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
-            case 10: hipLaunchKernelGGL(mrstft_bwd_split_kernel<2>, grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
-            case 11: hipLaunchKernelGGL(mrstft_bwd_split_kernel<4>, grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
-            default: hipLaunchKernelGGL(mrstft_bwd_kernel, grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second);
-        }
+        if (s.w_lin != 0.f) mrstft_bwd_launch<true>(first, second, tw, stats, gloss, gfirst, s, rows, N, r, wrt_second, (hipStream_t)stream);
+        else mrstft_bwd_launch<false>(first, second, tw, stats, gloss, gfirst, s, rows, N, r, wrt_second, (hipStream_t)stream);
     }
     return sl_check();
 }
@@ -499,6 +609,40 @@ int dasp_mrstft_backward(const float* pred, const float* target, const void* tw,
 int dasp_mrstft_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gtarget,
                                 int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, void* stream) {
     return mrstft_backward_impl(target, pred, tw, stats, gloss, gtarget, rows, N, nres, fft, hop, win, eps, 1, stream);
+}
+int dasp_mrstft_weighted_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gpred,
+                                  int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
+                                  float w_log_mag, float w_lin_mag, void* stream) {
+    return mrstft_backward_impl(pred, target, tw, stats, gloss, gpred, rows, N, nres, fft, hop, win, eps, 0, stream, 13, w_sc, w_log_mag, w_lin_mag);
+}
+int dasp_mrstft_weighted_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
+                                         float* gtarget, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
+                                         float w_sc, float w_log_mag, float w_lin_mag, void* stream) {
+    return mrstft_backward_impl(target, pred, tw, stats, gloss, gtarget, rows, N, nres, fft, hop, win, eps, 1, stream, 13, w_sc, w_log_mag, w_lin_mag);
+}
+
+static int fir_same_launch(const float* a, const float* b, float* ya, float* yb, const float* taps, int ntaps, int rows, int N, int flip,
+                           void* stream) {
+    if (!a || !ya || !taps || (!b) != (!yb) || rows <= 0 || N <= 0) return DASP_ERR_ARG;
+    if (ntaps <= 0 || ntaps > FIR_MAXTAPS || !(ntaps & 1) || rows > 65535) return DASP_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)((N + FIR_TILE - 1) / FIR_TILE), (unsigned)rows, b ? 2u : 1u);
+    hipLaunchKernelGGL(fir_same_kernel, grid, dim3(FIR_NT), 0, (hipStream_t)stream, a, b, ya, yb, taps, ntaps, flip, N);
+    return sl_check();
+}
+int dasp_fir_same_forward(const float* x0, const float* x1, float* y0, float* y1, const float* taps, int ntaps, int rows, int N, void* stream) {
+    return fir_same_launch(x0, x1, y0, y1, taps, ntaps, rows, N, 0, stream);
+}
+int dasp_fir_same_adjoint(const float* g0, const float* g1, float* gx0, float* gx1, const float* taps, int ntaps, int rows, int N, void* stream) {
+    return fir_same_launch(g0, g1, gx0, gx1, taps, ntaps, rows, N, 1, stream);
+}
+int dasp_fir_taps_store(float* dst, const float* host_taps, int ntaps, void* stream) {
+    if (!dst || !host_taps) return DASP_ERR_ARG;
+    if (ntaps <= 0 || ntaps > FIR_MAXTAPS) return DASP_ERR_UNSUPPORTED;
+    FirTaps t = {};
+    for (int k = 0; k < ntaps; ++k) t.h[k] = host_taps[k];
+    t.n = ntaps;
+    hipLaunchKernelGGL(fir_taps_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, dst, t);
+    return sl_check();
 }
 
 }  // extern "C"

@@ -1,9 +1,13 @@
 """Multi-resolution STFT loss on the HIP kernels of csrc/stftloss.hip: the loss the reference's training loops put directly after
-the effect chain (auraloss.freq.MultiResolutionSTFTLoss(), examples/style_transfer.py:341,363). Same defaults and call convention as
-auraloss 0.4.0: `loss_fn(input, target)` with (bs, chs, seq_len) tensors, spectral convergence + log-magnitude L1 per resolution,
-mean over the resolutions. Only `input` receives a gradient (the target is the reference signal at every call site)."""
+the effect chain (auraloss.freq.MultiResolutionSTFTLoss(), examples/style_transfer.py:341,363, auto_eq.py:252, virtual_analog.py:288).
+Same defaults and call convention as auraloss 0.4.0: `loss_fn(input, target)` with (bs, chs, seq_len) tensors, per resolution
+w_sc * spectral convergence + w_log_mag * log-magnitude L1 + w_lin_mag * linear-magnitude L1, mean over the resolutions; with
+perceptual_weighting=True both signals first go through auraloss's 101-tap A-weighting FIR. Both arguments receive gradients."""
 import ctypes
+import functools
+import math
 
+import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -11,9 +15,60 @@ from . import _lib
 from ._lib import call, ptr, stream
 
 
+AW_TAPS = 101
+_AW_F = (20.598997, 107.65265, 737.86223, 12194.217)      # IEC 61672 A-weighting corner frequencies (Hz), as auraloss.perceptual
+_AW_A1000 = 1.9997
+
+
+@functools.lru_cache(maxsize=16)
+def a_weighting_taps(sample_rate: float) -> np.ndarray:
+    """The 101 float32 taps of auraloss.perceptual.FIRFilter(filter_type="aw", fs=sample_rate, ntaps=101): the analog A-weighting,
+    its bilinear transform, that filter's magnitude on 512 frequencies, and the least-squares linear-phase FIR through them."""
+    import scipy.signal
+    f1, f2, f3, f4 = _AW_F
+    num = [(2 * np.pi * f4) ** 2 * (10 ** (_AW_A1000 / 20)), 0, 0, 0, 0]
+    den = np.polymul([1, 4 * np.pi * f4, (2 * np.pi * f4) ** 2], [1, 4 * np.pi * f1, (2 * np.pi * f1) ** 2])
+    den = np.polymul(np.polymul(den, [1, 2 * np.pi * f3]), [1, 2 * np.pi * f2])
+    b, a = scipy.signal.bilinear(num, den, fs=sample_rate)
+    w, h = scipy.signal.freqz(b, a, worN=512, fs=sample_rate)
+    taps = scipy.signal.firls(AW_TAPS, w, abs(h), fs=sample_rate).astype(np.float32)
+    taps.flags.writeable = False
+    return taps
+
+
+_DEFAULTS = {"w_sc": 1.0, "w_log_mag": 1.0, "w_lin_mag": 0.0, "sample_rate": None, "perceptual_weighting": False, "w_phs": 0.0,
+             "window": "hann_window", "scale": None, "n_bins": None, "scale_invariance": False, "reduction": "mean", "mag_distance": "L1",
+             "output": "loss", "device": None}
+_NOT_IMPLEMENTED = ("w_phs", "window", "scale", "n_bins", "scale_invariance", "reduction", "mag_distance", "output")
+
+
+def _options(what, options):
+    """auraloss 0.4.0's keyword options -> None (the default loss) or (w_sc, w_log_mag, w_lin_mag, sample_rate or None). `device` is
+    ignored: the kernels follow the inputs."""
+    for name in options:
+        if name not in _DEFAULTS:
+            raise TypeError(f"{what}() got an unexpected keyword argument {name!r}")
+    o = dict(_DEFAULTS, **options)
+    for name in _NOT_IMPLEMENTED:
+        v, d = o[name], _DEFAULTS[name]
+        if (v is not None) if d is None else (v != d):
+            raise NotImplementedError(f"{what}: {name}={v!r} is not implemented (only the default {name}={d!r})")
+    if o["perceptual_weighting"] and o["sample_rate"] is None:
+        raise ValueError("`sample_rate` must be supplied when `perceptual_weighting = True`.")
+    w = (float(o["w_sc"]), float(o["w_log_mag"]), float(o["w_lin_mag"]))
+    if not all(math.isfinite(v) for v in w):
+        raise ValueError(f"{what}: the term weights must be finite, got w_sc, w_log_mag, w_lin_mag = {w}")
+    if w == (1.0, 1.0, 0.0) and not o["perceptual_weighting"]:
+        return None
+    return w + (float(o["sample_rate"]) if o["perceptual_weighting"] else None,)
+
+
 class _MRSTFTFunction(torch.autograd.Function):
+    """opts: None (the default loss: the unweighted entry points) or (w_sc, w_log_mag, w_lin_mag, sample_rate or None) - the
+    weighted entry points, which also take 8192-point frames, and with a sample rate the A-weighting FIR in front (and its adjoint behind)."""
+
     @staticmethod
-    def forward(ctx, inp, target, res, eps):
+    def forward(ctx, inp, target, res, eps, opts=None):
         _lib.require_device(inp, "input")
         _lib.require_device(target, "target")
         _lib.require_same_device(inp, target=target)
@@ -28,38 +83,62 @@ class _MRSTFTFunction(torch.autograd.Function):
         rows = p32.shape[0]
         nres = len(res)
         arr = [(ctypes.c_int * nres)(*[int(r[i]) for r in res]) for i in range(3)]
-        nfl = L.dasp_mrstft_partial_floats(rows, N, nres, *arr)
+        if opts is None and any(int(r[0]) > 4096 for r in res):
+            opts = (1.0, 1.0, 0.0, None)                # 8192-point frames: only the weighted entry points take them
+        weighted = opts is not None
+        nfl = (L.dasp_mrstft_weighted_partial_floats if weighted else L.dasp_mrstft_partial_floats)(rows, N, nres, *arr)
         if nfl < 0:
-            raise _lib.DaspHipError("unsupported STFT resolutions (fft a power of two in 8..4096, win <= fft, fft / 2 < seq_len, <= 8 of them)")
+            raise _lib.DaspHipError(f"unsupported STFT resolutions (fft a power of two in 8..{8192 if weighted else 4096}, win <= fft, "
+                                    "fft / 2 < seq_len, <= 8 of them)")
         dev = inp.device
         with torch.cuda.device(dev):
             tw = _twiddles(dev)
+            taps = None
+            if weighted and opts[3] is not None:         # A-weighting of both signals; the STFTs and the backward see the filtered pair
+                taps = _aw_taps(opts[3], dev)
+                pf, tf = torch.empty_like(p32), torch.empty_like(t32)
+                call("dasp_fir_same_forward", ptr(p32), ptr(t32), ptr(pf), ptr(tf), ptr(taps), AW_TAPS, rows, N, stream())
+                p32, t32 = pf, tf
             partials = torch.empty(nfl, dtype=torch.float32, device=dev)
             stats = torch.empty(4 * nres, dtype=torch.float32, device=dev)
             loss = torch.empty((), dtype=torch.float32, device=dev)
-            call("dasp_mrstft_forward", ptr(p32), ptr(t32), ptr(tw), ptr(partials), ptr(stats), ptr(loss), rows, N, nres, *arr, float(eps), stream())
-        ctx.save_for_backward(p32, t32, stats, tw)
+            if weighted:
+                call("dasp_mrstft_weighted_forward", ptr(p32), ptr(t32), ptr(tw), ptr(partials), ptr(stats), ptr(loss), rows, N, nres, *arr, float(eps),
+                     *opts[:3], stream())
+            else:
+                call("dasp_mrstft_forward", ptr(p32), ptr(t32), ptr(tw), ptr(partials), ptr(stats), ptr(loss), rows, N, nres, *arr, float(eps), stream())
+        ctx.save_for_backward(p32, t32, stats, tw, taps)
         ctx.cfg = (rows, N, nres, arr, float(eps), inp.shape, inp.dtype)
+        ctx.opts = opts
         ctx.tdtype = target.dtype
         return loss.to(inp.dtype)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gloss):
-        p32, t32, stats, tw = ctx.saved_tensors
+        p32, t32, stats, tw, taps = ctx.saved_tensors
         rows, N, nres, arr, eps, shape, dtype = ctx.cfg
+        opts = ctx.opts
+        name, wts = ("dasp_mrstft_weighted_backward", tuple(opts[:3])) if opts is not None else ("dasp_mrstft_backward", ())
         g = gt = None
         with torch.cuda.device(p32.device):
             gl = gloss.detach().reshape(1).to(torch.float32).contiguous()
             if ctx.needs_input_grad[0]:
                 g = torch.empty_like(p32)
-                call("dasp_mrstft_backward", ptr(p32), ptr(t32), ptr(tw), ptr(stats), ptr(gl), ptr(g), rows, N, nres, *arr, eps, stream())
-                g = g.reshape(shape).to(dtype)
+                call(name, ptr(p32), ptr(t32), ptr(tw), ptr(stats), ptr(gl), ptr(g), rows, N, nres, *arr, eps, *wts, stream())
             if ctx.needs_input_grad[1]:      # auraloss differentiates both arguments (a consistency loss between two model outputs)
                 gt = torch.empty_like(t32)
-                call("dasp_mrstft_backward_target", ptr(p32), ptr(t32), ptr(tw), ptr(stats), ptr(gl), ptr(gt), rows, N, nres, *arr, eps, stream())
-                gt = gt.reshape(shape).to(ctx.tdtype)
-        return g, gt, None, None
+                call(name + "_target", ptr(p32), ptr(t32), ptr(tw), ptr(stats), ptr(gl), ptr(gt), rows, N, nres, *arr, eps, *wts, stream())
+            if taps is not None and (g is not None or gt is not None):        # through the A-weighting FIR: its adjoint, one launch for both
+                first, second = (g, gt) if g is not None else (gt, None)
+                o1, o2 = torch.empty_like(first), (torch.empty_like(second) if second is not None else None)
+                call("dasp_fir_same_adjoint", ptr(first), ptr(second), ptr(o1), ptr(o2), ptr(taps), AW_TAPS, rows, N, stream())
+                g, gt = (o1, o2) if g is not None else (None, o1)
+        if g is not None:
+            g = g.reshape(shape).to(dtype)
+        if gt is not None:
+            gt = gt.reshape(shape).to(ctx.tdtype)
+        return g, gt, None, None, None
 
 
 _TW = {}
@@ -82,30 +161,56 @@ def _twiddles(device):
     return tw
 
 
-class MultiResolutionSTFTLoss(torch.nn.Module):
-    """auraloss.freq.MultiResolutionSTFTLoss with its default weights (w_sc = w_log_mag = 1, w_lin_mag = w_phs = 0, hann window,
-    L1 magnitude distance, mean reduction)."""
+_AW_DEV = {}
 
-    def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), eps: float = 1e-8):
+
+def _aw_taps(sample_rate, device):
+    """The A-weighting taps on the device, one copy per (sample_rate, device, stream), under _twiddles' capture rule. They are written by
+    a kernel that gets them as arguments (dasp_fir_taps_store), so building them inside a capture needs no copy from host memory."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    key = (float(sample_rate), device.index, int(torch.cuda.current_stream(device).cuda_stream))
+    if not capturing and key in _AW_DEV:
+        return _AW_DEV[key]
+    host = a_weighting_taps(float(sample_rate))
+    taps = torch.empty(AW_TAPS, dtype=torch.float32, device=device)
+    call("dasp_fir_taps_store", ptr(taps), host.ctypes.data_as(ctypes.c_void_p), AW_TAPS, stream())
+    if not capturing:
+        if len(_AW_DEV) >= 16:
+            _AW_DEV.clear()
+        _AW_DEV[key] = taps
+    return taps
+
+
+class MultiResolutionSTFTLoss(torch.nn.Module):
+    """auraloss.freq.MultiResolutionSTFTLoss (0.4.0). Positional arguments fft_sizes, hop_sizes, win_lengths, eps; keyword-only, with
+    auraloss's defaults: w_sc=1.0, w_log_mag=1.0, w_lin_mag=0.0, sample_rate=None, perceptual_weighting=False (True: the A-weighting
+    FIR of auraloss.perceptual in front, needs sample_rate), device=None (ignored: the kernels follow the inputs). w_phs, window, scale,
+    n_bins, scale_invariance, reduction, mag_distance and output are accepted at their defaults only (0.0, "hann_window", None, None,
+    False, "mean", "L1", "loss"); any other value raises NotImplementedError. n_fft: powers of two 8 .. 8192, at most 8 resolutions."""
+
+    def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), eps: float = 1e-8, **options):
         super().__init__()
         if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
             raise ValueError("fft_sizes, hop_sizes and win_lengths must have the same length")
+        self._opts = _options(type(self).__name__, options)
         self.resolutions = tuple(zip(fft_sizes, hop_sizes, win_lengths))
         self.eps = eps
 
     def forward(self, input: torch.Tensor, target: torch.Tensor):
-        return _MRSTFTFunction.apply(input, target, self.resolutions, self.eps)
+        return _MRSTFTFunction.apply(input, target, self.resolutions, self.eps, self._opts)
 
 
 class STFTLoss(MultiResolutionSTFTLoss):
     """auraloss.freq.STFTLoss with its default arguments (one resolution: fft 1024, hop 256, window 1024; w_sc = w_log_mag = 1, hann window,
     L1 magnitude distance, mean reduction) - the loss of the reference's examples/blind_estimation.py:141. One resolution of the same
-    kernels (csrc/stftloss.hip)."""
+    kernels (csrc/stftloss.hip); the keyword options of MultiResolutionSTFTLoss."""
 
-    def __init__(self, fft_size: int = 1024, hop_size: int = 256, win_length: int = 1024, eps: float = 1e-8):
-        super().__init__((fft_size,), (hop_size,), (win_length,), eps)
+    def __init__(self, fft_size: int = 1024, hop_size: int = 256, win_length: int = 1024, eps: float = 1e-8, **options):
+        super().__init__((fft_size,), (hop_size,), (win_length,), eps, **options)
 
 
 def mrstft_loss(input: torch.Tensor, target: torch.Tensor, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240),
-                eps: float = 1e-8):
-    return _MRSTFTFunction.apply(input, target, tuple(zip(fft_sizes, hop_sizes, win_lengths)), eps)
+                eps: float = 1e-8, **options):
+    """MultiResolutionSTFTLoss(fft_sizes, hop_sizes, win_lengths, eps, **options)(input, target) as a function."""
+    opts = _options("mrstft_loss", options)
+    return _MRSTFTFunction.apply(input, target, tuple(zip(fft_sizes, hop_sizes, win_lengths)), eps, opts)

@@ -418,6 +418,30 @@ int dasp_mrstft_backward(const float* pred, const float* target, const void* tw,
 int dasp_mrstft_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
                                 float* gtarget, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
                                 void* stream);
+/* The loss with auraloss's term weights (MultiResolutionSTFTLoss(w_sc=, w_log_mag=, w_lin_mag=)): per resolution
+ * w_sc * SC + w_log_mag * LOG + w_lin_mag * LIN, LIN = mean ||X| - |Y||; a weight of exactly 0 leaves its term out of the loss and the
+ * gradient. fft a power of two in 8..8192 (8192: one frame per 1024-thread workgroup); otherwise as above, and the same kernels:
+ * weights (1, 1, 0) give the unweighted loss. partials: dasp_mrstft_weighted_partial_floats floats (-1: not supported); stats 4*nres. */
+long dasp_mrstft_weighted_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win);
+int dasp_mrstft_weighted_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss,
+                                 int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
+                                 float w_log_mag, float w_lin_mag, void* stream);
+int dasp_mrstft_weighted_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
+                                  float* gpred, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
+                                  float w_sc, float w_log_mag, float w_lin_mag, void* stream);
+int dasp_mrstft_weighted_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
+                                         float* gtarget, int rows, int N, int nres, const int* fft, const int* hop, const int* win,
+                                         float eps, float w_sc, float w_log_mag, float w_lin_mag, void* stream);
+/* The perceptual weighting of the loss (auraloss FIRFilter(filter_type="aw", ntaps=101), applied to both signals before the STFTs):
+ * y[n] = sum_k taps[k] x[n + k - ntaps/2] over rows of N samples, zeros outside [0, N) (conv1d(x, taps, padding=ntaps/2)); ntaps odd,
+ * <= 101; taps on the device. Fixed summation order: bit-identical run to run. dasp_fir_same_forward filters x0 -> y0 and x1 -> y1;
+ * dasp_fir_same_adjoint is its adjoint (the taps reversed) on g0 -> gx0 and g1 -> gx1. The second pair may be NULL (one signal).
+ * dasp_fir_taps_store writes ntaps host floats to dst through a kernel's arguments (no host-memory copy: capturable into a graph). */
+int dasp_fir_same_forward(const float* x0, const float* x1, float* y0, float* y1, const float* taps, int ntaps, int rows, int N,
+                          void* stream);
+int dasp_fir_same_adjoint(const float* g0, const float* g1, float* gx0, float* gx1, const float* taps, int ntaps, int rows, int N,
+                          void* stream);
+int dasp_fir_taps_store(float* dst, const float* host_taps, int ntaps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Filters longer than one biquad.  Replaces dasp_pytorch.signal.lfilter_via_fsm (dasp_pytorch/signal.py:95-133) for K = 4 .. 16
