@@ -105,6 +105,9 @@ SIGNATURES = {
     "dasp_freqz_work_doubles": (_l, [_i, _i, _i, _i, _l]),
     "dasp_freqz_forward": (_i, [_p, _p, _i, _i, _i, _i, _l, _i, _p, _p]),
     "dasp_freqz_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _i, _p, _l, _p, _p, _p]),
+    "dasp_fdfir_work_floats": (_l, [_l, _l, _l, _l]),
+    "dasp_fdfir_forward": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p]),
+    "dasp_fdfir_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _l, _l, _l, _l, _p]),
     "dasp_sos64_normalize": (_i, [_p, _i, _i, _p, _p]),
     "dasp_sos64_forward": (_i, [_p, _i, _p, _p, _p, _i, _i, _l, _i, _p]),
     "dasp_sos64_backward": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _l, _i, _p]),

@@ -185,6 +185,15 @@ def _register_fakes():
     def _(b, a, grad_H, n_fft):
         return like(b), like(a)
 
+    # ---- filtering by a supplied frequency response (signal.freqdomain_fir)
+    @torch.library.register_fake("dasp::freqdomain_fir")
+    def _(x, H, n_fft):
+        return x.new_empty((x.shape[0], n_fft))
+
+    @torch.library.register_fake("dasp::_freqdomain_fir_backward")
+    def _(x, H, grad_y, n_fft, need_gx, need_gH):
+        return (like(x) if need_gx else f32(x, 0)), (like(H) if need_gH else H.new_empty((0,)))
+
     @torch.library.register_fake("dasp::_reverb_backward")
     def _(grad_y, ir, A, H, noise, fspec, gains, decays, mix, Cx, num_samples, taps, bands, seed, seed_offset, decay_bound):
         B, _, N = grad_y.shape

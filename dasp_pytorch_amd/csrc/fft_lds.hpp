@@ -1,7 +1,7 @@
 // Complex FFTs held in registers + LDS (gfx950), 8 elements per thread, radix-8 Stockham passes with LDS exchanges in
 // between. Element `idx = j + T q` (T = length / 8) lives in register q of thread j both before and after a transform
 // (natural order in, natural order out), so a forward transform, a pointwise product and the inverse transform chain
-// through registers without touching LDS in between. Three shapes, all used by reverb.hip:
+// through registers without touching LDS in between. Three shapes (reverb.hip, stftloss.hip, fdfir.hip):
 //   fft512_wave  one 512-point transform per wave, no workgroup barriers      (row pass of the four-step long FFT)
 //   fft4096_split_fwd / _inv  one 4096-point transform per 512-thread workgroup as radix-8 x 512 with a single
 //                workgroup barrier                                             (filter bank, functional.py:548-558)
@@ -358,6 +358,23 @@ __device__ __forceinline__ void col_fft(float (&r)[8], float (&i)[8], const ColC
             r[m + 4] = ar - r[m + 4]; i[m + 4] = ai - i[m + 4];
         }
     }
+}
+
+// ---- shared by the four-step transforms n = NA x 512 of reverb.hip and fdfir.hip --------------------------------------------------
+// Workgroups are dealt round-robin to the 8 XCDs in launch order: physical index bx of nx -> logical index, a contiguous run per XCD
+// (identity when nx is not a multiple of 8). Used where neighbouring logical workgroups share cache lines: neighbouring column tiles of the
+// four-step kernels touch neighbouring (at small NA: the same) 128-byte lines of the signal; the windows of an item share its band spectra.
+__device__ __forceinline__ int xcd_tile(int bx, int nx) { return (nx & 7) ? bx : (bx & 7) * (nx >> 3) + (bx >> 3); }
+
+// forward twiddle w_n1^(ka (j + 64 q)), q = 0..7, as a chain from two accurate sincospi evaluations
+__device__ __forceinline__ void fourstep_twiddles(int ka, int j, int n1, float (&wr)[8], float (&wi)[8]) {
+    const float inv = 2.f / (float)n1;        // power-of-two n1: exact (the reduced exponents are below 2^24); 3 x 2^k: rounded once (6e-8 relative)
+    float s0, c0, s1, c1;
+    sincospif(-(float)((ka * j) % n1) * inv, &s0, &c0);
+    sincospif(-(float)((ka * 64) % n1) * inv, &s1, &c1);
+    wr[0] = c0; wi[0] = s0;
+#pragma unroll
+    for (int q = 1; q < 8; ++q) { wr[q] = wr[q - 1] * c1 - wi[q - 1] * s1; wi[q] = wr[q - 1] * s1 + wi[q - 1] * c1; }
 }
 
 }  // namespace dasp

@@ -39,11 +39,6 @@ constexpr int LOAD_LOG = 12, COLS_LOG = 13;   // workgroup size (log2 elements) 
 typedef ColGeom<LOAD_LOG> LoadGeom;
 typedef ColGeom<COLS_LOG> ColsGeom;
 
-// Workgroups are dealt round-robin to the 8 XCDs in launch order: physical index bx of nx -> logical index, a contiguous run per XCD
-// (identity when nx is not a multiple of 8). Used where neighbouring logical workgroups share cache lines: neighbouring column tiles of the
-// four-step kernels touch neighbouring (at small NA: the same) 128-byte lines of the signal; the windows of an item share its band spectra.
-__device__ __forceinline__ int xcd_tile(int bx, int nx) { return (nx & 7) ? bx : (bx & 7) * (nx >> 3) + (bx >> 3); }
-
 // ---- counter-based white noise (device_noise): the reference's torch.randn(bs * 2, 12, num_samples + taps - 1) (functional.py:548) ---------
 // generated where it is consumed. Written to memory by torch.randn and read by the forward and the backward filter bank it was 0.82 GB of
 // HBM traffic three times over per step; the stream below is a pure function of (seed, batch item, band, sample index), so both kernels -
@@ -373,17 +368,6 @@ __global__ __launch_bounds__(FFT_T, 4) void fb_fused_kernel(const float* __restr
 // instead of two 2 Lp-point frames - verified them against this path and measured the long convolution at 1.79 ms against 1.60
 // (profiles/r04/reverb_r3_kernels.log): removed in round 5, the code is in the history of this file.)
 struct ConvDims { int logNA, NA, n1, Lb, npairs; long N; };
-
-// forward twiddle w_n1^(ka (j + 64 q)), q = 0..7, as a chain from two accurate sincospi evaluations
-__device__ __forceinline__ void fourstep_twiddles(int ka, int j, int n1, float (&wr)[8], float (&wi)[8]) {
-    const float inv = 2.f / (float)n1;        // power-of-two n1: exact (the reduced exponents are below 2^24); 3 x 2^k: rounded once (6e-8 relative)
-    float s0, c0, s1, c1;
-    sincospif(-(float)((ka * j) % n1) * inv, &s0, &c0);
-    sincospif(-(float)((ka * 64) % n1) * inv, &s1, &c1);
-    wr[0] = c0; wi[0] = s0;
-#pragma unroll
-    for (int q = 1; q < 8; ++q) { wr[q] = wr[q - 1] * c1 - wi[q - 1] * s1; wi[q] = wr[q - 1] * s1 + wi[q - 1] * c1; }
-}
 
 
 // Column pass, time -> A[ka][jb]. grid (NA * 512 / 4096 column tiles, pairs, signals), 512 threads; thread (j, c): column jb = tile * TC + c,

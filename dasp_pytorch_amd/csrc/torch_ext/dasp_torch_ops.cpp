@@ -5,6 +5,7 @@
 //   * the effect chain of the reference's training loop (examples/style_transfer.py:150-154) on normalised parameters (round 4):
 //     parametric_eq_norm, dynamics_ctl, reverb on control matrices, and the chain's fused control de-normalisation chain_controls;
 //   * freqz: the frequency response behind signal.fft_freqz / fft_sosfreqz (signal.py:7-32), float32 and float64 - it has no ctypes binding.
+//   * freqdomain_fir: signal.freqdomain_fir (signal.py:35-39), filtering by a supplied frequency response - no ctypes binding either.
 // What SURVEY 8(b) / BASELINE north_star specify: ops
 // registered with TORCH_LIBRARY (schemas visible to torch.compile / torch.library.opcheck), forward + hand-derived adjoint as
 // torch::autograd::Function in C++ (the backward pass runs on autograd's worker thread without the Python interpreter), errors as
@@ -1204,6 +1205,108 @@ struct FreqzFn : public torch::autograd::Function<FreqzFn> {
 };
 Tensor freqz_autograd(const Tensor& b, const Tensor& a, int64_t n_fft) { return FreqzFn::apply(b, a, n_fft); }
 
+// ---- signal.freqdomain_fir (signal.py:35-39): y = irfft(rfft(x, n_fft) * H, n_fft), not cropped (csrc/fdfir.hip) ------------------------
+// x (rows, T) float32, H (h_rows, n_fft / 2 + 1) complex64, rows = h_rows * chs (the chs consecutive rows of an item share a response)
+// -> y (rows, n_fft). Nothing is saved but the inputs: the adjoint recomputes the spectrum of x. The 4096-entry twiddle table is kept per
+// (device, stream) under the rule of ops._filter_spectrum / losses._twiddles: a table built during a graph capture belongs to that
+// graph's pool and is not cached.
+std::mutex g_fdfir_mu;
+std::map<std::pair<int, void*>, Tensor> g_fdfir_tw;
+Tensor fdfir_twiddles(const Tensor& like) {
+    const auto opts = like.options().dtype(at::kFloat);
+    hipStream_t st = (hipStream_t)stream_of(like);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone;
+    const auto key = std::make_pair((int)like.device().index(), (void*)st);
+    std::lock_guard<std::mutex> lock(g_fdfir_mu);
+    if (!capturing) {
+        auto it = g_fdfir_tw.find(key);
+        if (it != g_fdfir_tw.end()) return it->second;
+    }
+    Tensor tw = at::empty({2 * 4096}, opts);
+    check_rc(dasp_mrstft_table(tw.data_ptr<float>(), (void*)st), "dasp_mrstft_table");
+    if (!capturing) {
+        if (g_fdfir_tw.size() >= 16) g_fdfir_tw.clear();
+        g_fdfir_tw.emplace(key, tw);
+    }
+    return tw;
+}
+struct FdfirDims { int64_t rows, T, h_rows; };
+FdfirDims fdfir_check(const Tensor& x, const Tensor& H, int64_t n_fft) {
+    need_device(x, "x");
+    same_device(x, H, "H");
+    TORCH_CHECK(x.dim() == 2 && H.dim() == 2, "dasp::freqdomain_fir: x must be (rows, T) and H (h_rows, n_fft / 2 + 1); got ", x.sizes(), " and ", H.sizes());
+    TORCH_CHECK(x.scalar_type() == at::kFloat && H.scalar_type() == at::kComplexFloat, "dasp::freqdomain_fir: x must be float32 and H complex64; got ",
+                x.scalar_type(), " and ", H.scalar_type());
+    TORCH_CHECK(n_fft >= 8 && n_fft <= (1 << 20) && !(n_fft & (n_fft - 1)), "dasp::freqdomain_fir: n_fft = ", n_fft,
+                " is not supported (powers of two from 8 to 2^20)");
+    TORCH_CHECK(H.size(1) == n_fft / 2 + 1, "dasp::freqdomain_fir: H has ", H.size(1), " bins, n_fft = ", n_fft, " needs ", n_fft / 2 + 1);
+    const FdfirDims d{x.size(0), x.size(1), H.size(0)};
+    TORCH_CHECK(d.T >= 1, "dasp::freqdomain_fir: x needs at least one sample per row");
+    TORCH_CHECK((d.rows == 0 && d.h_rows == 0) || (d.h_rows > 0 && d.rows % d.h_rows == 0), "dasp::freqdomain_fir: ", d.rows,
+                " rows of x are not a multiple of the ", d.h_rows, " rows of H");
+    return d;
+}
+Tensor fdfir_device(const Tensor& x, const Tensor& H, int64_t n_fft) {
+    const FdfirDims d = fdfir_check(x, H, n_fft);
+    c10::DeviceGuard guard(x.device());
+    const Tensor xc = x.contiguous(), Hc = H.resolve_conj().contiguous();
+    Tensor y = at::empty({d.rows, n_fft}, xc.options());
+    if (d.rows == 0) return y;
+    const long nw = dasp_fdfir_work_floats(d.rows, d.T, n_fft, d.h_rows);
+    TORCH_CHECK(nw >= 0, "dasp::freqdomain_fir: unsupported sizes (rows ", d.rows, ", T ", d.T, ", n_fft ", n_fft, ", h_rows ", d.h_rows, ")");
+    // the forward pass transforms the frames of x only (dasp_hip.h): one complex frame of n_fft points per two rows of an item
+    const long fw = nw ? 2L * d.h_rows * ((d.rows / d.h_rows + 1) / 2) * n_fft : 0;
+    Tensor work = empty_f32(fw, xc);
+    const Tensor tw = fdfir_twiddles(xc);
+    check_rc(dasp_fdfir_forward(xc.data_ptr<float>(), Hc.data_ptr(), tw.data_ptr<float>(), y.data_ptr<float>(), fp(work), fw, d.rows, d.T, n_fft, d.h_rows,
+                                stream_of(xc)),
+             "dasp_fdfir_forward");
+    return y;
+}
+std::tuple<Tensor, Tensor> fdfir_backward(const Tensor& x, const Tensor& H, const Tensor& grad_y, int64_t n_fft, bool need_gx, bool need_gH) {
+    const FdfirDims d = fdfir_check(x, H, n_fft);
+    same_device(x, grad_y, "grad_y");
+    TORCH_CHECK(grad_y.dim() == 2 && grad_y.size(0) == d.rows && grad_y.size(1) == n_fft, "dasp::_freqdomain_fir_backward: grad_y must be (", d.rows, ", ",
+                n_fft, "), got ", grad_y.sizes());
+    c10::DeviceGuard guard(x.device());
+    const Tensor xc = x.contiguous(), Hc = H.resolve_conj().contiguous(), g = f32c(grad_y);
+    Tensor gx = need_gx ? at::empty_like(xc) : empty_f32(0, xc);
+    Tensor gH = need_gH ? at::empty_like(Hc) : at::empty({0}, Hc.options());
+    if (d.rows == 0 || (!need_gx && !need_gH)) return {gx, gH};
+    const long nw = dasp_fdfir_work_floats(d.rows, d.T, n_fft, d.h_rows);
+    TORCH_CHECK(nw >= 0, "dasp::_freqdomain_fir_backward: unsupported sizes");
+    Tensor work = empty_f32(nw, xc);
+    const Tensor tw = fdfir_twiddles(xc);
+    check_rc(dasp_fdfir_backward(xc.data_ptr<float>(), Hc.data_ptr(), g.data_ptr<float>(), tw.data_ptr<float>(), need_gx ? gx.data_ptr<float>() : nullptr,
+                                 need_gH ? gH.data_ptr() : nullptr, fp(work), nw, d.rows, d.T, n_fft, d.h_rows, stream_of(xc)),
+             "dasp_fdfir_backward");
+    return {gx, gH};
+}
+struct FdfirFn : public torch::autograd::Function<FdfirFn> {
+    static Tensor forward(AutogradContext* ctx, const Tensor& x, const Tensor& H, int64_t n_fft) {
+        fdfir_check(x, H, n_fft);
+        at::AutoDispatchBelowADInplaceOrView below;
+        static auto fop = c10::Dispatcher::singleton().findSchemaOrThrow("dasp::freqdomain_fir", "").typed<Tensor(const Tensor&, const Tensor&, int64_t)>();
+        Tensor y = fop.call(x, H, n_fft);
+        if (x.requires_grad() || H.requires_grad()) {
+            ctx->save_for_backward({x, H});
+            ctx->saved_data["n_fft"] = n_fft;
+        }
+        return y;
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        const auto s = ctx->get_saved_variables();
+        const bool nx = ctx->needs_input_grad(0), nh = ctx->needs_input_grad(1);
+        if (!grads[0].defined()) return {nx ? at::zeros_like(s[0]) : Tensor(), nh ? at::zeros_like(s[1]) : Tensor(), Tensor()};
+        static auto bop = c10::Dispatcher::singleton().findSchemaOrThrow("dasp::_freqdomain_fir_backward", "")
+                              .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, int64_t, bool, bool)>();
+        auto [gx, gH] = bop.call(s[0], s[1], grads[0], ctx->saved_data["n_fft"].toInt(), nx, nh);
+        return {nx ? gx : Tensor(), nh ? gH : Tensor(), Tensor()};
+    }
+};
+Tensor fdfir_autograd(const Tensor& x, const Tensor& H, int64_t n_fft) { return FdfirFn::apply(x, H, n_fft); }
+
 }  // namespace
 
 #ifndef DASP_ABI_HASH
@@ -1257,6 +1360,8 @@ TORCH_LIBRARY(dasp, m) {
           "int taps, int bands, int seed, Tensor? seed_offset, float decay_bound) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("freqz(Tensor b, Tensor a, int n_fft) -> Tensor");
     m.def("_freqz_backward(Tensor b, Tensor a, Tensor grad_H, int n_fft) -> (Tensor, Tensor)");
+    m.def("freqdomain_fir(Tensor x, Tensor H, int n_fft) -> Tensor");
+    m.def("_freqdomain_fir_backward(Tensor x, Tensor H, Tensor grad_y, int n_fft, bool need_gx, bool need_gH) -> (Tensor, Tensor)");
     m.def("_abi_hash() -> int", &abi_hash);
     m.def("_plan_override(int sos_tiles, int dyn_tiles) -> ()", &plan_override);
 }
@@ -1291,6 +1396,8 @@ TORCH_LIBRARY_IMPL(dasp, CUDA, m) {
     m.impl("_reverb_backward", &reverb_backward);
     m.impl("freqz", &freqz_device);
     m.impl("_freqz_backward", &freqz_backward);
+    m.impl("freqdomain_fir", &fdfir_device);
+    m.impl("_freqdomain_fir_backward", &fdfir_backward);
 }
 TORCH_LIBRARY_IMPL(dasp, Autograd, m) {
     m.impl("parametric_eq", &peq_autograd);
@@ -1305,10 +1412,11 @@ TORCH_LIBRARY_IMPL(dasp, Autograd, m) {
     m.impl("chain_controls", &chain_controls_autograd);
     m.impl("reverb", &reverb_autograd);
     m.impl("freqz", &freqz_autograd);
+    m.impl("freqdomain_fir", &fdfir_autograd);
     // the two directions themselves carry no derivative: backpropagating through them (a double backward, or calling `_forward` on tensors
     // that require a gradient) raises "derivative for dasp::... is not implemented" instead of treating the result as a constant
     for (const char* name : {"_peq_forward", "_peq_backward", "_ew_forward", "_ew_backward", "_sosfilt_forward", "_sosfilt_backward", "_peq_norm_forward",
                              "_peq_norm_backward", "_dynamics_forward", "_dynamics_backward", "_dynamics6_forward", "_dynamics6_backward", "_chain_controls_backward", "_reverb_forward", "_eq_dyn_norm_forward",
-                             "_reverb_backward", "_freqz_backward"})
+                             "_reverb_backward", "_freqz_backward", "_freqdomain_fir_backward"})
         m.impl(name, torch::autograd::autogradNotImplementedFallback());
 }

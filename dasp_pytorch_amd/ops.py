@@ -6,8 +6,9 @@ torch.compile, opcheck-clean. Everything else - float64, the ops the extension d
 without libdasp_torch.so - takes the ctypes autograd.Functions of _ctypes_ops.py (same kernels, same C entry points; what changes is
 the host side: ctypes marshalling and Python in the backward pass), which also own the dtype / device error messages.
 
-The exception is `freqz` (signal.fft_freqz / fft_sosfreqz): it exists only as torch.ops.dasp.freqz, for float32 and float64 alike and
-whatever config.plan.torch_ops says (there is no second binding to compare it with). Without libdasp_torch.so it raises DaspHipError.
+The exceptions are `freqz` (signal.fft_freqz / fft_sosfreqz) and `freqdomain_fir` (signal.freqdomain_fir): they exist only as
+torch.ops.dasp.freqz / torch.ops.dasp.freqdomain_fir, whatever config.plan.torch_ops says (there is no second binding to compare them
+with). Without libdasp_torch.so they raise DaspHipError.
 """
 import ctypes
 
@@ -169,3 +170,15 @@ def freqz(b, a, n_fft):
         raise _lib.DaspHipError(f"{_torch_ops.EXT_PATH} (libdasp_torch.so) is not built or does not load: fft_freqz / fft_sosfreqz run only "
                                 "through torch.ops.dasp.freqz. Build it with `python -m dasp_pytorch_amd.csrc.build` (or __graft_entry__.build())")
     return torch.ops.dasp.freqz(b, a, int(n_fft))
+
+
+def freqdomain_fir(x, H, n_fft):
+    """torch.ops.dasp.freqdomain_fir: y (rows, n_fft) = irfft(rfft(x, n_fft) * H, n_fft) for x (rows, T) float32 and H (h_rows, n_fft // 2 + 1)
+    complex64, rows = h_rows * chs (the chs consecutive rows of an item share a response), differentiable w.r.t. x and H (csrc/fdfir.hip).
+    No ctypes binding: without the extension this raises."""
+    from . import _torch_ops
+    loaded = _torch_ops._state["loaded"] is True if torch.compiler.is_compiling() else _torch_ops.load()
+    if not loaded:
+        raise _lib.DaspHipError(f"{_torch_ops.EXT_PATH} (libdasp_torch.so) is not built or does not load: freqdomain_fir runs only "
+                                "through torch.ops.dasp.freqdomain_fir. Build it with `python -m dasp_pytorch_amd.csrc.build` (or __graft_entry__.build())")
+    return torch.ops.dasp.freqdomain_fir(x, H, int(n_fft))

@@ -7,7 +7,8 @@ decayed within the signal length. float64 input takes
 kernels of csrc/ref64.hip (ops64.py): float64 in, float64 arithmetic, as in the reference.
 
 `fft_freqz` / `fft_sosfreqz` keep the reference's frequency responses: evaluated per bin in fp64 (csrc/freqz.hip) instead of through
-zero-padded FFTs, for float32 and float64 alike, with a hand-written adjoint. `freqdomain_fir` still raises (it needs an FFT of any length).
+zero-padded FFTs, for float32 and float64 alike, with a hand-written adjoint. `freqdomain_fir` applies such a response (or any other) to
+audio: irfft(rfft(x, n_fft) * H, n_fft) on the library's own transforms (csrc/fdfir.hip), float32, n_fft a power of two from 8 to 2^20.
 """
 import functools
 import operator
@@ -92,8 +93,7 @@ def _frequency_domain_helper(name, line):
 
 # The reference's L1 helpers of the frequency-sampling method are not part of this package's boundary; they exist as names
 # so that `from dasp_pytorch_amd.signal import *` fails loudly at the call, not at import. one_pole_butter_lowpass / one_pole_filter
-# are dead code in the reference (they print to stdout).
-freqdomain_fir = _frequency_domain_helper("freqdomain_fir", "35-39")
+# are dead code in the reference (they print to stdout). freqdomain_fir is implemented below.
 one_pole_butter_lowpass = _frequency_domain_helper("one_pole_butter_lowpass", "169-198")
 one_pole_filter = _frequency_domain_helper("one_pole_filter", "201-239")
 
@@ -162,6 +162,67 @@ def fft_sosfreqz(sos: torch.Tensor, n_fft: int = 512):
                                   "(multiply the responses of successive calls for a longer cascade)")
     s = sos.to(_freqz_dtype(sos))
     return _ops.freqz(s[..., :3], s[..., 3:], n)
+
+
+FDFIR_MIN_N, FDFIR_MAX_N = 8, 1 << 20        # transform lengths of freqdomain_fir (csrc/fdfir.hip): the powers of two in between
+FDFIR_MAX_SHARED = 8                         # rows that share one response inside the kernels (one wave / workgroup walks them in turn)
+
+
+def freqdomain_fir(x: torch.Tensor, H: torch.Tensor, n_fft: int):
+    """Filter by a supplied frequency response: irfft(rfft(x, n_fft) * H, n_fft) (reference: dasp_pytorch/signal.py:35-39) - circular
+    convolution of length n_fft. The result is not cropped: its last dimension is n_fft.
+
+    x (..., T) real float32, T >= 1: zero-padded to n_fft, or cropped to it, as torch.fft.rfft does. H (..., n_fft // 2 + 1) complex64 in
+    rfft order; its leading dimensions broadcast against x.shape[:-1]. A real H is a zero-phase response (the reference's `H.type_as(X)`)
+    and gets a real gradient. The imaginary parts of the DC and Nyquist bins do not reach the output (irfft ignores them); their gradient
+    is exactly 0. n_fft: an integer or a 0-dim integer tensor, a power of two from 8 to 2^20 (NotImplementedError otherwise).
+    Differentiable w.r.t. x and H (PyTorch's convention for complex gradients); gradients are bit-identical from run to run.
+
+    One launch per direction up to n_fft = 8192, a four-step transform above (csrc/fdfir.hip, through torch.ops.dasp.freqdomain_fir). A
+    response per row, or one shared by the trailing dimensions of x (H (bs, 1, bins) on x (bs, chs, T): the reference's own call) is read
+    as it is (up to 8 rows per response) - two rows that share a response travel as one complex transform; any other broadcast pattern
+    is expanded first.
+    float64 / complex128 input is refused unless config.plan.fp64_as_fp32 (then cast, computed in float32 and cast back)."""
+    from .ops64 import require_fp32_ok
+    for name, t in (("x", x), ("H", H)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    n = _freqz_n(n_fft)
+    if n < FDFIR_MIN_N or n > FDFIR_MAX_N or n & (n - 1):
+        raise NotImplementedError(f"freqdomain_fir: n_fft = {n}; supported are the powers of two from {FDFIR_MIN_N} to {FDFIR_MAX_N} (2^20). "
+                                  "For another length: torch.fft.irfft(torch.fft.rfft(x, n_fft) * H, n_fft)")
+    if x.is_complex() or not x.is_floating_point():
+        raise TypeError(f"freqdomain_fir: x must be a real floating-point tensor, got {x.dtype}")
+    if not (H.is_complex() or H.is_floating_point()):
+        raise TypeError(f"freqdomain_fir: H must be a complex or real floating-point tensor, got {H.dtype}")
+    if x.dim() < 1 or x.shape[-1] < 1:
+        raise ValueError(f"freqdomain_fir: x needs at least one sample along its last dimension, got shape {tuple(x.shape)}")
+    bins = n // 2 + 1
+    if H.dim() < 1 or H.shape[-1] != bins:
+        raise RuntimeError(f"freqdomain_fir: H has {H.shape[-1] if H.dim() else 0} bins along its last dimension, n_fft = {n} needs {bins}")
+    require_fp32_ok(x, "freqdomain_fir")
+    if H.dtype in (torch.float64, torch.complex128):
+        require_fp32_ok(torch.empty(0, dtype=torch.float64), "freqdomain_fir (H)")
+    _lib.require_device(x, "x")
+    _lib.require_device(H, "H")
+    _lib.require_same_device(x, H=H)
+    out_dtype = torch.float64 if torch.float64 in (x.dtype, H.real.dtype if H.is_complex() else H.dtype) else torch.float32
+    xx = x.to(torch.float32)
+    Hc = H.to(torch.complex64) if H.is_complex() else torch.complex(H.to(torch.float32), torch.zeros_like(H, dtype=torch.float32))
+    lead = torch.broadcast_shapes(xx.shape[:-1], Hc.shape[:-1])
+    T = xx.shape[-1]
+    if tuple(xx.shape[:-1]) != tuple(lead):
+        xx = xx.expand(*lead, T)
+    hl = (1,) * (len(lead) - (Hc.dim() - 1)) + tuple(Hc.shape[:-1])
+    # H shared by the trailing dimensions of x (hl = lead[:m] + (1, ..., 1)) goes in as it is; anything else is expanded to a response per row
+    m = len(lead)
+    while m > 0 and hl[m - 1] == 1:
+        m -= 1
+    shared = functools.reduce(operator.mul, lead[m:], 1)
+    if hl[:m] != tuple(lead[:m]) or shared > FDFIR_MAX_SHARED:
+        Hc = Hc.expand(*lead, bins)
+    y = _ops.freqdomain_fir(xx.reshape(-1, T), Hc.reshape(-1, bins), n).reshape(*lead, n)
+    return y if out_dtype == torch.float32 else y.to(out_dtype)
 
 
 def sosfilt_via_fsm(sos: torch.Tensor, x: torch.Tensor):

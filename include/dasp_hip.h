@@ -478,6 +478,25 @@ int dasp_freqz_backward(const void* b, const void* a, const void* gH, int rows, 
                         long work_doubles, void* gb, void* ga, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Filtering by a supplied frequency response.  Replaces dasp_pytorch.signal.freqdomain_fir (dasp_pytorch/signal.py:35-39):
+ * y = irfft(rfft(x, n_fft) * H, n_fft), circular convolution, not cropped (csrc/fdfir.hip).
+ *   x, gx: (rows, T) fp32, T >= 1 (zero-padded to n_fft, or cropped to it; gx is 0 for cropped samples);  y, gy: (rows, n_fft) fp32;
+ *   H, gH: (h_rows, n_fft/2 + 1) interleaved complex fp32 in natural rfft order, rows = h_rows * chs: the chs consecutive rows of an item
+ *   share one response (h_rows = rows: a response per row). The imaginary parts of bins 0 and n_fft/2 are ignored; their gradient is 0.
+ *   gH = w_k / n conj(X_k) GY_k summed over the item's rows in a fixed order (no atomics; PyTorch's complex-gradient convention).
+ *   n_fft: a power of two, 8 .. 2^20, else DASP_ERR_UNSUPPORTED;  tw: 4096 complex twiddles from dasp_mrstft_table;
+ *   work: dasp_fdfir_work_floats(...) floats of scratch (0 up to n_fft = 8192: one launch per direction; -1: unsupported arguments),
+ *   its size passed as work_floats (checked: DASP_ERR_ARG). The forward call needs the frames of x only:
+ *   2 * h_rows * ((rows / h_rows + 1) / 2) * n_fft floats, one complex frame per two rows of an item.
+ *   dasp_fdfir_backward: gx and / or gH may be NULL (skipped); x may be NULL when gH is.
+ * ------------------------------------------------------------------------------------------- */
+long dasp_fdfir_work_floats(long rows, long T, long n_fft, long h_rows);
+int dasp_fdfir_forward(const float* x, const void* H, const void* tw, float* y, float* work, long work_floats, long rows, long T, long n_fft,
+                       long h_rows, void* stream);
+int dasp_fdfir_backward(const float* x, const void* H, const float* gy, const void* tw, float* gx, void* gH, float* work, long work_floats,
+                        long rows, long T, long n_fft, long h_rows, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Double precision.  The reference follows the dtype of its input (`.type_as(x)`, dasp_pytorch/signal.py:113,119,
  * functional.py:211), so float64 tensors mean float64 arithmetic. These entry points are that path for the recurrences and the
  * elementwise effects - the same maps as above evaluated plainly, one thread per row / batch item, sequential in time: meant for
