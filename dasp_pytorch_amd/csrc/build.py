@@ -8,6 +8,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libdasp_hip.so")
 ARCH = "gfx950"
+# compile flags of every kernel source (scripts/isa_histogram.py compiles to assembly with the same ones)
+HIPCC_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wno-pass-failed", "-Wno-inline-asm"]
 
 
 def kernel_source_hash(files=("sosfilt.hip", "sos_tile.hpp", "sos_gram_fin.hpp", "common.hpp"), root=HERE):
@@ -61,7 +63,7 @@ def build_lib(force=False, verbose=False):
         newest = max(os.path.getmtime(src), os.path.getmtime(HEADER)) if stamp else max(
             os.path.getmtime(src), *[os.path.getmtime(os.path.join(HERE, f)) for f in os.listdir(HERE) if f.endswith(".hpp")])
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < newest:
-            jobs.append([hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wno-pass-failed", "-Wno-inline-asm"]
+            jobs.append([hipcc] + HIPCC_FLAGS
                         + ([f"-DDASP_ABI_HASH={abi_hash()}ULL"] if stamp else []) + ["-c", src, "-o", obj])
         objs.append(obj)
     if jobs:        # one hipcc per stale source, side by side (sosfilt.hip alone is most of a serial build)

@@ -175,15 +175,39 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
 // two accumulators halve the dependent chain.
 #define TLD2(p) (*reinterpret_cast<const f2*>(p))
 #define TLD4(p) (*reinterpret_cast<const f4*>(p))
+// One section's 16-term table product as one asm statement (see blk_apply_s: no padding between the FMAs): z0 takes the even samples,
+// z1 the odd ones, terms in ascending n - z0 = fma2_bcast<0>(G[n], (X[n], X[n+1]), z0), z1 = fma2_bcast<1>(G[n+1], (X[n], X[n+1]), z1),
+// n = 0, 2, .., 14 - and the result is z0 + z1 (the packed add ends the statement). Operands: %0 %1 the accumulators, %2 .. %17 G[0 .. 15] (SGPR pairs), %18 .. %25 the sample pairs.
+#define DASP_TP_PAIR(ge, go, xy) "v_pk_fma_f32 %0, %" #ge ", %" #xy ", %0 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t" \
+                                 "v_pk_fma_f32 %1, %" #go ", %" #xy ", %1 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+__device__ __forceinline__ f2 table_product16(const f2 (&G)[16], const float (&X)[16]) {
+    f2 z0 = f2{0.f, 0.f}, z1 = f2{0.f, 0.f};
+    asm(DASP_TP_PAIR(2, 3, 18) DASP_TP_PAIR(4, 5, 19) DASP_TP_PAIR(6, 7, 20) DASP_TP_PAIR(8, 9, 21)
+        DASP_TP_PAIR(10, 11, 22) DASP_TP_PAIR(12, 13, 23) DASP_TP_PAIR(14, 15, 24) DASP_TP_PAIR(16, 17, 25)
+        "v_pk_add_f32 %0, %0, %1"
+        : "+&v"(z0), "+&v"(z1)
+        : "s"(G[0]), "s"(G[1]), "s"(G[2]), "s"(G[3]), "s"(G[4]), "s"(G[5]), "s"(G[6]), "s"(G[7]),
+          "s"(G[8]), "s"(G[9]), "s"(G[10]), "s"(G[11]), "s"(G[12]), "s"(G[13]), "s"(G[14]), "s"(G[15]),
+          "v"(f2{X[0], X[1]}), "v"(f2{X[2], X[3]}), "v"(f2{X[4], X[5]}), "v"(f2{X[6], X[7]}),
+          "v"(f2{X[8], X[9]}), "v"(f2{X[10], X[11]}), "v"(f2{X[12], X[13]}), "v"(f2{X[14], X[15]}));
+    return z0;
+}
 
 // f += [c.x c.z; c.y c.w] * (t1, t2)   (column-major 2x2 block, packed FMAs)
 // f + [[c.x, c.z], [c.y, c.w]] * t with t.x / t.y broadcast by op_sel: two issue slots per packed FMA and nothing else (the splat
 // form below costs two extra v_mov per application). _s: wave-uniform block (SGPRs), _v: per-lane block.
+// Both packed FMAs are ONE asm statement: the compiler's hazard recogniser cannot look into an asm statement and pads every asm -> asm
+// boundary with an s_nop (an issue slot each; the hardware interlocks dependent VALU results, and the compiler's own packed FMAs carry
+// no such padding). Same two instructions in the same order as fma2_bcast<0>(col0, t, fma2_bcast<1>(col1, t, f)).
+#define DASP_BLK_APPLY_ASM "v_pk_fma_f32 %0, %1, %3, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t" \
+                           "v_pk_fma_f32 %0, %2, %3, %0 op_sel:[0,0,0] op_sel_hi:[1,0,1]"
 __device__ __forceinline__ f2 blk_apply_s(f4 c, f2 t, f2 f) {
-    return fma2_bcast<0>(f2{c.x, c.y}, t, fma2_bcast<1>(f2{c.z, c.w}, t, f));
+    asm(DASP_BLK_APPLY_ASM : "+&v"(f) : "s"(f2{c.z, c.w}), "s"(f2{c.x, c.y}), "v"(t));
+    return f;
 }
 __device__ __forceinline__ f2 blk_apply_v(f4 c, f2 t, f2 f) {
-    return fma2_bcast_v<0>(f2{c.x, c.y}, t, fma2_bcast_v<1>(f2{c.z, c.w}, t, f));
+    asm(DASP_BLK_APPLY_ASM : "+&v"(f) : "v"(f2{c.z, c.w}), "v"(f2{c.x, c.y}), "v"(t));
+    return f;
 }
 __device__ __forceinline__ f2 blk_apply(f4 c, float t1, float t2, f2 f) {
     return fma2(f2{c.x, c.y}, splat(t1), fma2(f2{c.z, c.w}, splat(t2), f));

@@ -1057,15 +1057,39 @@ sos_chain_kernel(const double* __restrict__ segtab, int tab_bcast, int C, const 
 // inside it, which measured 3 % better than one block.) sos_gram_finalize_kernel turns sum-over-rows(C) into the gradients (fp64 basis
 // responses). Executable specification and error budget: oracle/chunkscan_model.py (gram_backward_row), tests/test_oracle_cpu.py.
 // gram: [row][16 registers][64 lanes] doubles - register 4 (2 bv + bu) + e of lane l = C[16 bv + 4 (l / 16) + e][16 bu + l % 16].
-__device__ __forceinline__ void gram_operands_load(const float* img, float (&R)[16], int lane) {
+// Steps m and m + 4 differ by exactly 64 floats and the XOR term depends on m & 3 only, so an image is four lane-dependent slots (one per
+// m & 3, the same for every image of the wave: GramSlots, once per kernel) plus constants, and every image is 8 two-address reads
+// (ds_read2st64_b32). The slots are opaque to the compiler: left to itself it folds 64 m into sixteen address registers per image pair
+// and pairs 18 of the 32 possible reads.
+struct GramSlots { int e[4]; };
+__device__ __forceinline__ GramSlots gram_operand_slots(int lane) {
     const int k = lane >> 4, i = lane & 15;
+    GramSlots s;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) R[m] = img[64 * m + 16 * k + 4 * ((i >> 2) ^ (m & 3)) + (i & 3)];      // (swz_slot(4 m + k, i / 4), entry i % 4)
+    for (int j = 0; j < 4; ++j) {
+        s.e[j] = 16 * k + 4 * ((i >> 2) ^ j) + (i & 3);      // (swz_slot(4 m + k, i / 4), entry i % 4, for m % 4 == j)
+        asm("" : "+v"(s.e[j]));
+    }
+    return s;
+}
+__device__ __forceinline__ void gram_operands_load(const float* img, float (&R)[16], const GramSlots& s) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int m = 8 * h + j;
+            R[m] = img[s.e[j] + 64 * m];
+            R[m + 4] = img[s.e[j] + 64 * (m + 4)];
+        }
 }
 
 // FLAGS & BWD_NOGX: no gradient for x is wanted (the EQ is the first effect of the reference's chain: examples/style_transfer.py:150) - no
 // output map, 4 B per sample less.
 constexpr int BWD_NOGX = 2;
+// FLAGS & BWD_ALLFULL: every tile of every row is full and vectorisable (N a multiple of the tile, 16-byte aligned rows: the headline and
+// every length the reference trains on) - the tile loop carries no `full` tests, no guarded load / store code and a constant number of
+// stores in flight. The launcher decides; the general instantiation serves ragged rows. (SEG 0 only.)
+constexpr int BWD_ALLFULL = 4;
 // SEG = 1: segmented rows (few rows): workgroup = (row, segment of Tseg tiles), the adjoint state entering the segment from above comes from
 // segstart[row][segment][2S] (the scan-only pre-pass of sos_bwd_kernel<SEG = 2> and its chain); one matrix per (row, segment).
 template <int S, int L, int W, int FLAGS, int SEG = 0>
@@ -1076,11 +1100,14 @@ sos_bwd_gram_kernel(const float* __restrict__ tab, int tab_bcast, const float* _
                     GramFuse fz = GramFuse{}) {
     using LY = SosLayout<S, L>;
     static_assert(L == 16 && 2 * S <= 16, "one 16-wide block of state components");
-    constexpr bool GX = !(FLAGS & BWD_NOGX);
+    constexpr bool GX = !(FLAGS & BWD_NOGX), ALLFULL = (FLAGS & BWD_ALLFULL) != 0;
+    static_assert(!ALLFULL || SEG == 0, "the all-full variant exists for whole rows only");
     constexpr int TS = 64 * L, IMG = 64 * L, REGION = 4 * IMG;      // per wave: gy, x, states, scratch (chunk products / adjoint states / gx on its way out)
     constexpr int LDS_T = W * REGION, LDS_MB = W * S * 4, LDS_PW = S * 64 * 4;
     static_assert(REGION >= 2 * 1024, "a wave's region holds its 1024 fp64 sums at the end");
     __shared__ __attribute__((aligned(16))) float lds[LDS_T + LDS_MB + LDS_PW];
+    // (taking the wave number - and with it the loop counter, the tile index and every test on them - through an SGPR turns ~140 exec-mask
+    // instructions per tile into ~20 scalar ones and measured 3 - 4 us SLOWER at the headline shape: profiles/r08/README.md)
     const int lane = lane_id(), wave = wave_id();
     const int wg = blockIdx.x;
     if constexpr (SEG != 0) {
@@ -1131,6 +1158,7 @@ sos_bwd_gram_kernel(const float* __restrict__ tab, int tab_bcast, const float* _
     // states: image slot 64 q + lane is granule g = (lane % 4) ^ (lane / 16) of chunk 16 q + lane / 4 (swz_slot), granule = section pair;
     // the pad granules (g >= S / 2) fetch pair 0 again: finite numbers in columns of C that nobody reads
     const int sg_ = (lane & 3) ^ (lane >> 4), soff = ((sg_ < S / 2 ? sg_ : 0) * 64 + (lane >> 2)) * 4;
+    auto is_full = [&](int tt) { return ALLFULL || tile_full<L>((long)tt * TS, N, vec); };
     auto issue_dma = [&](int tt, bool full, int parts = 7) {     // parts: 1 x, 2 gy, 4 saved states
         if (full && (parts & 1)) tile_dma_issue_swz(xr + (size_t)tt * TS, a_x, lane);
         if (full && (parts & 2)) tile_dma_issue_swz(gr + (size_t)tt * TS, a_g, lane);
@@ -1142,33 +1170,29 @@ sos_bwd_gram_kernel(const float* __restrict__ tab, int tab_bcast, const float* _
     };
     if constexpr (SEG == 3) {
         // (the pass's first x tile and saved states are on their way while the sweep and the look-back run: their images are not the sweep's)
-        if (wave < nr) issue_dma(t1 - 1 - wave, tile_full<L>((long)(t1 - 1 - wave) * TS, N, vec), 5);
+        if (wave < nr) issue_dma(t1 - 1 - wave, is_full(t1 - 1 - wave), 5);
         // ---- the adjoint scan-only sweep over the segment's gy (sos_bwd_kernel<SEG = 2>'s loop with this kernel's table products), the
         //      look-back, and wave 0's inbox for the pass ----
         const unsigned tag = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, tb[LY::TAG])) ^ 0x5A5A0000u;     // (the forward pass's words carry the plain tag)
         unsigned long long* z64 = reinterpret_cast<unsigned long long*>(const_cast<float*>(segstart)) + (size_t)row * G * (2 * S);
-        if (wave < nr && tile_full<L>((long)(t1 - 1 - wave) * TS, N, vec)) tile_dma_issue_swz(gr + (size_t)(t1 - 1 - wave) * TS, a_g, lane);
+        if (wave < nr && is_full(t1 - 1 - wave)) tile_dma_issue_swz(gr + (size_t)(t1 - 1 - wave) * TS, a_g, lane);
         for (int r = wave; r < nr; r += W) {
             const int t = t1 - 1 - r;
             int toff = 0;
             asm volatile("" : "+s"(toff));
             const float* __restrict__ tbl = tb + toff;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (!tile_full<L>((long)t * TS, N, vec)) tile_global_to_swz_guarded(tbg, gr, (long)t * TS, N);
+            if (!is_full(t)) tile_global_to_swz_guarded(tbg, gr, (long)t * TS, N);
             float GYc[L], Z[L];
             lds_to_chunks_swz<L>(tbg, GYc, 63 - lane);
             pin(GYc);
             if (r + W < nr) tile_dma_issue_swz(gr + (size_t)(t - W) * TS, a_g, lane);      // (tiles below a row's last one are always full)
 #pragma unroll
             for (int k = 0; k < S; ++k) {
-                f2 z0 = f2{0.f, 0.f}, z1 = f2{0.f, 0.f};
+                f2 G[L];
 #pragma unroll
-                for (int n = 0; n < L; n += 2) {
-                    const f2 xy = f2{GYc[n], GYc[n + 1]};
-                    z0 = fma2_bcast<0>(TLD2(tbl + LY::GAT + (k * L + n) * 2), xy, z0);
-                    z1 = fma2_bcast<1>(TLD2(tbl + LY::GAT + (k * L + n + 1) * 2), xy, z1);
-                }
-                const f2 z = z0 + z1;
+                for (int n = 0; n < L; ++n) G[n] = TLD2(tbl + LY::GAT + (k * L + n) * 2);
+                const f2 z = table_product16(G, GYc);
                 Z[2 * k] = z.x; Z[2 * k + 1] = z.y;
             }
 #pragma unroll
@@ -1192,28 +1216,33 @@ sos_bwd_gram_kernel(const float* __restrict__ tab, int tab_bcast, const float* _
         __shared__ double lb_st[2][2 * S];
         // the pass's first gy tile is on its way as well now (x and the saved states since before the sweep); the look-back stages its words
         // in wave 0's scratch image, idle between tiles
-        if (wave < nr) issue_dma(t1 - 1 - wave, tile_full<L>((long)(t1 - 1 - wave) * TS, N, vec), 2);
+        if (wave < nr) issue_dma(t1 - 1 - wave, is_full(t1 - 1 - wave), 2);
         lookback_start<S, W>(z64, seg, G, -1, fz.segtab_adj + (size_t)(row / C) * 2 * (2 * S) * (2 * S), tag, lds, t1 + SEQ2, pw_lds + LDS_PW + 3 * IMG, lb_st, fz.err, DASP_DEVERR_SOS_BWD);
         __syncthreads();
     }
-    if (SEG != 3 && wave < nr) issue_dma(t1 - 1 - wave, tile_full<L>((long)(t1 - 1 - wave) * TS, N, vec));
+    if (SEG != 3 && wave < nr) issue_dma(t1 - 1 - wave, is_full(t1 - 1 - wave));
     int stores_in_flight = 0;
     float Aop[4], AT[4], AO[4];
     chunk_table_operands<S, L>(tb + LY::GAT, Aop, lane);
     if (GX) cascade_map_operands<S, L>(tb + LY::YMA, LY::YMC, AT, AO, lane);
+    const GramSlots gslots = gram_operand_slots(lane);
     double gsum[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) gsum[i] = 0.0;
+    // all tiles full, with gx: the wait at the top of a tile is for everything but the L / 4 output stores of the tile before - a constant
+    // once the first tile's images (the only loads without stores behind them) have landed
+    if (ALLFULL && GX) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     for (int r = wave; r < nr; r += W) {
         const int t = t1 - 1 - r;
         int toff = 0;
         asm volatile("" : "+s"(toff));   // opaque uniform 0: keeps the scalar table loads inside the tile loop
         const float* __restrict__ tbl = tb + toff;
-        const bool full = tile_full<L>((long)t * TS, N, vec);
+        const bool full = is_full(t);
         WIDE_PRIO(DASP_SCAN_PRIO);
         TRACE(16);
-        if (full && GX && stores_in_flight == L / 4) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(L / 4) : "memory");
+        if (ALLFULL && GX) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(L / 4) : "memory");
+        else if (full && GX && stores_in_flight == L / 4) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(L / 4) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (!full) {
             tile_global_to_swz_guarded(tbx, xr, (long)t * TS, N);
@@ -1224,14 +1253,14 @@ sos_bwd_gram_kernel(const float* __restrict__ tab, int tab_bcast, const float* _
         f4 Bg[4];
         float Rg[16], Rx[16], Rs[16];
         chunk_products_load(tbg, Bg, lane);
-        gram_operands_load(tbg, Rg, lane);
-        gram_operands_load(tbx, Rx, lane);
-        gram_operands_load(tsi, Rs, lane);
+        gram_operands_load(tbg, Rg, gslots);
+        gram_operands_load(tbx, Rx, gslots);
+        gram_operands_load(tsi, Rs, gslots);
         float GYc[L];
         lds_to_chunks_swz<L>(tbg, GYc, cl);
         pin(GYc);
         pin(Bg); pin(Rg); pin(Rx); pin(Rs);
-        if (r + W < nr) issue_dma(t - W, tile_full<L>((long)(t - W) * TS, N, vec));     // the three images are in registers now
+        if (r + W < nr) issue_dma(t - W, is_full(t - W));     // the three images are in registers now
         TRACE(18);
         float Z[L];
         {   // zero-state chunk end states on the VALU (packed FMAs against the wave-uniform table in SGPRs, one section's 16 entries at a time,
@@ -1242,25 +1271,20 @@ sos_bwd_gram_kernel(const float* __restrict__ tab, int tab_bcast, const float* _
             for (int n = 0; n < L; ++n) G[n] = TLD2(tbl + LY::GAT + 2 * n);
 #pragma unroll
             for (int k = 0; k < S; ++k) {
-                f2 z0 = f2{0.f, 0.f}, z1 = f2{0.f, 0.f};
-#pragma unroll
-                for (int n = 0; n < L; n += 2) {
-                    const f2 xy = f2{GYc[n], GYc[n + 1]};
-                    z0 = fma2_bcast<0>(G[n], xy, z0);
-                    z1 = fma2_bcast<1>(G[n + 1], xy, z1);
-                }
+                const f2 z = table_product16(G, GYc);
                 __builtin_amdgcn_sched_barrier(0);
                 if (k + 1 < S) {
 #pragma unroll
                     for (int n = 0; n < L; ++n) G[n] = TLD2(tbl + LY::GAT + ((k + 1) * L + n) * 2);
                 }
-                const f2 z = z0 + z1;
                 Z[2 * k] = z.x; Z[2 * k + 1] = z.y;
             }
 #pragma unroll
             for (int c = 2 * S; c < L; ++c) Z[c] = 0.f;
         }
-        pin(Z); TRACE(25);
+#pragma unroll
+        for (int c = 0; c < 2 * S; ++c) pin(Z[c]);      // (the scan reads no more: pinning the zeros behind them would materialise them)
+        TRACE(25);
         // the half of the tile's products that does not need the scan: (gy x) and (gy states) blocks of C, TA gy of gx - they run on the
         // matrix cores while the VALU scans
         f4 cacc[4], oacc[4];
@@ -1312,7 +1336,7 @@ sos_bwd_gram_kernel(const float* __restrict__ tab, int tab_bcast, const float* _
         }
         {
             float Rl[16];
-            gram_operands_load(tbo, Rl, lane);
+            gram_operands_load(tbo, Rl, gslots);
             pin(Rl); TRACE(27);
 #pragma unroll
             for (int m = 0; m < 16; ++m) {
@@ -1567,14 +1591,17 @@ int dasp_sosfilt_backward_ex(const float* tab, int Bs, const float* x, const flo
         const dim3 g(B * C), b(64 * kWB), b2(128 * kWB);
         double* gm = reinterpret_cast<double*>(partials);
         const bool wide = wide_rows(B * C);
-        if (wide && !gx)
-            hipLaunchKernelGGL((sos_bwd_gram_kernel<SS, kL, 2 * kWB, BWD_NOGX>), g, b2, 0, st, tab, bc, x, gy, carries, gx, gm, C, (int)N, nt, vec);
-        else if (wide)
-            hipLaunchKernelGGL((sos_bwd_gram_kernel<SS, kL, 2 * kWB, 0>), g, b2, 0, st, tab, bc, x, gy, carries, gx, gm, C, (int)N, nt, vec);
-        else if (!gx)
-            hipLaunchKernelGGL((sos_bwd_gram_kernel<SS, kL, kWB, BWD_NOGX>), g, b, 0, st, tab, bc, x, gy, carries, gx, gm, C, (int)N, nt, vec);
-        else
-            hipLaunchKernelGGL((sos_bwd_gram_kernel<SS, kL, kWB, 0>), g, b, 0, st, tab, bc, x, gy, carries, gx, gm, C, (int)N, nt, vec);
+        // FLAGS: no gx wanted -> no output map; no ragged tile anywhere -> the variant without the guarded paths
+        auto launch = [&](auto flags) {
+            constexpr int F = decltype(flags)::value;
+            if (wide) hipLaunchKernelGGL((sos_bwd_gram_kernel<SS, kL, 2 * kWB, F>), g, b2, 0, st, tab, bc, x, gy, carries, gx, gm, C, (int)N, nt, vec);
+            else hipLaunchKernelGGL((sos_bwd_gram_kernel<SS, kL, kWB, F>), g, b, 0, st, tab, bc, x, gy, carries, gx, gm, C, (int)N, nt, vec);
+        };
+        const bool allfull = vec && N % (64 * kL) == 0;
+        if (allfull && !gx) launch(std::integral_constant<int, BWD_NOGX | BWD_ALLFULL>{});
+        else if (allfull) launch(std::integral_constant<int, BWD_ALLFULL>{});
+        else if (!gx) launch(std::integral_constant<int, BWD_NOGX>{});
+        else launch(std::integral_constant<int, 0>{});
         return check_launch();
     });
 }
