@@ -99,6 +99,13 @@ SIGNATURES = {
     "dasp_fir_same_forward": (_i, [_p] * 5 + [_i, _i, _i, _p]),
     "dasp_fir_same_adjoint": (_i, [_p] * 5 + [_i, _i, _i, _p]),
     "dasp_fir_taps_store": (_i, [_p, _p, _i, _p]),
+    "dasp_mel_table_floats": (_l, [_i, _i]),
+    "dasp_mel_table_store": (_i, [_p, _p, _d, _i, _i, _p]),
+    "dasp_mel_table_dense": (_i, [_p, _p, _i, _i, _p]),
+    "dasp_mrstft_mel_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i]),
+    "dasp_mrstft_mel_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
+    "dasp_mrstft_mel_backward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
+    "dasp_mrstft_mel_backward_target": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
     "dasp_lfilter_work_doubles": (_l, [_i, _l, _i, _l]),
     "dasp_lfilter_forward": (_i, [_p, _p, _p, _i, _p, _p, _p, _l, _i, _l, _i, _i, _l, _p]),
     "dasp_lfilter_backward": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l, _i, _i, _l, _p]),

@@ -487,6 +487,246 @@ struct FirTaps { float h[FIR_MAXTAPS]; int n; };
 __global__ void fir_taps_kernel(float* __restrict__ dst, FirTaps taps) {
     if ((int)threadIdx.x < taps.n) dst[threadIdx.x] = taps.h[threadIdx.x];
 }
+
+// ---- mel-scaled magnitudes: auraloss's scale="mel" (M = W |X| per frame, W = librosa.filters.mel(sr, n_fft, n_mels), Slaney) -----------
+// The sums of a resolution then run over rows x frames x n_bins of M_P = W |P|, M_T = W |T| (no clamp after the projection), and the
+// gradient goes back through W^T: dL/d|P|[k] = sum_m W[m, k] dL/dM_P[m]. The filters are triangles between consecutive edge
+// frequencies e[0 .. B+1], so a filter's support is a run of bins and a bin lies in at most two filters, m0 and m0 + 1. One table per
+// resolution (K = n_fft / 2 + 1 bins, B filters) serves both directions:
+//   f2  w[K]        the bin's weights in filters m0 and m0 + 1 (0 where that filter does not exist or does not reach the bin)
+//   int m0[K]       0 .. B - 1
+//   int span[B][2]  first bin and bin count of the filter's support (count 0: a filter narrower than the bin spacing)
+// built on the device in fp64 from the edges, which arrive as kernel arguments (fir_taps_kernel's route: a kernel node of a captured graph).
+// The kernels are mrstft_fwd_kernel / mrstft_bwd_kernel (col_fft, every power of two 8 .. 8192) with the magnitudes of the one-sided
+// bins laid out in the exchange buffer, free after frames_to_spectra's last barrier, as mag[signal][bin][frame column]; the (filter, column)
+// sums are then gathered over each filter's support in a fixed order (no LDS atomics: the loss is bit-identical run to run).
+constexpr int MEL_MAXBINS = 256;
+struct MelEdges { double e[MEL_MAXBINS + 2]; };
+struct MelTab { const f2* w; const int* m0; const int* span; int B; };
+__host__ __device__ __forceinline__ long mel_table_len(int F, int B) { return 3L * (F / 2 + 1) + 2L * B; }
+__device__ __forceinline__ MelTab mel_tab(const float* t, int F, int B) {
+    const int K = F / 2 + 1;
+    return MelTab{reinterpret_cast<const f2*>(t), reinterpret_cast<const int*>(t + 2 * K), reinterpret_cast<const int*>(t + 3 * K), B};
+}
+
+__global__ void __launch_bounds__(256)
+mel_table_kernel(float* __restrict__ tab, MelEdges E, double sr, int F, int B) {
+    __shared__ double es[MEL_MAXBINS + 2];
+    for (int n = threadIdx.x; n < B + 2; n += 256) es[n] = E.e[n];
+    __syncthreads();
+    const int K = F / 2 + 1;
+    f2* w = reinterpret_cast<f2*>(tab);
+    int* m0 = reinterpret_cast<int*>(tab + 2 * K);
+    int* span = reinterpret_cast<int*>(tab + 3 * K);
+    auto freq = [&](int k) { return (double)k * sr / (double)F; };
+    // losses.mel_filterbank's expression, operation for operation (IEEE fp64 on both sides, nothing here can contract into an fma)
+    auto weight = [&](int m, double f) {
+        const double lo = (f - es[m]) / (es[m + 1] - es[m]), hi = (es[m + 2] - f) / (es[m + 2] - es[m + 1]);
+        return fmax(0.0, fmin(lo, hi)) * (2.0 / (es[m + 2] - es[m]));
+    };
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < K; k += gridDim.x * 256) {
+        const double f = freq(k);
+        int lo = 0, hi = B + 1;                                  // the last edge <= f (e[0] = 0 <= f)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (es[mid] <= f) lo = mid; else hi = mid - 1;
+        }
+        int m = lo - 1;                                          // f in [e[lo], e[lo + 1]): the falling side of filter lo - 1, the rising side of filter lo
+        m = m < 0 ? 0 : (m > B - 1 ? B - 1 : m);
+        const double wa = weight(m, f), wb = m + 1 < B ? weight(m + 1, f) : 0.0;
+        w[k] = f2{(float)wa, (float)wb};
+        m0[k] = m;
+    }
+    if (blockIdx.x == 0) {
+        for (int m = threadIdx.x; m < B; m += 256) {             // bins with e[m] < f_k < e[m + 2]
+            const double a = es[m], b = es[m + 2];
+            int k0 = (int)(a * (double)F / sr);
+            k0 = k0 < 0 ? 0 : (k0 > K ? K : k0);
+            while (k0 > 0 && freq(k0 - 1) > a) --k0;
+            while (k0 < K && freq(k0) <= a) ++k0;
+            int k1 = (int)(b * (double)F / sr);
+            k1 = k1 < 0 ? 0 : (k1 > K - 1 ? K - 1 : k1);
+            while (k1 < K - 1 && freq(k1 + 1) < b) ++k1;
+            while (k1 >= 0 && freq(k1) >= b) --k1;
+            span[2 * m] = k0 < K ? k0 : 0;
+            span[2 * m + 1] = k1 >= k0 ? k1 - k0 + 1 : 0;
+        }
+    }
+}
+// the dense (B, K) matrix a table stands for, as the forward reads it: bin k of filter m inside the filter's span, 0 outside
+__global__ void mel_dense_kernel(const float* __restrict__ tab, float* __restrict__ dense, int F, int B) {
+    const int K = F / 2 + 1, k = blockIdx.x * blockDim.x + threadIdx.x, m = blockIdx.y;
+    if (k >= K) return;
+    const MelTab t = mel_tab(tab, F, B);
+    const int first = t.span[2 * m], cnt = t.span[2 * m + 1], mk = t.m0[k];
+    const f2 w = t.w[k];
+    dense[(size_t)m * K + k] = (k >= first && k < first + cnt) ? (mk == m ? w.x : (mk + 1 == m ? w.y : 0.f)) : 0.f;
+}
+
+// mag[(s K + k) TC + c] = |X_s|[k] of frame column c, s = 0 (first signal), 1 (second); consecutive threads of a q write consecutive words
+template <int LOGN>
+__device__ __forceinline__ void mel_magnitudes_to_lds(float* mag, const ColCfg& g, int F, float eps, const float (&r)[8], const float (&i)[8],
+                                                      const float (&mr)[8], const float (&mi)[8]) {
+    const int K = F / 2 + 1;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int k = g.j + g.T * q;
+        if (k <= F / 2) {
+            const Bin b = split_bin(r[q], i[q], mr[q], mi[q]);
+            mag[k * g.TC + g.c] = sqrtf(fmaxf(b.pr * b.pr + b.pi * b.pi, eps));
+            mag[(K + k) * g.TC + g.c] = sqrtf(fmaxf(b.tr * b.tr + b.ti * b.ti, eps));
+        }
+    }
+    __syncthreads();
+}
+// The B x TC sums M_s[m][c] = sum_k W[m, k] mag_s[k][c]. Items (m, c), c fastest, so the threads of a wave read one contiguous segment
+// of a bin's row; where there are fewer items than threads (one 8192-point frame per workgroup, 128 filters of up to 254 bins) L = 2 .. 64
+// lanes share an item, stride through the filter's support and add up by butterflies - the same order every run. fn(owner, m, c, M_P, M_T)
+// is called by every thread (the shuffles in front of it need whole waves), owner true in one lane per item.
+template <int NT, class Fn>
+__device__ __forceinline__ void mel_filter_sums(const float* mag, int K, int TC, int logTC, const MelTab& t, Fn&& fn) {
+    const int items = t.B * TC;
+    int logL = 0;
+    while (logL < 6 && (items << (logL + 1)) <= NT) ++logL;
+    const int L = 1 << logL, sub = threadIdx.x & (L - 1), slot = threadIdx.x >> logL, nslots = NT >> logL;
+    for (int base = 0; base < items; base += nslots) {                // workgroup-uniform trip count
+        const int item = base + slot, m = item >> logTC, c = item & (TC - 1);
+        float mp = 0.f, mt = 0.f;
+        if (item < items) {
+            const int first = t.span[2 * m], cnt = t.span[2 * m + 1];
+            for (int s = sub; s < cnt; s += L) {
+                const int k = first + s;
+                const f2 w = t.w[k];
+                const float wk = t.m0[k] == m ? w.x : w.y;
+                mp = fmaf(wk, mag[k * TC + c], mp);
+                mt = fmaf(wk, mag[(K + k) * TC + c], mt);
+            }
+        }
+        for (int o = L >> 1; o > 0; o >>= 1) { mp += __shfl_xor(mp, o); mt += __shfl_xor(mt, o); }
+        fn(item < items && sub == 0, m, c, mp, mt);
+    }
+}
+
+template <int LOGN>
+__global__ void __launch_bounds__(ColGeom<LOGN>::T)
+mrstft_mel_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, const f2* __restrict__ tw, const float* __restrict__ tab,
+                      float* __restrict__ partials, StftSpec spec, int N, int res, int nbins) {
+    constexpr int NT = ColGeom<LOGN>::T, NW = NT / 64;
+    __shared__ f2 lds[ColGeom<LOGN>::LDS];
+    __shared__ float wlds[1 << LOGN];
+    __shared__ float red[NW][4];
+    StftRes R = spec.r[res];
+    if constexpr (LOGN == 13) R.logF = 13;
+    const ColCfg g = col_config<LOGN>(R.logF, threadIdx.x);
+    const int row = blockIdx.y, F = 1 << R.logF;
+    if ((int)blockIdx.x * g.TC >= R.frames) return;
+    const int frame = blockIdx.x * g.TC + g.c;
+    const bool live = frame < R.frames;
+    window_to_lds<NT>(wlds, R);
+    float r[8], i[8], mr[8], mi[8];
+    frames_to_spectra<LOGN>(pred + (size_t)row * N, target + (size_t)row * N, N, frame, live, R, g, tw, lds, wlds, r, i, mr, mi);
+    float* mag = reinterpret_cast<float*>(lds);                  // 2 (F/2 + 1) TC <= 5120 (8194) floats of the buffer's 9216 (18432)
+    mel_magnitudes_to_lds<LOGN>(mag, g, F, spec.eps, r, i, mr, mi);
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+    const int live_cols = R.frames - (int)blockIdx.x * g.TC;
+    const bool with_log = spec.w_lm != 0.f;                      // an empty filter has M_P = M_T = 0: allowed where the log term is not computed
+    mel_filter_sums<NT>(mag, F / 2 + 1, g.TC, LOGN - R.logF, mel_tab(tab, F, nbins), [&](bool owner, int, int c, float mp, float mt) {
+        if (owner && c < live_cols) {
+            const float d = mt - mp;
+            s1 = fmaf(d, d, s1);
+            s2 = fmaf(mt, mt, s2);
+            if (with_log) s3 += fabsf(logf(mp / mt));
+            s4 += fabsf(d);
+        }
+    });
+    s1 = wave_sum_uniform(s1); s2 = wave_sum_uniform(s2); s3 = wave_sum_uniform(s3); s4 = wave_sum_uniform(s4);
+    if (lane_id() == 0) { red[wave_id()][0] = s1; red[wave_id()][1] = s2; red[wave_id()][2] = s3; red[wave_id()][3] = s4; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        float a = 0.f;
+        for (int v = 0; v < NW; ++v) a += red[v][threadIdx.x];
+        partials[(((size_t)res * gridDim.y + row) * spec.groups + blockIdx.x) * 4 + threadIdx.x] = a;
+    }
+}
+// mrstft_finalize_kernel with count = rows x frames x n_bins
+__global__ void mrstft_mel_finalize_kernel(StftSpec spec, int rows, int nbins, float* __restrict__ stats, float* __restrict__ loss) {
+    if (threadIdx.x != 0) return;
+    double total = 0.0;
+    for (int res = 0; res < spec.nres; ++res) {
+        const double count = (double)rows * spec.r[res].frames * (double)nbins;
+        const double s1 = sqrt((double)stats[res * 4 + 0]), s2 = sqrt((double)stats[res * 4 + 1]), s3 = (double)stats[res * 4 + 2];
+        const double s4 = (double)stats[res * 4 + 3];
+        stats[res * 4 + 0] = (float)s1; stats[res * 4 + 1] = (float)s2; stats[res * 4 + 2] = (float)count; stats[res * 4 + 3] = (float)s3;
+        double l = 0.0;
+        if (spec.w_sc != 0.f) l += (double)spec.w_sc * (s1 / s2);
+        if (spec.w_lm != 0.f) l += (double)spec.w_lm * (s3 / count);
+        if (spec.w_lin != 0.f) l += (double)spec.w_lin * (s4 / count);
+        total += l;
+    }
+    loss[0] = (float)(total / spec.nres);
+}
+
+// dL/dM_P[m][c] goes to LDS behind the magnitudes (dm[m TC + c], n_bins TC <= (F/2 + 1) TC floats: 7680 (8450) of the buffer in all), each
+// thread then gathers dL/d|P| of its bins from its at most two filters; the rest is mrstft_bwd_kernel
+template <int LOGN, bool LIN>
+__global__ void __launch_bounds__(ColGeom<LOGN>::T)
+mrstft_mel_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, const f2* __restrict__ tw, const float* __restrict__ tab,
+                      const float* __restrict__ stats, const float* __restrict__ gloss, float* __restrict__ gpred, StftSpec spec, int N, int res,
+                      int nbins, int wrt_second) {
+    constexpr int NT = ColGeom<LOGN>::T;
+    __shared__ f2 lds[ColGeom<LOGN>::LDS];
+    __shared__ float wlds[1 << LOGN];
+    StftRes R = spec.r[res];
+    if constexpr (LOGN == 13) R.logF = 13;
+    const ColCfg g = col_config<LOGN>(R.logF, threadIdx.x);
+    const int row = blockIdx.y, F = 1 << R.logF, K = F / 2 + 1;
+    if ((int)blockIdx.x * g.TC >= R.frames) return;
+    const int frame = blockIdx.x * g.TC + g.c;
+    const bool live = frame < R.frames;
+    window_to_lds<NT>(wlds, R);
+    float r[8], i[8], mr[8], mi[8];
+    frames_to_spectra<LOGN>(pred + (size_t)row * N, target + (size_t)row * N, N, frame, live, R, g, tw, lds, wlds, r, i, mr, mi);
+    float* mag = reinterpret_cast<float*>(lds);
+    float* dm = mag + 2 * K * g.TC;
+    mel_magnitudes_to_lds<LOGN>(mag, g, F, spec.eps, r, i, mr, mi);
+    const GradK kk = grad_consts(spec, stats, gloss, res, wrt_second);
+    const MelTab t = mel_tab(tab, F, nbins);
+    const int TC = g.TC;
+    mel_filter_sums<NT>(mag, K, TC, LOGN - R.logF, t, [&](bool owner, int m, int c, float mp, float mt) {
+        if (owner) {
+            const float sgn = mt > mp ? 1.f : (mt < mp ? -1.f : 0.f);
+            float d = kk.sc * (mp - mt) + kk.self * mp;
+            if (mp > 0.f) d -= kk.lm * sgn / mp;                 // an empty filter (M_P = 0) reaches no bin
+            if constexpr (LIN) d -= kk.lin * sgn;
+            dm[m * TC + c] = d;
+        }
+    });
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int k = g.j + g.T * q;
+        float hr = 0.f, hi = 0.f;
+        if (live && k <= F / 2) {
+            const Bin b = split_bin(r[q], i[q], mr[q], mi[q]);
+            const float praw = b.pr * b.pr + b.pi * b.pi;
+            if (praw > spec.eps) {                               // the clamp has zero slope below eps
+                const f2 w = t.w[k];
+                const int ma = t.m0[k], mb = ma + 1 < nbins ? ma + 1 : ma;           // w.y = 0 where filter m0 + 1 does not exist
+                const float gm = (w.x * dm[ma * TC + g.c] + w.y * dm[mb * TC + g.c]) / sqrtf(praw);      // dL/d|P| / |P|
+                hr = gm * b.pr; hi = gm * b.pi;
+            }
+        }
+        r[q] = hr; i[q] = hi;
+    }
+    col_fft<1, LOGN>(r, i, g, tw, lds);          // its first exchange starts with a barrier: every dm read above is done by then
+    float* grow = gpred + (size_t)row * N;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int n = g.j + g.T * q;
+        const float w = hann_in_frame(n, F, R.win);
+        if (live && w != 0.f) atomicAdd(grow + reflect_index(frame * R.hop - F / 2 + n, N), w * r[q]);
+    }
+}
 }  // namespace dasp
 
 // ================================================================================================
@@ -528,6 +768,16 @@ void mrstft_bwd_launch(const float* first, const float* second, const void* tw, 
         case 13: hipLaunchKernelGGL((mrstft_bwd_kernel<13, LIN>), grid, dim3(1024), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
         default: hipLaunchKernelGGL((mrstft_bwd_kernel<12, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second);
     }
+}
+template <bool LIN>
+void mrstft_mel_bwd_launch(const float* first, const float* second, const void* tw, const float* tab, const float* stats, const float* gloss,
+                                  float* gfirst, const StftSpec& s, int rows, int N, int r, int n_bins, int wrt_second, hipStream_t st) {
+    const int TC = frames_per_group(s.r[r].logF);
+    const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
+    if (s.r[r].logF == 13)
+        hipLaunchKernelGGL((mrstft_mel_bwd_kernel<13, LIN>), grid, dim3(1024), 0, st, first, second, (const f2*)tw, tab, stats, gloss, gfirst, s, N, r, n_bins, wrt_second);
+    else
+        hipLaunchKernelGGL((mrstft_mel_bwd_kernel<12, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, tab, stats, gloss, gfirst, s, N, r, n_bins, wrt_second);
 }
 }  // namespace
 
@@ -643,6 +893,102 @@ int dasp_fir_taps_store(float* dst, const float* host_taps, int ntaps, void* str
     t.n = ntaps;
     hipLaunchKernelGGL(fir_taps_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, dst, t);
     return sl_check();
+}
+
+/* ---- scale="mel" ---- */
+static bool mel_bins_ok(int n_fft, int n_bins) {
+    int lg = 0;
+    while (lg < 30 && (1 << lg) < n_fft) ++lg;
+    return (1 << lg) == n_fft && lg >= 3 && lg <= 13 && n_bins >= 1 && n_bins <= MEL_MAXBINS && n_bins <= n_fft / 2 + 1;
+}
+static bool mel_spec(int N, int nres, const int* fft, const int* hop, const int* win, float eps, int n_bins, StftSpec* out, float w_sc = 1.f,
+                     float w_lm = 1.f, float w_lin = 0.f) {
+    if (!sl_spec(N, nres, fft, hop, win, eps, out, 13, w_sc, w_lm, w_lin)) return false;
+    for (int r = 0; r < nres; ++r)
+        if (!mel_bins_ok(fft[r], n_bins)) return false;
+    return true;
+}
+/* floats of one resolution's mel table; -1: n_fft not a power of two in 8..8192, or n_bins outside 1..min(256, n_fft / 2 + 1) */
+long dasp_mel_table_floats(int n_fft, int n_bins) {
+    return mel_bins_ok(n_fft, n_bins) ? mel_table_len(n_fft, n_bins) : -1;
+}
+/* host_edges: the n_bins + 2 edge frequencies in Hz (fp64, increasing, the first >= 0); they travel as kernel arguments */
+int dasp_mel_table_store(float* table, const double* host_edges, double sample_rate, int n_fft, int n_bins, void* stream) {
+    if (!table || !host_edges) return DASP_ERR_ARG;
+    if (!mel_bins_ok(n_fft, n_bins)) return DASP_ERR_UNSUPPORTED;
+    if (!(sample_rate > 0.0) || !std::isfinite(sample_rate) || !(host_edges[0] >= 0.0)) return DASP_ERR_ARG;
+    MelEdges E = {};
+    for (int n = 0; n < n_bins + 2; ++n) {
+        if (!std::isfinite(host_edges[n]) || (n > 0 && !(host_edges[n] > host_edges[n - 1]))) return DASP_ERR_ARG;
+        E.e[n] = host_edges[n];
+    }
+    const int K = n_fft / 2 + 1;
+    hipLaunchKernelGGL(mel_table_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table, E, sample_rate, n_fft, n_bins);
+    return sl_check();
+}
+/* dense: (n_bins, n_fft / 2 + 1) floats, the matrix the table stands for */
+int dasp_mel_table_dense(const float* table, float* dense, int n_fft, int n_bins, void* stream) {
+    if (!table || !dense) return DASP_ERR_ARG;
+    if (!mel_bins_ok(n_fft, n_bins)) return DASP_ERR_UNSUPPORTED;
+    const int K = n_fft / 2 + 1;
+    hipLaunchKernelGGL(mel_dense_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)n_bins), dim3(256), 0, (hipStream_t)stream, table, dense, n_fft, n_bins);
+    return sl_check();
+}
+long dasp_mrstft_mel_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins) {
+    StftSpec s;
+    if (!mel_spec(N, nres, fft, hop, win, 0.f, n_bins, &s)) return -1;
+    return (long)nres * rows * s.groups * 4;
+}
+/* mel_tables: nres device pointers (a host array), table r built by dasp_mel_table_store for fft[r] and n_bins */
+int dasp_mrstft_mel_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials, float* stats,
+                            float* loss, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
+                            float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
+    if (!pred || !target || !tw || !mel_tables || !partials || !stats || !loss || rows <= 0 || N <= 0) return DASP_ERR_ARG;
+    StftSpec s;
+    if (!mel_spec(N, nres, fft, hop, win, eps, n_bins, &s, w_sc, w_log_mag, w_lin_mag)) return DASP_ERR_UNSUPPORTED;
+    if (rows > 65535) return DASP_ERR_UNSUPPORTED;
+    for (int r = 0; r < nres; ++r)
+        if (!mel_tables[r]) return DASP_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    for (int r = 0; r < nres; ++r) {
+        const int TC = frames_per_group(s.r[r].logF);
+        const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
+        const float* tab = (const float*)mel_tables[r];
+        if (s.r[r].logF == 13) hipLaunchKernelGGL(mrstft_mel_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
+        else hipLaunchKernelGGL(mrstft_mel_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
+    }
+    hipLaunchKernelGGL(mrstft_reduce_kernel, dim3((unsigned)(nres * 4)), dim3(1024), 0, st, (const float*)partials, s, rows, stats);
+    hipLaunchKernelGGL(mrstft_mel_finalize_kernel, dim3(1), dim3(64), 0, st, s, rows, n_bins, stats, loss);
+    return sl_check();
+}
+static int mrstft_mel_backward_impl(const float* first, const float* second, const void* tw, const void* const* mel_tables, const float* stats,
+                                    const float* gloss, float* gfirst, int rows, int N, int nres, const int* fft, const int* hop, const int* win,
+                                    float eps, float w_sc, float w_lm, float w_lin, int n_bins, int wrt_second, void* stream) {
+    if (!first || !second || !tw || !mel_tables || !stats || !gloss || !gfirst || rows <= 0 || N <= 0) return DASP_ERR_ARG;
+    StftSpec s;
+    if (!mel_spec(N, nres, fft, hop, win, eps, n_bins, &s, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
+    if (rows > 65535) return DASP_ERR_UNSUPPORTED;
+    for (int r = 0; r < nres; ++r)
+        if (!mel_tables[r]) return DASP_ERR_ARG;
+    if (zero_async(gfirst, (size_t)rows * N * sizeof(float), (hipStream_t)stream) != hipSuccess) return sl_check();
+    for (int r = 0; r < nres; ++r) {
+        const float* tab = (const float*)mel_tables[r];
+        if (s.w_lin != 0.f) mrstft_mel_bwd_launch<true>(first, second, tw, tab, stats, gloss, gfirst, s, rows, N, r, n_bins, wrt_second, (hipStream_t)stream);
+        else mrstft_mel_bwd_launch<false>(first, second, tw, tab, stats, gloss, gfirst, s, rows, N, r, n_bins, wrt_second, (hipStream_t)stream);
+    }
+    return sl_check();
+}
+int dasp_mrstft_mel_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                             const float* gloss, float* gpred, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
+                             float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
+    return mrstft_mel_backward_impl(pred, target, tw, mel_tables, stats, gloss, gpred, rows, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag,
+                                    n_bins, 0, stream);
+}
+int dasp_mrstft_mel_backward_target(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                                    const float* gloss, float* gtarget, int rows, int N, int nres, const int* fft, const int* hop, const int* win,
+                                    float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
+    return mrstft_mel_backward_impl(target, pred, tw, mel_tables, stats, gloss, gtarget, rows, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag,
+                                    n_bins, 1, stream);
 }
 
 }  // extern "C"

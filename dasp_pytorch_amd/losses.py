@@ -2,10 +2,13 @@
 the effect chain (auraloss.freq.MultiResolutionSTFTLoss(), examples/style_transfer.py:341,363, auto_eq.py:252, virtual_analog.py:288).
 Same defaults and call convention as auraloss 0.4.0: `loss_fn(input, target)` with (bs, chs, seq_len) tensors, per resolution
 w_sc * spectral convergence + w_log_mag * log-magnitude L1 + w_lin_mag * linear-magnitude L1, mean over the resolutions; with
-perceptual_weighting=True both signals first go through auraloss's 101-tap A-weighting FIR. Both arguments receive gradients."""
+perceptual_weighting=True both signals first go through auraloss's 101-tap A-weighting FIR; with scale="mel", n_bins and sample_rate
+the three terms are taken on mel-scaled magnitudes W |X| (librosa's Slaney filterbank, mel_filterbank below), which is also what
+MelSTFTLoss computes. Both arguments receive gradients."""
 import ctypes
 import functools
 import math
+import operator
 
 import numpy as np
 import torch
@@ -36,6 +39,50 @@ def a_weighting_taps(sample_rate: float) -> np.ndarray:
     return taps
 
 
+MEL_MAX_BINS = 256
+_MEL_F_SP = 200.0 / 3.0                    # Slaney's mel scale (librosa.filters.mel, htk=False): linear below 1 kHz, 27 log steps up to 6.4 kHz
+_MEL_LOGSTEP = math.log(6.4) / 27.0
+
+
+def hz_to_mel(f):
+    f = np.asarray(f, dtype=np.float64)
+    return np.where(f < 1000.0, f / _MEL_F_SP, 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) / _MEL_LOGSTEP)
+
+
+def mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m < 15.0, _MEL_F_SP * m, 1000.0 * np.exp(_MEL_LOGSTEP * (np.maximum(m, 15.0) - 15.0)))
+
+
+@functools.lru_cache(maxsize=32)
+def mel_edges(sample_rate: float, n_mels: int) -> np.ndarray:
+    """The n_mels + 2 edge frequencies (Hz, float64) of librosa.filters.mel(sr=sample_rate, n_mels=n_mels) with its defaults fmin=0,
+    fmax=sr/2: equally spaced on the Slaney mel scale. The device table is built from these very numbers (dasp_mel_table_store)."""
+    e = np.ascontiguousarray(mel_to_hz(np.linspace(float(hz_to_mel(0.0)), float(hz_to_mel(float(sample_rate) / 2.0)), int(n_mels) + 2)))
+    e.flags.writeable = False
+    return e
+
+
+@functools.lru_cache(maxsize=32)
+def mel_filterbank(sample_rate: float, n_fft: int, n_mels: int) -> np.ndarray:
+    """librosa.filters.mel(sr=sample_rate, n_fft=n_fft, n_mels=n_mels) with librosa's defaults (fmin=0, fmax=sr/2, Slaney scale,
+    norm="slaney"), which is what auraloss's scale="mel" multiplies the magnitudes by: (n_mels, n_fft // 2 + 1) float32, computed in
+    float64 and rounded once. W[m, k] = max(0, min((f_k - e[m]) / (e[m+1] - e[m]), (e[m+2] - f_k) / (e[m+2] - e[m+1]))) * (2 / (e[m+2] - e[m])),
+    f_k = k sample_rate / n_fft - the host-side statement of what the kernels' per-resolution table holds (csrc/stftloss.hip)."""
+    e = mel_edges(sample_rate, n_mels)
+    f = np.arange(int(n_fft) // 2 + 1, dtype=np.float64) * float(sample_rate) / float(n_fft)
+    lo = (f[None, :] - e[:-2, None]) / (e[1:-1] - e[:-2])[:, None]
+    hi = (e[2:, None] - f[None, :]) / (e[2:] - e[1:-1])[:, None]
+    W = (np.maximum(0.0, np.minimum(lo, hi)) * (2.0 / (e[2:] - e[:-2]))[:, None]).astype(np.float32)
+    W.flags.writeable = False
+    return W
+
+
+@functools.lru_cache(maxsize=64)
+def _mel_empty_rows(sample_rate, n_fft, n_mels):
+    return int((~mel_filterbank(sample_rate, n_fft, n_mels).any(axis=1)).sum())
+
+
 _DEFAULTS = {"w_sc": 1.0, "w_log_mag": 1.0, "w_lin_mag": 0.0, "sample_rate": None, "perceptual_weighting": False, "w_phs": 0.0,
              "window": "hann_window", "scale": None, "n_bins": None, "scale_invariance": False, "reduction": "mean", "mag_distance": "L1",
              "output": "loss", "device": None}
@@ -49,7 +96,10 @@ def _options(what, options):
         if name not in _DEFAULTS:
             raise TypeError(f"{what}() got an unexpected keyword argument {name!r}")
     o = dict(_DEFAULTS, **options)
+    mel = o["scale"] == "mel" and o["n_bins"] is not None and o["sample_rate"] is not None          # carried separately: _mel_options
     for name in _NOT_IMPLEMENTED:
+        if mel and name in ("scale", "n_bins"):
+            continue
         v, d = o[name], _DEFAULTS[name]
         if (v is not None) if d is None else (v != d):
             raise NotImplementedError(f"{what}: {name}={v!r} is not implemented (only the default {name}={d!r})")
@@ -63,12 +113,41 @@ def _options(what, options):
     return w + (float(o["sample_rate"]) if o["perceptual_weighting"] else None,)
 
 
+def _mel_options(what, options, fft_sizes):
+    """None, or (n_bins, sample_rate) for scale="mel" with n_bins and sample_rate (anything less raises in _options, as every other
+    unimplemented option does). The same n_bins for every resolution, as in auraloss; 1 <= n_bins <= 256 and n_bins <= n_fft / 2 + 1. A
+    filter narrower than the bin spacing is an all-zero row of the filterbank: its log-magnitude term is log 0 - log 0, so that
+    configuration is refused here unless w_log_mag = 0 (then the row adds 0 to the sums and still counts in the mean)."""
+    if options.get("scale") != "mel" or options.get("n_bins") is None or options.get("sample_rate") is None:
+        return None
+    nb, sr = options["n_bins"], float(options["sample_rate"])
+    try:
+        nb = operator.index(nb)
+    except TypeError:
+        raise NotImplementedError(f"{what}: n_bins={options['n_bins']!r} is not implemented (an integer from 1 to {MEL_MAX_BINS})") from None
+    if not (math.isfinite(sr) and sr > 0):
+        raise ValueError(f"{what}: sample_rate must be positive, got {options['sample_rate']!r}")
+    for n_fft in fft_sizes:
+        if not 1 <= nb <= min(MEL_MAX_BINS, int(n_fft) // 2 + 1):
+            raise NotImplementedError(f"{what}: n_bins={nb} is not implemented for n_fft={n_fft} (1 <= n_bins <= {MEL_MAX_BINS} and "
+                                      "n_bins <= n_fft / 2 + 1)")
+    if float(options.get("w_log_mag", _DEFAULTS["w_log_mag"])) != 0.0:
+        for n_fft in fft_sizes:
+            empty = _mel_empty_rows(sr, int(n_fft), nb)
+            if empty:
+                raise ValueError(f"{what}: at sample_rate={sr:g}, n_fft={n_fft}, {empty} of the {nb} mel filters are narrower than the bin spacing "
+                                 "and empty, so the log-magnitude term is log 0 - log 0 (auraloss returns NaN there); use fewer bins, longer "
+                                 "frames, or w_log_mag=0")
+    return nb, sr
+
+
 class _MRSTFTFunction(torch.autograd.Function):
     """opts: None (the default loss: the unweighted entry points) or (w_sc, w_log_mag, w_lin_mag, sample_rate or None) - the
-    weighted entry points, which also take 8192-point frames, and with a sample rate the A-weighting FIR in front (and its adjoint behind)."""
+    weighted entry points, which also take 8192-point frames, and with a sample rate the A-weighting FIR in front (and its adjoint behind).
+    mel: None or (n_bins, sample_rate) - the mel entry points (scale="mel"), with opts' weights and A-weighting, (1, 1, 0) and none if opts is None."""
 
     @staticmethod
-    def forward(ctx, inp, target, res, eps, opts=None):
+    def forward(ctx, inp, target, res, eps, opts=None, mel=None):
         _lib.require_device(inp, "input")
         _lib.require_device(target, "target")
         _lib.require_same_device(inp, target=target)
@@ -83,13 +162,16 @@ class _MRSTFTFunction(torch.autograd.Function):
         rows = p32.shape[0]
         nres = len(res)
         arr = [(ctypes.c_int * nres)(*[int(r[i]) for r in res]) for i in range(3)]
-        if opts is None and any(int(r[0]) > 4096 for r in res):
+        if opts is None and (mel is not None or any(int(r[0]) > 4096 for r in res)):
             opts = (1.0, 1.0, 0.0, None)                # 8192-point frames: only the weighted entry points take them
         weighted = opts is not None
-        nfl = (L.dasp_mrstft_weighted_partial_floats if weighted else L.dasp_mrstft_partial_floats)(rows, N, nres, *arr)
+        if mel is not None:
+            nfl = L.dasp_mrstft_mel_partial_floats(rows, N, nres, *arr, int(mel[0]))
+        else:
+            nfl = (L.dasp_mrstft_weighted_partial_floats if weighted else L.dasp_mrstft_partial_floats)(rows, N, nres, *arr)
         if nfl < 0:
             raise _lib.DaspHipError(f"unsupported STFT resolutions (fft a power of two in 8..{8192 if weighted else 4096}, win <= fft, "
-                                    "fft / 2 < seq_len, <= 8 of them)")
+                                    "fft / 2 < seq_len, <= 8 of them" + ("" if mel is None else f"; n_bins <= {MEL_MAX_BINS} and <= fft / 2 + 1") + ")")
         dev = inp.device
         with torch.cuda.device(dev):
             tw = _twiddles(dev)
@@ -102,12 +184,19 @@ class _MRSTFTFunction(torch.autograd.Function):
             partials = torch.empty(nfl, dtype=torch.float32, device=dev)
             stats = torch.empty(4 * nres, dtype=torch.float32, device=dev)
             loss = torch.empty((), dtype=torch.float32, device=dev)
-            if weighted:
+            tables = ()
+            if mel is not None:
+                tables = tuple(_mel_table(mel[1], int(r[0]), int(mel[0]), dev) for r in res)
+                tabs = (ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables])
+                call("dasp_mrstft_mel_forward", ptr(p32), ptr(t32), ptr(tw), tabs, ptr(partials), ptr(stats), ptr(loss), rows, N, nres, *arr,
+                     float(eps), *opts[:3], int(mel[0]), stream())
+            elif weighted:
                 call("dasp_mrstft_weighted_forward", ptr(p32), ptr(t32), ptr(tw), ptr(partials), ptr(stats), ptr(loss), rows, N, nres, *arr, float(eps),
                      *opts[:3], stream())
             else:
                 call("dasp_mrstft_forward", ptr(p32), ptr(t32), ptr(tw), ptr(partials), ptr(stats), ptr(loss), rows, N, nres, *arr, float(eps), stream())
-        ctx.save_for_backward(p32, t32, stats, tw, taps)
+        ctx.save_for_backward(p32, t32, stats, tw, taps, *tables)
+        ctx.nbins = None if mel is None else int(mel[0])
         ctx.cfg = (rows, N, nres, arr, float(eps), inp.shape, inp.dtype)
         ctx.opts = opts
         ctx.tdtype = target.dtype
@@ -116,19 +205,23 @@ class _MRSTFTFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gloss):
-        p32, t32, stats, tw, taps = ctx.saved_tensors
+        p32, t32, stats, tw, taps, *tables = ctx.saved_tensors
         rows, N, nres, arr, eps, shape, dtype = ctx.cfg
         opts = ctx.opts
         name, wts = ("dasp_mrstft_weighted_backward", tuple(opts[:3])) if opts is not None else ("dasp_mrstft_backward", ())
+        pre = ()
+        if ctx.nbins is not None:
+            name, wts = "dasp_mrstft_mel_backward", wts + (ctx.nbins,)
+            pre = ((ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables]),)
         g = gt = None
         with torch.cuda.device(p32.device):
             gl = gloss.detach().reshape(1).to(torch.float32).contiguous()
             if ctx.needs_input_grad[0]:
                 g = torch.empty_like(p32)
-                call(name, ptr(p32), ptr(t32), ptr(tw), ptr(stats), ptr(gl), ptr(g), rows, N, nres, *arr, eps, *wts, stream())
+                call(name, ptr(p32), ptr(t32), ptr(tw), *pre, ptr(stats), ptr(gl), ptr(g), rows, N, nres, *arr, eps, *wts, stream())
             if ctx.needs_input_grad[1]:      # auraloss differentiates both arguments (a consistency loss between two model outputs)
                 gt = torch.empty_like(t32)
-                call(name + "_target", ptr(p32), ptr(t32), ptr(tw), ptr(stats), ptr(gl), ptr(gt), rows, N, nres, *arr, eps, *wts, stream())
+                call(name + "_target", ptr(p32), ptr(t32), ptr(tw), *pre, ptr(stats), ptr(gl), ptr(gt), rows, N, nres, *arr, eps, *wts, stream())
             if taps is not None and (g is not None or gt is not None):        # through the A-weighting FIR: its adjoint, one launch for both
                 first, second = (g, gt) if g is not None else (gt, None)
                 o1, o2 = torch.empty_like(first), (torch.empty_like(second) if second is not None else None)
@@ -138,7 +231,7 @@ class _MRSTFTFunction(torch.autograd.Function):
             g = g.reshape(shape).to(dtype)
         if gt is not None:
             gt = gt.reshape(shape).to(ctx.tdtype)
-        return g, gt, None, None, None
+        return g, gt, None, None, None, None
 
 
 _TW = {}
@@ -181,23 +274,53 @@ def _aw_taps(sample_rate, device):
     return taps
 
 
+_MEL_DEV = {}
+
+
+def _mel_table(sample_rate, n_fft, n_bins, device):
+    """One resolution's mel table on the device (per bin: first filter and two weights; per filter: first bin and bin count), one per
+    (sample_rate, n_fft, n_bins, device, stream) under _twiddles' capture rule. A kernel builds it in fp64 from the edge frequencies it
+    gets as arguments (dasp_mel_table_store), so inside a capture it is a kernel node, not a copy from host memory."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    key = (float(sample_rate), int(n_fft), int(n_bins), device.index, int(torch.cuda.current_stream(device).cuda_stream))
+    if not capturing and key in _MEL_DEV:
+        return _MEL_DEV[key]
+    nfl = _lib.lib().dasp_mel_table_floats(int(n_fft), int(n_bins))
+    if nfl < 0:
+        raise _lib.DaspHipError(f"unsupported mel table: n_fft={n_fft}, n_bins={n_bins}")
+    edges = mel_edges(float(sample_rate), int(n_bins))
+    tab = torch.empty(nfl, dtype=torch.float32, device=device)
+    call("dasp_mel_table_store", ptr(tab), edges.ctypes.data_as(ctypes.c_void_p), float(sample_rate), int(n_fft), int(n_bins), stream())
+    if not capturing:
+        if len(_MEL_DEV) >= 64:
+            _MEL_DEV.clear()
+        _MEL_DEV[key] = tab
+    return tab
+
+
 class MultiResolutionSTFTLoss(torch.nn.Module):
     """auraloss.freq.MultiResolutionSTFTLoss (0.4.0). Positional arguments fft_sizes, hop_sizes, win_lengths, eps; keyword-only, with
     auraloss's defaults: w_sc=1.0, w_log_mag=1.0, w_lin_mag=0.0, sample_rate=None, perceptual_weighting=False (True: the A-weighting
-    FIR of auraloss.perceptual in front, needs sample_rate), device=None (ignored: the kernels follow the inputs). w_phs, window, scale,
-    n_bins, scale_invariance, reduction, mag_distance and output are accepted at their defaults only (0.0, "hann_window", None, None,
-    False, "mean", "L1", "loss"); any other value raises NotImplementedError. n_fft: powers of two 8 .. 8192, at most 8 resolutions."""
+    FIR of auraloss.perceptual in front, needs sample_rate), device=None (ignored: the kernels follow the inputs), scale=None, n_bins=None
+    (scale="mel" with an integer n_bins <= 256 and a sample_rate: the terms on mel-scaled magnitudes, librosa's Slaney filterbank with
+    n_bins filters at every resolution; any other scale, "mel" without n_bins or sample_rate, or n_bins without a scale raises
+    NotImplementedError). w_phs, window, scale_invariance, reduction, mag_distance and output are accepted at their defaults only (0.0,
+    "hann_window", False, "mean", "L1", "loss"); any other value raises NotImplementedError. n_fft: powers of two 8 .. 8192, at most 8
+    resolutions."""
 
     def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), eps: float = 1e-8, **options):
         super().__init__()
         if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
             raise ValueError("fft_sizes, hop_sizes and win_lengths must have the same length")
         self._opts = _options(type(self).__name__, options)
+        self._mel = _mel_options(type(self).__name__, options, fft_sizes)
         self.resolutions = tuple(zip(fft_sizes, hop_sizes, win_lengths))
         self.eps = eps
 
     def forward(self, input: torch.Tensor, target: torch.Tensor):
-        return _MRSTFTFunction.apply(input, target, self.resolutions, self.eps, self._opts)
+        if self._mel is None:
+            return _MRSTFTFunction.apply(input, target, self.resolutions, self.eps, self._opts)
+        return _MRSTFTFunction.apply(input, target, self.resolutions, self.eps, self._opts, self._mel)
 
 
 class STFTLoss(MultiResolutionSTFTLoss):
@@ -209,8 +332,20 @@ class STFTLoss(MultiResolutionSTFTLoss):
         super().__init__((fft_size,), (hop_size,), (win_length,), eps, **options)
 
 
+class MelSTFTLoss(STFTLoss):
+    """auraloss.freq.MelSTFTLoss (0.4.0), its signature and defaults: STFTLoss(fft_size, hop_size, win_length, scale="mel", n_bins=n_mels,
+    sample_rate=sample_rate, ...) - one resolution, the three terms on n_mels mel-scaled magnitudes. window and w_phs are accepted at
+    their defaults only; further keywords are those of MultiResolutionSTFTLoss (and eps)."""
+
+    def __init__(self, sample_rate, fft_size: int = 1024, hop_size: int = 256, win_length: int = 1024, window: str = "hann_window",
+                 w_sc: float = 1.0, w_log_mag: float = 1.0, w_lin_mag: float = 0.0, w_phs: float = 0.0, n_mels: int = 128, **kwargs):
+        super().__init__(fft_size, hop_size, win_length, window=window, w_sc=w_sc, w_log_mag=w_log_mag, w_lin_mag=w_lin_mag, w_phs=w_phs,
+                         sample_rate=sample_rate, scale="mel", n_bins=n_mels, **kwargs)
+
+
 def mrstft_loss(input: torch.Tensor, target: torch.Tensor, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240),
                 eps: float = 1e-8, **options):
     """MultiResolutionSTFTLoss(fft_sizes, hop_sizes, win_lengths, eps, **options)(input, target) as a function."""
     opts = _options("mrstft_loss", options)
-    return _MRSTFTFunction.apply(input, target, tuple(zip(fft_sizes, hop_sizes, win_lengths)), eps, opts)
+    mel = _mel_options("mrstft_loss", options, fft_sizes)
+    return _MRSTFTFunction.apply(input, target, tuple(zip(fft_sizes, hop_sizes, win_lengths)), eps, opts, mel)

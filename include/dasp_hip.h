@@ -442,6 +442,29 @@ int dasp_fir_same_forward(const float* x0, const float* x1, float* y0, float* y1
 int dasp_fir_same_adjoint(const float* g0, const float* g1, float* gx0, float* gx1, const float* taps, int ntaps, int rows, int N,
                           void* stream);
 int dasp_fir_taps_store(float* dst, const float* host_taps, int ntaps, void* stream);
+/* The loss on mel-scaled magnitudes (auraloss scale="mel", n_bins; auraloss.freq.MelSTFTLoss): per frame M = W |X| with
+ * W = librosa.filters.mel(sr, n_fft, n_mels) (n_bins x (n_fft / 2 + 1), Slaney scale and normalisation, not clamped after the projection),
+ * the sums and the mean over rows x frames x n_bins. 1 <= n_bins <= 256 and n_bins <= n_fft / 2 + 1 for every resolution; resolutions as
+ * for the weighted entry points (n_fft a power of two in 8..8192); every size query returns -1 otherwise.
+ * One device table per resolution (dasp_mel_table_floats floats): per bin the first filter it lies in and its weights in that filter and
+ * the next, per filter its first bin and bin count. dasp_mel_table_store builds it on the device in fp64 from the n_bins + 2 edge
+ * frequencies in Hz (host fp64, increasing, passed on as kernel arguments: capturable into a graph); dasp_mel_table_dense writes the
+ * (n_bins, n_fft / 2 + 1) float matrix a table stands for. mel_tables: a host array of nres device pointers, table r for fft[r].
+ * The loss value is bit-identical run to run (fixed summation order); the gradients use float atomics as above. */
+long dasp_mel_table_floats(int n_fft, int n_bins);
+int dasp_mel_table_store(float* table, const double* host_edges, double sample_rate, int n_fft, int n_bins, void* stream);
+int dasp_mel_table_dense(const float* table, float* dense, int n_fft, int n_bins, void* stream);
+long dasp_mrstft_mel_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins);
+int dasp_mrstft_mel_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials,
+                            float* stats, float* loss, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
+                            float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
+int dasp_mrstft_mel_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                             const float* gloss, float* gpred, int rows, int N, int nres, const int* fft, const int* hop, const int* win,
+                             float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
+int dasp_mrstft_mel_backward_target(const float* pred, const float* target, const void* tw, const void* const* mel_tables,
+                                    const float* stats, const float* gloss, float* gtarget, int rows, int N, int nres, const int* fft,
+                                    const int* hop, const int* win, float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins,
+                                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Filters longer than one biquad.  Replaces dasp_pytorch.signal.lfilter_via_fsm (dasp_pytorch/signal.py:95-133) for K = 4 .. 16
