@@ -992,3 +992,495 @@ int dasp_mrstft_mel_backward_target(const float* pred, const float* target, cons
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// Sum / difference loss of a stereo pair (auraloss.freq.SumAndDifferenceSTFTLoss): the loss above on s = L + R and on d = L - R, as two
+// separate losses (each with its own sums, spectral-convergence ratio and means over its `items` rows), from one launch per
+// resolution over the (items, 2, N) signals. A workgroup owns a frame group of one batch ITEM - both channels - on the col_fft geometry (every power of two
+// 8 .. 8192; frames of 512 / 1024 / 2048 points run here too, there are no split variants): the frame slots of L and R of both signals are
+// gathered once per half (4 loads per slot each time, the second time from lines the first brought into the cache - sd_gather_half says
+// why not once), (pL + pR) + i (tL + tR) and (pL - pR) + i (tL - tR) are transformed one after the other and reduced to
+// the four sums of their half:  partials[(((half * nres + res) * items + item) * groups + group) * 4 + c], stats[(half * nres + res) * 4 + c],
+// loss[half]; half 0 = sum, 1 = difference. Fixed summation order throughout: the forward is bit-identical run to run.
+// Backward: both halves' one-sided gradient spectra H_s, H_d (grad_consts / grad_bin with the half's own stats and its own element of the
+// two-element gloss) go back to channels in the frequency domain, H_L = H_s + H_d, H_R = H_s - H_d, and through ONE packed inverse
+// transform: with G_X the Hermitian spectrum of the real frame g_X = Re sum_{k <= F/2} H_X[k] e^{+2 pi i k n / F},
+//   G_X[k] = H_X[k] / 2 (0 < k < F/2),  Re H_X[k] (k = 0, F/2),  conj(H_X[F - k]) / 2 (k > F/2),
+// Z = G_L + i G_R gives Re IFFT(Z) = g_L and Im IFFT(Z) = g_R: three transforms per item and frame group where two calls of the mono loss
+// run four, and one float atomic per sample, frame and channel. After frames_to_spectra's exchange a thread holds Z[k] AND Z[F - k] for
+// each of its slots k = j + T q over the whole range 0 .. F - 1, so the thread that owns an upper slot k > F/2 forms bin F - k itself from the
+// swapped pair: no further exchange; the price is grad_bin on F instead of F/2 + 1 bins.
+namespace dasp {
+
+// One half only (DIFF: L - R, else L + R); every kernel gathers twice, once per half. Gathering both halves at once (4 loads per slot in
+// all) holds the second half's 16 registers through the first half's transform: 128 .. 145 VGPRs, scratch spills in the 8192-point
+// instances and one 512-thread workgroup per CU where the mono kernels run three - measured at twice the mono kernels' time per transform.
+// The second gather reads lines the first one brought in.
+template <bool DIFF>
+__device__ __forceinline__ void sd_gather_half(const float* __restrict__ aL, const float* __restrict__ aR, const float* __restrict__ bL,
+                                               const float* __restrict__ bR, int N, int frame, bool live, const StftRes& R, const ColCfg& g,
+                                               const float* wlds, float (&r)[8], float (&i)[8]) {
+    const int F = 1 << R.logF;
+    float ar[8], br[8];
+    int s[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        s[q] = reflect_index(frame * R.hop - F / 2 + g.j + g.T * q, N);
+        s[q] = s[q] < 0 ? 0 : (s[q] >= N ? N - 1 : s[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { r[q] = aL[s[q]]; ar[q] = aR[s[q]]; }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { i[q] = bL[s[q]]; br[q] = bR[s[q]]; }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const float w = live ? wlds[g.j + g.T * q] : 0.f;
+        r[q] = w * (DIFF ? r[q] - ar[q] : r[q] + ar[q]);
+        i[q] = w * (DIFF ? i[q] - br[q] : i[q] + br[q]);
+    }
+}
+// The thread's coordinates for the next phase of a kernel (second half, inverse transform), behind an empty dependency on two results (a, b)
+// of the phase before: the copy of (j, c) and of the frame index is opaque to the compiler, so the next phase's loads cannot be hoisted
+// above the phase before, and its twiddles, LDS addresses and sample indices - common subexpressions of the earlier phase's - are formed
+// again instead of being held in registers across both (that alone is 20 .. 30 VGPRs, the difference between two and three workgroups per
+// CU). No instruction is emitted. tests/test_sumdiff_stft_cpu.py holds the built kernels to their register counts and to zero scratch.
+__device__ __forceinline__ ColCfg sd_next_phase(const ColCfg& g, int& frame, float a, float b) {
+    ColCfg o = g;
+    asm volatile("" : "+v"(frame), "+v"(o.j), "+v"(o.c) : "v"(a), "v"(b));
+    return o;
+}
+// frames_to_spectra behind its gather: r/i <- Z[j + T q], mr/mi <- Z[F - (j + T q)]
+template <int LOGN>
+__device__ __forceinline__ void regs_to_spectra(const StftRes& R, const ColCfg& g, const f2* __restrict__ tw, f2* lds, float (&r)[8], float (&i)[8],
+                                                float (&mr)[8], float (&mi)[8]) {
+    const int F = 1 << R.logF;
+    col_fft<-1, LOGN>(r, i, g, tw, lds);
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) lds[fft_pad(g.j + g.T * q) * g.TC + g.c] = f2{r[q], i[q]};
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const f2 m = lds[fft_pad((F - (g.j + g.T * q)) & (F - 1)) * g.TC + g.c];
+        mr[q] = m.x; mi[q] = m.y;
+    }
+    __syncthreads();
+}
+// the eight sums of a workgroup (4 per half) -> its partials
+template <int NW>
+__device__ __forceinline__ void sd_write_partials(float (&s)[8], float (*red)[8], float* __restrict__ partials, const StftSpec& spec, int res) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) s[c] = wave_sum_uniform(s[c]);
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) red[wave_id()][c] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        float a = 0.f;
+        for (int v = 0; v < NW; ++v) a += red[v][threadIdx.x];
+        const int half = threadIdx.x >> 2, c = threadIdx.x & 3;
+        partials[((((size_t)half * spec.nres + res) * gridDim.y + blockIdx.y) * spec.groups + blockIdx.x) * 4 + c] = a;
+    }
+}
+
+template <int LOGN>
+__global__ void __launch_bounds__(ColGeom<LOGN>::T, LOGN == 13 ? 4 : 6)
+mrstft_sd_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, const f2* __restrict__ tw, float* __restrict__ partials,
+                     StftSpec spec, int N, int res) {
+    constexpr int NT = ColGeom<LOGN>::T, NW = NT / 64;
+    __shared__ f2 lds[ColGeom<LOGN>::LDS];
+    __shared__ float wlds[1 << LOGN];
+    __shared__ float red[NW][8];
+    StftRes R = spec.r[res];
+    if constexpr (LOGN == 13) R.logF = 13;
+    const ColCfg g = col_config<LOGN>(R.logF, threadIdx.x);
+    const int item = blockIdx.y, F = 1 << R.logF;
+    if ((int)blockIdx.x * g.TC >= R.frames) return;
+    const int frame = blockIdx.x * g.TC + g.c;
+    const bool live = frame < R.frames;
+    window_to_lds<NT>(wlds, R);
+    const float* pL = pred + (size_t)(2 * item) * N;
+    const float* tL = target + (size_t)(2 * item) * N;
+    float r[8], i[8], mr[8], mi[8];
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    sd_gather_half<false>(pL, pL + N, tL, tL + N, N, frame, live, R, g, wlds, r, i);
+    regs_to_spectra<LOGN>(R, g, tw, lds, r, i, mr, mi);
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+        if (live && g.j + g.T * q <= F / 2) loss_terms(split_bin(r[q], i[q], mr[q], mi[q]), spec.eps, s[0], s[1], s[2], s[3]);
+    int frame2 = frame;
+    const ColCfg g2 = sd_next_phase(g, frame2, s[0], s[2]);
+    sd_gather_half<true>(pL, pL + N, tL, tL + N, N, frame2, live, R, g2, wlds, r, i);
+    regs_to_spectra<LOGN>(R, g2, tw, lds, r, i, mr, mi);
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+        if (live && g2.j + g2.T * q <= F / 2) loss_terms(split_bin(r[q], i[q], mr[q], mi[q]), spec.eps, s[4], s[5], s[6], s[7]);
+    sd_write_partials<NW>(s, red, partials, spec, res);
+}
+// mrstft_reduce_kernel over 2 nres (half, resolution) pairs: one workgroup per (half, resolution, sum), fp64, fixed order
+__global__ void __launch_bounds__(1024)
+mrstft_sd_reduce_kernel(const float* __restrict__ partials, StftSpec spec, int items, float* __restrict__ stats) {
+    __shared__ double red[16];
+    const int hr = blockIdx.x / 4, c = blockIdx.x % 4, res = hr % spec.nres, l = lane_id(), wv = wave_id();
+    const int TC = frames_per_group(spec.r[res].logF), ng = (spec.r[res].frames + TC - 1) / TC;
+    double s = 0.0;
+    for (int row = wv; row < items; row += 16) {
+        const float* p = partials + ((size_t)hr * items + row) * spec.groups * 4 + c;
+        for (int g0 = l; g0 < ng; g0 += 256) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { const int gi = g0 + 64 * u; v[u] = p[(size_t)(gi < ng ? gi : ng - 1) * 4]; }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s += g0 + 64 * u < ng ? (double)v[u] : 0.0;
+        }
+    }
+    s = wave_sum(s);
+    if (l == 0) red[wv] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int v = 0; v < 16; ++v) t += red[v];
+        stats[hr * 4 + c] = (float)t;
+    }
+}
+// thread `half` finalizes its half as mrstft_finalize_kernel does: stats[(half nres + res) 4 ..] = (sqrt S1, sqrt S2, count, S3), loss[half];
+// count = items x frames x (n_fft / 2 + 1), or items x frames x n_bins on mel-scaled magnitudes (nbins > 0)
+__global__ void mrstft_sd_finalize_kernel(StftSpec spec, int items, int nbins, float* __restrict__ stats, float* __restrict__ loss) {
+    if (threadIdx.x >= 2) return;
+    const int half = threadIdx.x;
+    float* st = stats + half * spec.nres * 4;
+    double total = 0.0;
+    for (int res = 0; res < spec.nres; ++res) {
+        const double F = (double)(1 << spec.r[res].logF);
+        const double count = (double)items * spec.r[res].frames * (nbins > 0 ? (double)nbins : F / 2 + 1);
+        const double s1 = sqrt((double)st[res * 4 + 0]), s2 = sqrt((double)st[res * 4 + 1]), s3 = (double)st[res * 4 + 2];
+        const double s4 = (double)st[res * 4 + 3];
+        st[res * 4 + 0] = (float)s1; st[res * 4 + 1] = (float)s2; st[res * 4 + 2] = (float)count; st[res * 4 + 3] = (float)s3;
+        double l = 0.0;
+        if (spec.w_sc != 0.f) l += (double)spec.w_sc * (s1 / s2);
+        if (spec.w_lm != 0.f) l += (double)spec.w_lm * (s3 / count);
+        if (spec.w_lin != 0.f) l += (double)spec.w_lin * (s4 / count);
+        total += l;
+    }
+    loss[half] = (float)(total / spec.nres);
+}
+
+// slot k of the Hermitian spectrum G from the one-sided gradient bin H of bin k (k <= F/2) or F - k (k > F/2)
+__device__ __forceinline__ void sd_hermitian_slot(int k, int F, float hr, float hi, float& gr, float& gi) {
+    const bool edge = k == 0 || k == F / 2;
+    gr = edge ? hr : 0.5f * hr;
+    gi = edge ? 0.f : (k > F / 2 ? -0.5f * hi : 0.5f * hi);
+}
+// r/i (Z[k]), mr/mi (Z[F - k]) of one half -> r/i = G[k] of that half's gradient frame
+template <bool LIN>
+__device__ __forceinline__ void sd_grad_spectrum(const ColCfg& g, int F, bool live, float eps, const GradK& kk, float (&r)[8], float (&i)[8],
+                                                 const float (&mr)[8], const float (&mi)[8]) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int k = g.j + g.T * q;
+        const Bin b = k > F / 2 ? split_bin(mr[q], mi[q], r[q], i[q]) : split_bin(r[q], i[q], mr[q], mi[q]);
+        float hr = 0.f, hi = 0.f;
+        if (live) grad_bin<LIN>(b, eps, kk, hr, hi);
+        sd_hermitian_slot(k, F, hr, hi, r[q], i[q]);
+    }
+}
+// Z = G_L + i G_R from the two halves' G (G_L = G_s + G_d, G_R = G_s - G_d), the packed inverse transform, and the two scatters
+template <int LOGN>
+__device__ __forceinline__ void sd_inverse_and_scatter(float (&r)[8], float (&i)[8], const float (&dr)[8], const float (&di)[8], const StftRes& R,
+                                                       const ColCfg& g, const f2* __restrict__ tw, f2* lds, int frame, bool live, int N,
+                                                       float* __restrict__ gL, float* __restrict__ gR) {
+    const int F = 1 << R.logF;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const float lr = r[q] + dr[q], li = i[q] + di[q], rr = r[q] - dr[q], ri = i[q] - di[q];
+        r[q] = lr - ri; i[q] = li + rr;
+    }
+    col_fft<1, LOGN>(r, i, g, tw, lds);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int n = g.j + g.T * q;
+        const float w = hann_in_frame(n, F, R.win);
+        if (live && w != 0.f) {
+            const int s = reflect_index(frame * R.hop - F / 2 + n, N);
+            atomicAdd(gL + s, w * r[q]);
+            atomicAdd(gR + s, w * i[q]);
+        }
+    }
+}
+
+// gfirst (2 items, N) must be zero on entry; gloss: two device floats, d(objective)/d(sum_loss) and d(objective)/d(diff_loss)
+template <int LOGN, bool LIN>
+__global__ void __launch_bounds__(ColGeom<LOGN>::T)
+mrstft_sd_bwd_kernel(const float* __restrict__ first, const float* __restrict__ second, const f2* __restrict__ tw, const float* __restrict__ stats,
+                     const float* __restrict__ gloss, float* __restrict__ gfirst, StftSpec spec, int N, int res, int wrt_second) {
+    __shared__ f2 lds[ColGeom<LOGN>::LDS];
+    __shared__ float wlds[1 << LOGN];
+    StftRes R = spec.r[res];
+    if constexpr (LOGN == 13) R.logF = 13;
+    const ColCfg g = col_config<LOGN>(R.logF, threadIdx.x);
+    const int item = blockIdx.y, F = 1 << R.logF;
+    if ((int)blockIdx.x * g.TC >= R.frames) return;
+    const int frame = blockIdx.x * g.TC + g.c;
+    const bool live = frame < R.frames;
+    window_to_lds<ColGeom<LOGN>::T>(wlds, R);
+    const float* aL = first + (size_t)(2 * item) * N;
+    const float* bL = second + (size_t)(2 * item) * N;
+    float r[8], i[8], dr[8], di[8], mr[8], mi[8];
+    sd_gather_half<false>(aL, aL + N, bL, bL + N, N, frame, live, R, g, wlds, r, i);
+    regs_to_spectra<LOGN>(R, g, tw, lds, r, i, mr, mi);
+    sd_grad_spectrum<LIN>(g, F, live, spec.eps, grad_consts(spec, stats, gloss, res, wrt_second), r, i, mr, mi);
+    int frame2 = frame;
+    const ColCfg g2 = sd_next_phase(g, frame2, r[0], i[0]);
+    sd_gather_half<true>(aL, aL + N, bL, bL + N, N, frame2, live, R, g2, wlds, dr, di);
+    regs_to_spectra<LOGN>(R, g2, tw, lds, dr, di, mr, mi);
+    sd_grad_spectrum<LIN>(g2, F, live, spec.eps, grad_consts(spec, stats + 4 * spec.nres, gloss + 1, res, wrt_second), dr, di, mr, mi);
+    const ColCfg g3 = sd_next_phase(g, frame2, dr[0], di[0]);
+    float* gL = gfirst + (size_t)(2 * item) * N;
+    sd_inverse_and_scatter<LOGN>(r, i, dr, di, R, g3, tw, lds, frame2, live, N, gL, gL + N);
+}
+
+// ---- mel-scaled magnitudes: mrstft_mel_fwd_kernel / mrstft_mel_bwd_kernel's steps once per half, on the same per-resolution tables ----
+template <int LOGN>
+__device__ __forceinline__ void sd_mel_half_sums(float* mag, const ColCfg& g, const StftRes& R, const StftSpec& spec, const MelTab& t, int live_cols,
+                                                 const float (&r)[8], const float (&i)[8], const float (&mr)[8], const float (&mi)[8],
+                                                 float& s1, float& s2, float& s3, float& s4) {
+    const int F = 1 << R.logF;
+    mel_magnitudes_to_lds<LOGN>(mag, g, F, spec.eps, r, i, mr, mi);
+    const bool with_log = spec.w_lm != 0.f;
+    mel_filter_sums<ColGeom<LOGN>::T>(mag, F / 2 + 1, g.TC, LOGN - R.logF, t, [&](bool owner, int, int c, float mp, float mt) {
+        if (owner && c < live_cols) {
+            const float d = mt - mp;
+            s1 = fmaf(d, d, s1);
+            s2 = fmaf(mt, mt, s2);
+            if (with_log) s3 += fabsf(logf(mp / mt));
+            s4 += fabsf(d);
+        }
+    });
+    __syncthreads();             // the magnitudes are read: the buffer goes back to the next transform
+}
+
+template <int LOGN>
+__global__ void __launch_bounds__(ColGeom<LOGN>::T, LOGN == 13 ? 4 : 6)
+mrstft_sd_mel_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, const f2* __restrict__ tw, const float* __restrict__ tab,
+                         float* __restrict__ partials, StftSpec spec, int N, int res, int nbins) {
+    constexpr int NT = ColGeom<LOGN>::T, NW = NT / 64;
+    __shared__ f2 lds[ColGeom<LOGN>::LDS];
+    __shared__ float wlds[1 << LOGN];
+    __shared__ float red[NW][8];
+    StftRes R = spec.r[res];
+    if constexpr (LOGN == 13) R.logF = 13;
+    const ColCfg g = col_config<LOGN>(R.logF, threadIdx.x);
+    const int item = blockIdx.y, F = 1 << R.logF;
+    if ((int)blockIdx.x * g.TC >= R.frames) return;
+    const int frame = blockIdx.x * g.TC + g.c;
+    const bool live = frame < R.frames;
+    window_to_lds<NT>(wlds, R);
+    const float* pL = pred + (size_t)(2 * item) * N;
+    const float* tL = target + (size_t)(2 * item) * N;
+    float r[8], i[8], mr[8], mi[8];
+    float* mag = reinterpret_cast<float*>(lds);
+    const MelTab t = mel_tab(tab, F, nbins);
+    const int live_cols = R.frames - (int)blockIdx.x * g.TC;
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    sd_gather_half<false>(pL, pL + N, tL, tL + N, N, frame, live, R, g, wlds, r, i);
+    regs_to_spectra<LOGN>(R, g, tw, lds, r, i, mr, mi);
+    sd_mel_half_sums<LOGN>(mag, g, R, spec, t, live_cols, r, i, mr, mi, s[0], s[1], s[2], s[3]);
+    int frame2 = frame;
+    const ColCfg g2 = sd_next_phase(g, frame2, s[0], s[2]);
+    sd_gather_half<true>(pL, pL + N, tL, tL + N, N, frame2, live, R, g2, wlds, r, i);
+    regs_to_spectra<LOGN>(R, g2, tw, lds, r, i, mr, mi);
+    sd_mel_half_sums<LOGN>(mag, g2, R, spec, t, live_cols, r, i, mr, mi, s[4], s[5], s[6], s[7]);
+    sd_write_partials<NW>(s, red, partials, spec, res);
+}
+
+// one half: magnitudes and dL/dM_P to LDS (mrstft_mel_bwd_kernel), then r/i = G[k]: every slot gathers dL/d|P| of its bin (k, or F - k for
+// an upper slot) from that bin's at most two filters
+template <int LOGN, bool LIN>
+__device__ __forceinline__ void sd_mel_grad_spectrum(float* mag, const ColCfg& g, const StftRes& R, const StftSpec& spec, const MelTab& t,
+                                                     const GradK& kk, bool live, float (&r)[8], float (&i)[8], const float (&mr)[8],
+                                                     const float (&mi)[8]) {
+    const int F = 1 << R.logF, K = F / 2 + 1, TC = g.TC;
+    float* dm = mag + 2 * K * TC;
+    mel_magnitudes_to_lds<LOGN>(mag, g, F, spec.eps, r, i, mr, mi);
+    mel_filter_sums<ColGeom<LOGN>::T>(mag, K, TC, LOGN - R.logF, t, [&](bool owner, int m, int c, float mp, float mt) {
+        if (owner) {
+            const float sgn = mt > mp ? 1.f : (mt < mp ? -1.f : 0.f);
+            float d = kk.sc * (mp - mt) + kk.self * mp;
+            if (mp > 0.f) d -= kk.lm * sgn / mp;
+            if constexpr (LIN) d -= kk.lin * sgn;
+            dm[m * TC + c] = d;
+        }
+    });
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int k = g.j + g.T * q, kb = k > F / 2 ? F - k : k;
+        const Bin b = k > F / 2 ? split_bin(mr[q], mi[q], r[q], i[q]) : split_bin(r[q], i[q], mr[q], mi[q]);
+        float hr = 0.f, hi = 0.f;
+        const float praw = b.pr * b.pr + b.pi * b.pi;
+        if (live && praw > spec.eps) {
+            const f2 w = t.w[kb];
+            const int ma = t.m0[kb], mb = ma + 1 < t.B ? ma + 1 : ma;
+            const float gm = (w.x * dm[ma * TC + g.c] + w.y * dm[mb * TC + g.c]) / sqrtf(praw);
+            hr = gm * b.pr; hi = gm * b.pi;
+        }
+        sd_hermitian_slot(k, F, hr, hi, r[q], i[q]);
+    }
+    __syncthreads();             // dm is read: the buffer goes back to the next transform
+}
+
+template <int LOGN, bool LIN>
+__global__ void __launch_bounds__(ColGeom<LOGN>::T)
+mrstft_sd_mel_bwd_kernel(const float* __restrict__ first, const float* __restrict__ second, const f2* __restrict__ tw, const float* __restrict__ tab,
+                         const float* __restrict__ stats, const float* __restrict__ gloss, float* __restrict__ gfirst, StftSpec spec, int N, int res,
+                         int nbins, int wrt_second) {
+    __shared__ f2 lds[ColGeom<LOGN>::LDS];
+    __shared__ float wlds[1 << LOGN];
+    StftRes R = spec.r[res];
+    if constexpr (LOGN == 13) R.logF = 13;
+    const ColCfg g = col_config<LOGN>(R.logF, threadIdx.x);
+    const int item = blockIdx.y, F = 1 << R.logF;
+    if ((int)blockIdx.x * g.TC >= R.frames) return;
+    const int frame = blockIdx.x * g.TC + g.c;
+    const bool live = frame < R.frames;
+    window_to_lds<ColGeom<LOGN>::T>(wlds, R);
+    const float* aL = first + (size_t)(2 * item) * N;
+    const float* bL = second + (size_t)(2 * item) * N;
+    float r[8], i[8], dr[8], di[8], mr[8], mi[8];
+    sd_gather_half<false>(aL, aL + N, bL, bL + N, N, frame, live, R, g, wlds, r, i);
+    float* mag = reinterpret_cast<float*>(lds);
+    const MelTab t = mel_tab(tab, F, nbins);
+    regs_to_spectra<LOGN>(R, g, tw, lds, r, i, mr, mi);
+    sd_mel_grad_spectrum<LOGN, LIN>(mag, g, R, spec, t, grad_consts(spec, stats, gloss, res, wrt_second), live, r, i, mr, mi);
+    int frame2 = frame;
+    const ColCfg g2 = sd_next_phase(g, frame2, r[0], i[0]);
+    sd_gather_half<true>(aL, aL + N, bL, bL + N, N, frame2, live, R, g2, wlds, dr, di);
+    regs_to_spectra<LOGN>(R, g2, tw, lds, dr, di, mr, mi);
+    sd_mel_grad_spectrum<LOGN, LIN>(mag, g2, R, spec, t, grad_consts(spec, stats + 4 * spec.nres, gloss + 1, res, wrt_second), live, dr, di, mr, mi);
+    const ColCfg g3 = sd_next_phase(g, frame2, dr[0], di[0]);
+    float* gL = gfirst + (size_t)(2 * item) * N;
+    sd_inverse_and_scatter<LOGN>(r, i, dr, di, R, g3, tw, lds, frame2, live, N, gL, gL + N);
+}
+}  // namespace dasp
+
+namespace {
+// tab: one resolution's mel table, or null for the plain loss
+template <bool LIN>
+void mrstft_sd_bwd_launch(const float* first, const float* second, const void* tw, const float* tab, const float* stats, const float* gloss,
+                          float* gfirst, const StftSpec& s, int items, int N, int r, int n_bins, int wrt_second, hipStream_t st) {
+    const int TC = frames_per_group(s.r[r].logF);
+    const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)items);
+    const bool big = s.r[r].logF == 13;
+    if (tab) {
+        if (big) hipLaunchKernelGGL((mrstft_sd_mel_bwd_kernel<13, LIN>), grid, dim3(1024), 0, st, first, second, (const f2*)tw, tab, stats, gloss, gfirst, s, N, r, n_bins, wrt_second);
+        else hipLaunchKernelGGL((mrstft_sd_mel_bwd_kernel<12, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, tab, stats, gloss, gfirst, s, N, r, n_bins, wrt_second);
+    } else {
+        if (big) hipLaunchKernelGGL((mrstft_sd_bwd_kernel<13, LIN>), grid, dim3(1024), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second);
+        else hipLaunchKernelGGL((mrstft_sd_bwd_kernel<12, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second);
+    }
+}
+// mel_tables null: the plain loss (n_bins ignored)
+bool sd_spec(int N, int nres, const int* fft, const int* hop, const int* win, float eps, const void* const* mel_tables, int n_bins, StftSpec* s,
+             float w_sc = 1.f, float w_lm = 1.f, float w_lin = 0.f) {
+    return mel_tables ? mel_spec(N, nres, fft, hop, win, eps, n_bins, s, w_sc, w_lm, w_lin) : sl_spec(N, nres, fft, hop, win, eps, s, 13, w_sc, w_lm, w_lin);
+}
+int sd_forward_impl(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials, float* stats, float* loss,
+                    int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_lm, float w_lin,
+                    int n_bins, void* stream) {
+    if (!pred || !target || !tw || !partials || !stats || !loss || items <= 0 || N <= 0) return DASP_ERR_ARG;
+    StftSpec s;
+    if (!sd_spec(N, nres, fft, hop, win, eps, mel_tables, n_bins, &s, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
+    if (items > 65535) return DASP_ERR_UNSUPPORTED;
+    for (int r = 0; mel_tables && r < nres; ++r)
+        if (!mel_tables[r]) return DASP_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    for (int r = 0; r < nres; ++r) {
+        const int TC = frames_per_group(s.r[r].logF);
+        const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)items);
+        const bool big = s.r[r].logF == 13;
+        if (mel_tables) {
+            const float* tab = (const float*)mel_tables[r];
+            if (big) hipLaunchKernelGGL(mrstft_sd_mel_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
+            else hipLaunchKernelGGL(mrstft_sd_mel_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
+        } else {
+            if (big) hipLaunchKernelGGL(mrstft_sd_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
+            else hipLaunchKernelGGL(mrstft_sd_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
+        }
+    }
+    hipLaunchKernelGGL(mrstft_sd_reduce_kernel, dim3((unsigned)(nres * 8)), dim3(1024), 0, st, (const float*)partials, s, items, stats);
+    hipLaunchKernelGGL(mrstft_sd_finalize_kernel, dim3(1), dim3(64), 0, st, s, items, mel_tables ? n_bins : 0, stats, loss);
+    return sl_check();
+}
+int sd_backward_impl(const float* first, const float* second, const void* tw, const void* const* mel_tables, const float* stats, const float* gloss,
+                     float* gfirst, int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_lm,
+                     float w_lin, int n_bins, int wrt_second, void* stream) {
+    if (!first || !second || !tw || !stats || !gloss || !gfirst || items <= 0 || N <= 0) return DASP_ERR_ARG;
+    StftSpec s;
+    if (!sd_spec(N, nres, fft, hop, win, eps, mel_tables, n_bins, &s, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
+    if (items > 65535) return DASP_ERR_UNSUPPORTED;
+    for (int r = 0; mel_tables && r < nres; ++r)
+        if (!mel_tables[r]) return DASP_ERR_ARG;
+    if (zero_async(gfirst, (size_t)2 * items * N * sizeof(float), (hipStream_t)stream) != hipSuccess) return sl_check();
+    for (int r = 0; r < nres; ++r) {
+        const float* tab = mel_tables ? (const float*)mel_tables[r] : nullptr;
+        if (s.w_lin != 0.f) mrstft_sd_bwd_launch<true>(first, second, tw, tab, stats, gloss, gfirst, s, items, N, r, n_bins, wrt_second, (hipStream_t)stream);
+        else mrstft_sd_bwd_launch<false>(first, second, tw, tab, stats, gloss, gfirst, s, items, N, r, n_bins, wrt_second, (hipStream_t)stream);
+    }
+    return sl_check();
+}
+}  // namespace
+
+extern "C" {
+
+/* floats of `partials` for items stereo pairs of N samples: 2 halves x nres x items x groups x 4; -1 as dasp_mrstft_weighted_partial_floats */
+long dasp_mrstft_sd_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win) {
+    StftSpec s;
+    if (items <= 0 || !sl_spec(N, nres, fft, hop, win, 0.f, &s, 13)) return -1;
+    return 2L * nres * items * s.groups * 4;
+}
+long dasp_mrstft_sd_mel_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins) {
+    StftSpec s;
+    if (items <= 0 || !mel_spec(N, nres, fft, hop, win, 0.f, n_bins, &s)) return -1;
+    return 2L * nres * items * s.groups * 4;
+}
+/* pred, target (items, 2, N); stats: 8 * nres floats (kept for the backward); loss: 2 floats (sum_loss, diff_loss) */
+int dasp_mrstft_sd_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int items, int N,
+                           int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_log_mag, float w_lin_mag,
+                           void* stream) {
+    return sd_forward_impl(pred, target, tw, nullptr, partials, stats, loss, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, 0, stream);
+}
+/* gpred (items, 2, N) is overwritten with gloss[0] d sum_loss / d pred + gloss[1] d diff_loss / d pred (gloss: two device floats) */
+int dasp_mrstft_sd_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gpred, int items,
+                            int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_log_mag,
+                            float w_lin_mag, void* stream) {
+    return sd_backward_impl(pred, target, tw, nullptr, stats, gloss, gpred, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, 0, 0, stream);
+}
+int dasp_mrstft_sd_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gtarget,
+                                   int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
+                                   float w_log_mag, float w_lin_mag, void* stream) {
+    return sd_backward_impl(target, pred, tw, nullptr, stats, gloss, gtarget, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, 0, 1, stream);
+}
+int dasp_mrstft_sd_mel_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials, float* stats,
+                               float* loss, int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
+                               float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
+    if (!mel_tables) return DASP_ERR_ARG;
+    return sd_forward_impl(pred, target, tw, mel_tables, partials, stats, loss, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins,
+                           stream);
+}
+int dasp_mrstft_sd_mel_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                                const float* gloss, float* gpred, int items, int N, int nres, const int* fft, const int* hop, const int* win,
+                                float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
+    if (!mel_tables) return DASP_ERR_ARG;
+    return sd_backward_impl(pred, target, tw, mel_tables, stats, gloss, gpred, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins, 0,
+                            stream);
+}
+int dasp_mrstft_sd_mel_backward_target(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                                       const float* gloss, float* gtarget, int items, int N, int nres, const int* fft, const int* hop, const int* win,
+                                       float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
+    if (!mel_tables) return DASP_ERR_ARG;
+    return sd_backward_impl(target, pred, tw, mel_tables, stats, gloss, gtarget, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins, 1,
+                            stream);
+}
+
+}  // extern "C"

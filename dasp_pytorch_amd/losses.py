@@ -4,7 +4,8 @@ Same defaults and call convention as auraloss 0.4.0: `loss_fn(input, target)` wi
 w_sc * spectral convergence + w_log_mag * log-magnitude L1 + w_lin_mag * linear-magnitude L1, mean over the resolutions; with
 perceptual_weighting=True both signals first go through auraloss's 101-tap A-weighting FIR; with scale="mel", n_bins and sample_rate
 the three terms are taken on mel-scaled magnitudes W |X| (librosa's Slaney filterbank, mel_filterbank below), which is also what
-MelSTFTLoss computes. Both arguments receive gradients."""
+MelSTFTLoss computes. SumAndDifferenceSTFTLoss is that loss on the sum and on the difference of a stereo pair, from kernels whose workgroups own
+both channels of an item. Both arguments receive gradients."""
 import ctypes
 import functools
 import math
@@ -234,6 +235,91 @@ class _MRSTFTFunction(torch.autograd.Function):
         return g, gt, None, None, None, None
 
 
+class _SumDiffFunction(torch.autograd.Function):
+    """(sum_loss, diff_loss) of (bs, 2, N) signals from the item-owned kernels (dasp_mrstft_sd_*): opts and mel as _MRSTFTFunction's. The
+    backward hands the kernels the two upstream gradients as a two-element gloss, so either output may be differentiated alone."""
+
+    @staticmethod
+    def forward(ctx, inp, target, res, eps, opts=None, mel=None):
+        _lib.require_device(inp, "input")
+        _lib.require_device(target, "target")
+        _lib.require_same_device(inp, target=target)
+        from .ops64 import require_fp32_ok
+        require_fp32_ok(inp, "SumAndDifferenceSTFTLoss")
+        L = _lib.lib()
+        bs, _, N = inp.shape
+        p32 = inp.detach().reshape(2 * bs, N).to(torch.float32).contiguous()
+        t32 = target.detach().reshape(2 * bs, N).to(torch.float32).contiguous()
+        nres = len(res)
+        arr = [(ctypes.c_int * nres)(*[int(r[i]) for r in res]) for i in range(3)]
+        if opts is None:
+            opts = (1.0, 1.0, 0.0, None)
+        if mel is not None:
+            nfl = L.dasp_mrstft_sd_mel_partial_floats(bs, N, nres, *arr, int(mel[0]))
+        else:
+            nfl = L.dasp_mrstft_sd_partial_floats(bs, N, nres, *arr)
+        if nfl < 0:
+            raise _lib.DaspHipError("unsupported STFT resolutions (fft a power of two in 8..8192, win <= fft, fft / 2 < seq_len, <= 8 of them"
+                                    + ("" if mel is None else f"; n_bins <= {MEL_MAX_BINS} and <= fft / 2 + 1") + ")")
+        dev = inp.device
+        with torch.cuda.device(dev):
+            tw = _twiddles(dev)
+            taps = None
+            if opts[3] is not None:                      # the FIR is linear: per channel here, the sum and difference are formed behind it
+                taps = _aw_taps(opts[3], dev)
+                pf, tf = torch.empty_like(p32), torch.empty_like(t32)
+                call("dasp_fir_same_forward", ptr(p32), ptr(t32), ptr(pf), ptr(tf), ptr(taps), AW_TAPS, 2 * bs, N, stream())
+                p32, t32 = pf, tf
+            partials = torch.empty(nfl, dtype=torch.float32, device=dev)
+            stats = torch.empty(8 * nres, dtype=torch.float32, device=dev)
+            losses = torch.empty(2, dtype=torch.float32, device=dev)
+            tables = ()
+            if mel is not None:
+                tables = tuple(_mel_table(mel[1], int(r[0]), int(mel[0]), dev) for r in res)
+                tabs = (ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables])
+                call("dasp_mrstft_sd_mel_forward", ptr(p32), ptr(t32), ptr(tw), tabs, ptr(partials), ptr(stats), ptr(losses), bs, N, nres, *arr,
+                     float(eps), *opts[:3], int(mel[0]), stream())
+            else:
+                call("dasp_mrstft_sd_forward", ptr(p32), ptr(t32), ptr(tw), ptr(partials), ptr(stats), ptr(losses), bs, N, nres, *arr, float(eps),
+                     *opts[:3], stream())
+        ctx.save_for_backward(p32, t32, stats, tw, taps, *tables)
+        ctx.nbins = None if mel is None else int(mel[0])
+        ctx.cfg = (bs, N, nres, arr, float(eps), inp.shape, inp.dtype)
+        ctx.wts = tuple(opts[:3])
+        ctx.tdtype = target.dtype
+        out = losses.to(inp.dtype)
+        return out[0], out[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gsum, gdiff):
+        p32, t32, stats, tw, taps, *tables = ctx.saved_tensors
+        bs, N, nres, arr, eps, shape, dtype = ctx.cfg
+        name, wts, pre = "dasp_mrstft_sd_backward", ctx.wts, ()
+        if ctx.nbins is not None:
+            name, wts = "dasp_mrstft_sd_mel_backward", wts + (ctx.nbins,)
+            pre = ((ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables]),)
+        g = gt = None
+        with torch.cuda.device(p32.device):
+            gl = torch.stack((gsum.detach().reshape(()), gdiff.detach().reshape(()))).to(torch.float32).contiguous()
+            if ctx.needs_input_grad[0]:
+                g = torch.empty_like(p32)
+                call(name, ptr(p32), ptr(t32), ptr(tw), *pre, ptr(stats), ptr(gl), ptr(g), bs, N, nres, *arr, eps, *wts, stream())
+            if ctx.needs_input_grad[1]:
+                gt = torch.empty_like(t32)
+                call(name + "_target", ptr(p32), ptr(t32), ptr(tw), *pre, ptr(stats), ptr(gl), ptr(gt), bs, N, nres, *arr, eps, *wts, stream())
+            if taps is not None and (g is not None or gt is not None):
+                first, second = (g, gt) if g is not None else (gt, None)
+                o1, o2 = torch.empty_like(first), (torch.empty_like(second) if second is not None else None)
+                call("dasp_fir_same_adjoint", ptr(first), ptr(second), ptr(o1), ptr(o2), ptr(taps), AW_TAPS, 2 * bs, N, stream())
+                g, gt = (o1, o2) if g is not None else (None, o1)
+        if g is not None:
+            g = g.reshape(shape).to(dtype)
+        if gt is not None:
+            gt = gt.reshape(shape).to(ctx.tdtype)
+        return g, gt, None, None, None, None
+
+
 _TW = {}
 
 
@@ -349,3 +435,61 @@ def mrstft_loss(input: torch.Tensor, target: torch.Tensor, fft_sizes=(1024, 2048
     opts = _options("mrstft_loss", options)
     mel = _mel_options("mrstft_loss", options, fft_sizes)
     return _MRSTFTFunction.apply(input, target, tuple(zip(fft_sizes, hop_sizes, win_lengths)), eps, opts, mel)
+
+
+def _sum_diff_options(what, window, output, options):
+    """The loss's own keywords (window and output at the values it implements), then MultiResolutionSTFTLoss's validation of the rest."""
+    if window != _DEFAULTS["window"]:
+        raise NotImplementedError(f"{what}: window={window!r} is not implemented (only the default window={_DEFAULTS['window']!r})")
+    if output not in ("loss", "full"):
+        raise NotImplementedError(f"{what}: output={output!r} is not implemented (only output='loss' and output='full')")
+    return _options(what, options)
+
+
+def _sum_diff(input, target, res, eps, opts, mel, w_sum, w_diff, output):
+    if input.dim() != 3 or input.shape[1] != 2:
+        chs = input.shape[1] if input.dim() == 3 else f"shape {tuple(input.shape)}: not (bs, 2, seq_len);"
+        raise ValueError(f"Input must be stereo: {chs} channel(s).")
+    if input.shape != target.shape:
+        raise RuntimeError(f"input {tuple(input.shape)} and target {tuple(target.shape)} must have the same shape")
+    sum_loss, diff_loss = _SumDiffFunction.apply(input, target, res, eps, opts, mel)
+    loss = (w_sum * sum_loss + w_diff * diff_loss) / 2
+    return loss if output == "loss" else (loss, sum_loss, diff_loss)
+
+
+class SumAndDifferenceSTFTLoss(torch.nn.Module):
+    """auraloss.freq.SumAndDifferenceSTFTLoss (0.4.0): for (bs, 2, seq_len) signals, MultiResolutionSTFTLoss(fft_sizes, hop_sizes,
+    win_lengths, **kwargs) on L + R and on L - R as two separate losses, loss = (w_sum * sum_loss + w_diff * diff_loss) / 2;
+    output="full" returns (loss, sum_loss, diff_loss), each differentiable. fft_sizes, hop_sizes and win_lengths have no defaults, as in
+    auraloss. kwargs: the keyword options of MultiResolutionSTFTLoss (w_sc, w_log_mag, w_lin_mag, perceptual_weighting + sample_rate,
+    scale="mel" + n_bins, eps, device), refused where it refuses them; window at its default only. One workgroup owns a frame group of
+    both channels of an item (csrc/stftloss.hip: dasp_mrstft_sd_*): no L + R / L - R signals exist in memory, and the backward returns to channels in
+    the frequency domain, through one inverse transform. A channel count other than 2 raises ValueError."""
+
+    def __init__(self, fft_sizes, hop_sizes, win_lengths, window: str = "hann_window", w_sum: float = 1.0, w_diff: float = 1.0,
+                 output: str = "loss", **kwargs):
+        super().__init__()
+        if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
+            raise ValueError("fft_sizes, hop_sizes and win_lengths must have the same length")
+        kwargs = dict(kwargs)
+        self.eps = kwargs.pop("eps", 1e-8)
+        self._opts = _sum_diff_options(type(self).__name__, window, output, kwargs)
+        self._mel = _mel_options(type(self).__name__, kwargs, fft_sizes)
+        self.resolutions = tuple(zip(fft_sizes, hop_sizes, win_lengths))
+        self.w_sum, self.w_diff, self.output = float(w_sum), float(w_diff), output
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor):
+        return _sum_diff(input, target, self.resolutions, self.eps, self._opts, self._mel, self.w_sum, self.w_diff, self.output)
+
+
+def sum_and_difference_stft_loss(input: torch.Tensor, target: torch.Tensor, fft_sizes, hop_sizes, win_lengths, eps: float = 1e-8,
+                                 w_sum: float = 1.0, w_diff: float = 1.0, output: str = "loss", **options):
+    """SumAndDifferenceSTFTLoss(fft_sizes, hop_sizes, win_lengths, w_sum=w_sum, w_diff=w_diff, output=output, eps=eps, **options)(input,
+    target) as a function."""
+    if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
+        raise ValueError("fft_sizes, hop_sizes and win_lengths must have the same length")
+    options = dict(options)
+    window = options.pop("window", _DEFAULTS["window"])
+    opts = _sum_diff_options("sum_and_difference_stft_loss", window, output, options)
+    mel = _mel_options("sum_and_difference_stft_loss", options, fft_sizes)
+    return _sum_diff(input, target, tuple(zip(fft_sizes, hop_sizes, win_lengths)), eps, opts, mel, float(w_sum), float(w_diff), output)

@@ -465,6 +465,37 @@ int dasp_mrstft_mel_backward_target(const float* pred, const float* target, cons
                                     const float* stats, const float* gloss, float* gtarget, int rows, int N, int nres, const int* fft,
                                     const int* hop, const int* win, float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins,
                                     void* stream);
+/* The sum / difference loss of a stereo pair (auraloss.freq.SumAndDifferenceSTFTLoss): the loss above on L + R and on L - R as two
+ * separate losses, each with its own sums and its own means over the `items` rows of its half, from one launch per resolution and direction (a workgroup owns both channels of an item).
+ * pred, target: (items, 2, N) fp32, channel rows interleaved (row 2 b = left, 2 b + 1 = right of item b). Resolutions, weights and n_bins as
+ * for the weighted / mel entry points (n_fft a power of two in 8..8192; every size runs the generic-geometry kernels, one workgroup per
+ * frame group of an item). partials: dasp_mrstft_sd_partial_floats floats (2 x nres x items x groups x 4; -1: not supported).
+ * stats: 8 * nres floats, [(half * nres + res) * 4 + c], half 0 = sum, 1 = difference (forward -> backward). loss: 2 floats, (sum_loss,
+ * diff_loss), bit-identical run to run. gloss: 2 device floats, d objective / d sum_loss and d objective / d diff_loss; gpred / gtarget
+ * (items, 2, N) is overwritten with gloss[0] d sum_loss / d x + gloss[1] d diff_loss / d x: both halves' gradient spectra go back to
+ * channels in the frequency domain and through one packed inverse transform, one float atomic per sample, frame and channel.
+ * Null pointers: DASP_ERR_ARG before any launch. */
+long dasp_mrstft_sd_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win);
+int dasp_mrstft_sd_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int items,
+                           int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_log_mag,
+                           float w_lin_mag, void* stream);
+int dasp_mrstft_sd_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gpred,
+                            int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
+                            float w_log_mag, float w_lin_mag, void* stream);
+int dasp_mrstft_sd_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
+                                   float* gtarget, int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
+                                   float w_sc, float w_log_mag, float w_lin_mag, void* stream);
+long dasp_mrstft_sd_mel_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins);
+int dasp_mrstft_sd_mel_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials,
+                               float* stats, float* loss, int items, int N, int nres, const int* fft, const int* hop, const int* win,
+                               float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
+int dasp_mrstft_sd_mel_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                                const float* gloss, float* gpred, int items, int N, int nres, const int* fft, const int* hop,
+                                const int* win, float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
+int dasp_mrstft_sd_mel_backward_target(const float* pred, const float* target, const void* tw, const void* const* mel_tables,
+                                       const float* stats, const float* gloss, float* gtarget, int items, int N, int nres, const int* fft,
+                                       const int* hop, const int* win, float eps, float w_sc, float w_log_mag, float w_lin_mag,
+                                       int n_bins, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Filters longer than one biquad.  Replaces dasp_pytorch.signal.lfilter_via_fsm (dasp_pytorch/signal.py:95-133) for K = 4 .. 16
