@@ -114,6 +114,9 @@ SIGNATURES = {
     "dasp_mrstft_sd_mel_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
     "dasp_mrstft_sd_mel_backward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
     "dasp_mrstft_sd_mel_backward_target": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
+    "dasp_tdloss_scratch_doubles": (_l, [_l, _l]),
+    "dasp_tdloss_forward": (_i, [_p] * 6 + [_l, _l] + [_d] * 9 + [_i, _i, _p]),
+    "dasp_tdloss_backward": (_i, [_p] * 6 + [_l, _l] + [_d] * 9 + [_i, _i, _p]),
     "dasp_lfilter_work_doubles": (_l, [_i, _l, _i, _l]),
     "dasp_lfilter_forward": (_i, [_p, _p, _p, _i, _p, _p, _p, _l, _i, _l, _i, _i, _l, _p]),
     "dasp_lfilter_backward": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l, _i, _i, _l, _p]),

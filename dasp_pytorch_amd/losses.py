@@ -5,7 +5,11 @@ w_sc * spectral convergence + w_log_mag * log-magnitude L1 + w_lin_mag * linear-
 perceptual_weighting=True both signals first go through auraloss's 101-tap A-weighting FIR; with scale="mel", n_bins and sample_rate
 the three terms are taken on mel-scaled magnitudes W |X| (librosa's Slaney filterbank, mel_filterbank below), which is also what
 MelSTFTLoss computes. SumAndDifferenceSTFTLoss is that loss on the sum and on the difference of a stereo pair, from kernels whose workgroups own
-both channels of an item. Both arguments receive gradients."""
+both channels of an item. Both arguments receive gradients.
+
+The time-domain half of auraloss (auraloss.time: ESRLoss, DCLoss, LogCoshLoss, SNRLoss, SISDRLoss, SDSDRLoss) and the MSE term of the
+reference's examples/virtual_analog.py:299,324-326 are one weighted sum, time_domain_loss, from one moment pass over both signals
+(csrc/tdloss.hip); FIRFilter is auraloss.perceptual.FIRFilter, the pre-emphasis / A-weighting filter those losses are used behind."""
 import ctypes
 import functools
 import math
@@ -493,3 +497,264 @@ def sum_and_difference_stft_loss(input: torch.Tensor, target: torch.Tensor, fft_
     opts = _sum_diff_options("sum_and_difference_stft_loss", window, output, options)
     mel = _mel_options("sum_and_difference_stft_loss", options, fft_sizes)
     return _sum_diff(input, target, tuple(zip(fft_sizes, hop_sizes, win_lengths)), eps, opts, mel, float(w_sum), float(w_diff), output)
+
+
+# ---- auraloss.time on the fused moment kernels (csrc/tdloss.hip) ------------------------------------------------------------------------
+_TD_TERMS = ("w_esr", "w_dc", "w_log_cosh", "w_snr", "w_si_sdr", "w_sd_sdr", "w_mse")       # the order of the C ABI's weight arguments
+_TD_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+
+def _time_options(what, weights, a, zero_mean, eps, reduction):
+    """-> (the seven weights, a, eps, zero_mean, reduction code), validated as _options validates the STFT losses' keywords."""
+    w = tuple(float(v) for v in weights)
+    if not all(math.isfinite(v) for v in w):
+        raise ValueError(f"{what}: the term weights must be finite, got {', '.join(_TD_TERMS)} = {w}")
+    if not any(v != 0.0 for v in w):
+        raise ValueError(f"{what}: at least one of the term weights {', '.join(_TD_TERMS)} must be non-zero")
+    a, eps = float(a), float(eps)
+    if not (math.isfinite(a) and a > 0.0):
+        raise ValueError(f"{what}: a must be positive and finite, got {a!r}")
+    if not math.isfinite(eps):
+        raise ValueError(f"{what}: eps must be finite, got {eps!r}")
+    if reduction not in _TD_REDUCTIONS:
+        raise ValueError(f"{what}: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    return w, a, eps, bool(zero_mean), _TD_REDUCTIONS[reduction]
+
+
+def _check_pair(input, target):
+    if not isinstance(input, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise TypeError("input and target must be torch.Tensors")
+    if input.shape != target.shape:
+        raise RuntimeError(f"input {tuple(input.shape)} and target {tuple(target.shape)} must have the same shape")
+    if input.dim() < 1 or input.numel() == 0:
+        raise ValueError(f"input must be shaped (..., seq_len) with at least one sample, got {tuple(input.shape)}")
+
+
+class _TimeDomainFunction(torch.autograd.Function):
+    """cfg: _time_options' tuple. One forward call (moment pass, per-row finalize, scalar) and one backward launch for both gradients."""
+
+    @staticmethod
+    def forward(ctx, inp, target, cfg):
+        _lib.require_device(inp, "input")
+        _lib.require_device(target, "target")
+        _lib.require_same_device(inp, target=target)
+        from .ops64 import require_fp32_ok
+        require_fp32_ok(inp, "time_domain_loss")
+        w, a, eps, zero_mean, red = cfg
+        L = _lib.lib()
+        N = inp.shape[-1]
+        p32 = inp.detach().reshape(-1, N).to(torch.float32).contiguous()
+        t32 = target.detach().reshape(-1, N).to(torch.float32).contiguous()
+        rows = p32.shape[0]
+        nd = L.dasp_tdloss_scratch_doubles(rows, N)
+        if nd < 0:
+            raise _lib.DaspHipError(f"time_domain_loss: {rows} rows of {N} samples are not supported")
+        dev = inp.device
+        with torch.cuda.device(dev):
+            scratch = torch.empty(nd, dtype=torch.float64, device=dev)
+            moments = torch.empty(6 * rows, dtype=torch.float64, device=dev)
+            row_loss = torch.empty(rows, dtype=torch.float32, device=dev)
+            loss = torch.empty((), dtype=torch.float32, device=dev) if red else None
+            call("dasp_tdloss_forward", ptr(p32), ptr(t32), ptr(scratch), ptr(moments), ptr(row_loss), ptr(loss), rows, N, *w, a, eps,
+                 int(zero_mean), red, stream())
+        ctx.save_for_backward(p32, t32, moments)
+        ctx.cfg = (cfg, rows, N, inp.shape, inp.dtype, target.dtype)
+        return (loss if red else row_loss.reshape(inp.shape[:-1])).to(inp.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        p32, t32, moments = ctx.saved_tensors
+        (w, a, eps, zero_mean, red), rows, N, shape, dtype, tdtype = ctx.cfg
+        g = gt = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            with torch.cuda.device(p32.device):
+                gl = gout.detach().reshape(-1).to(torch.float32).contiguous()          # one value, or one per row for reduction="none"
+                g = torch.empty_like(p32) if ctx.needs_input_grad[0] else None
+                gt = torch.empty_like(t32) if ctx.needs_input_grad[1] else None
+                call("dasp_tdloss_backward", ptr(p32), ptr(t32), ptr(moments), ptr(gl), ptr(g), ptr(gt), rows, N, *w, a, eps, int(zero_mean), red,
+                     stream())
+        if g is not None:
+            g = g.reshape(shape).to(dtype)
+        if gt is not None:
+            gt = gt.reshape(shape).to(tdtype)
+        return g, gt, None
+
+
+def time_domain_loss(input: torch.Tensor, target: torch.Tensor, *, w_esr: float = 0.0, w_dc: float = 0.0, w_log_cosh: float = 0.0,
+                     w_snr: float = 0.0, w_si_sdr: float = 0.0, w_sd_sdr: float = 0.0, w_mse: float = 0.0, a: float = 1.0,
+                     zero_mean: bool = True, eps: float = 1e-8, reduction: str = "mean"):
+    """The weighted sum of auraloss.time's losses and an MSE term from one pass over (..., seq_len) signals. Per row (all leading axes),
+    with d = input - target: esr sum d^2 / (sum t^2 + eps); dc mean(d)^2 / (mean(t^2) + eps); log_cosh mean(log(cosh(a d) + eps) / a);
+    snr -10 log10(sum t^2 / (sum d^2 + eps) + eps); si_sdr and sd_sdr with alpha = sum p t / (sum t^2 + eps): -10 log10(sum (alpha t)^2 /
+    (sum (p - alpha t)^2 + eps) + eps) and -10 log10(sum (alpha t)^2 / (sum d^2 + eps) + eps), these three on the signals minus their row
+    means when zero_mean; mse mean(d^2). A weight of exactly 0 leaves its term out of value and gradient; one must be non-zero.
+    reduction: "mean" / "sum" over the rows, "none" the per-row values shaped input.shape[:-1]; the mse term is a per-row mean under every
+    reduction (w_mse=1 with "mean" is torch.nn.MSELoss(); "sum" is the sum of the rows' means, not MSELoss(reduction="sum")).
+    Both arguments are differentiable. float32, float16 and bfloat16 are computed in float32 and returned in the input's dtype."""
+    cfg = _time_options("time_domain_loss", (w_esr, w_dc, w_log_cosh, w_snr, w_si_sdr, w_sd_sdr, w_mse), a, zero_mean, eps, reduction)
+    _check_pair(input, target)
+    return _TimeDomainFunction.apply(input, target, cfg)
+
+
+class _TimeLoss(torch.nn.Module):
+    """One term of time_domain_loss with weight 1."""
+    _term = None
+
+    def __init__(self, a=1.0, zero_mean=True, eps=1e-8, reduction="mean"):
+        super().__init__()
+        weights = tuple(1.0 if name == self._term else 0.0 for name in _TD_TERMS)
+        self._cfg = _time_options(type(self).__name__, weights, a, zero_mean, eps, reduction)
+        self.eps, self.reduction = eps, reduction
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor):
+        _check_pair(input, target)
+        return _TimeDomainFunction.apply(input, target, self._cfg)
+
+
+class ESRLoss(_TimeLoss):
+    """auraloss.time.ESRLoss (0.4.0): error-to-signal ratio sum (target - input)^2 / (sum target^2 + eps) per row."""
+    _term = "w_esr"
+
+    def __init__(self, eps: float = 1e-8, reduction: str = "mean"):
+        super().__init__(eps=eps, reduction=reduction)
+
+
+class DCLoss(_TimeLoss):
+    """auraloss.time.DCLoss (0.4.0): mean(target - input)^2 / (mean(target^2) + eps) per row."""
+    _term = "w_dc"
+
+    def __init__(self, eps: float = 1e-8, reduction: str = "mean"):
+        super().__init__(eps=eps, reduction=reduction)
+
+
+class LogCoshLoss(_TimeLoss):
+    """auraloss.time.LogCoshLoss (0.4.0): mean(log(cosh(a (input - target)) + eps) / a) per row, evaluated without overflow at large
+    a |input - target| and without losing eps beside cosh ~ 1."""
+    _term = "w_log_cosh"
+
+    def __init__(self, a: float = 1.0, eps: float = 1e-8, reduction: str = "mean"):
+        super().__init__(a=a, eps=eps, reduction=reduction)
+        self.a = a
+
+
+class SNRLoss(_TimeLoss):
+    """auraloss.time.SNRLoss (0.4.0): -10 log10(sum target^2 / (sum (input - target)^2 + eps) + eps) per row, zero_mean: on the signals
+    minus their row means."""
+    _term = "w_snr"
+
+    def __init__(self, zero_mean: bool = True, eps: float = 1e-8, reduction: str = "mean"):
+        super().__init__(zero_mean=zero_mean, eps=eps, reduction=reduction)
+        self.zero_mean = zero_mean
+
+
+class SISDRLoss(_TimeLoss):
+    """auraloss.time.SISDRLoss (0.4.0): alpha = sum input target / (sum target^2 + eps); -10 log10(sum (alpha target)^2 /
+    (sum (input - alpha target)^2 + eps) + eps) per row."""
+    _term = "w_si_sdr"
+
+    def __init__(self, zero_mean: bool = True, eps: float = 1e-8, reduction: str = "mean"):
+        super().__init__(zero_mean=zero_mean, eps=eps, reduction=reduction)
+        self.zero_mean = zero_mean
+
+
+class SDSDRLoss(_TimeLoss):
+    """auraloss.time.SDSDRLoss (0.4.0): SISDRLoss's alpha; -10 log10(sum (alpha target)^2 / (sum (input - target)^2 + eps) + eps) per row."""
+    _term = "w_sd_sdr"
+
+    def __init__(self, zero_mean: bool = True, eps: float = 1e-8, reduction: str = "mean"):
+        super().__init__(zero_mean=zero_mean, eps=eps, reduction=reduction)
+        self.zero_mean = zero_mean
+
+
+_FIR_DEV = {}
+
+
+def _fir_taps(host, device):
+    """Host float32 taps on the device, one copy per (taps, device, stream), under _twiddles' capture rule (as _aw_taps)."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    key = (host.tobytes(), device.index, int(torch.cuda.current_stream(device).cuda_stream))
+    if not capturing and key in _FIR_DEV:
+        return _FIR_DEV[key]
+    taps = torch.empty(len(host), dtype=torch.float32, device=device)
+    call("dasp_fir_taps_store", ptr(taps), host.ctypes.data_as(ctypes.c_void_p), len(host), stream())
+    if not capturing:
+        if len(_FIR_DEV) >= 16:
+            _FIR_DEV.clear()
+        _FIR_DEV[key] = taps
+    return taps
+
+
+class _FIRPairFunction(torch.autograd.Function):
+    """Both signals through dasp_fir_same_forward in one launch; the backward is dasp_fir_same_adjoint on the gradients that exist."""
+
+    @staticmethod
+    def forward(ctx, inp, target, host_taps):
+        _lib.require_device(inp, "input")
+        _lib.require_device(target, "target")
+        _lib.require_same_device(inp, target=target)
+        from .ops64 import require_fp32_ok
+        require_fp32_ok(inp, "FIRFilter")
+        N = inp.shape[-1]
+        p32 = inp.detach().reshape(-1, N).to(torch.float32).contiguous()
+        t32 = target.detach().reshape(-1, N).to(torch.float32).contiguous()
+        rows = p32.shape[0]
+        with torch.cuda.device(inp.device):
+            taps = _fir_taps(host_taps, inp.device)
+            pf, tf = torch.empty_like(p32), torch.empty_like(t32)
+            call("dasp_fir_same_forward", ptr(p32), ptr(t32), ptr(pf), ptr(tf), ptr(taps), len(host_taps), rows, N, stream())
+        ctx.save_for_backward(taps)
+        ctx.cfg = (len(host_taps), rows, N, inp.shape, inp.dtype, target.dtype)
+        return pf.reshape(inp.shape).to(inp.dtype), tf.reshape(inp.shape).to(target.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gp, gt):
+        (taps,) = ctx.saved_tensors
+        ntaps, rows, N, shape, dtype, tdtype = ctx.cfg
+        grads = [g.detach().reshape(rows, N).to(torch.float32).contiguous() if need else None
+                 for g, need in zip((gp, gt), ctx.needs_input_grad[:2])]
+        live = [g for g in grads if g is not None]
+        if live:
+            with torch.cuda.device(taps.device):
+                outs = [torch.empty_like(g) for g in live]
+                call("dasp_fir_same_adjoint", ptr(live[0]), ptr(live[1] if len(live) > 1 else None), ptr(outs[0]),
+                     ptr(outs[1] if len(outs) > 1 else None), ptr(taps), ntaps, rows, N, stream())
+            outs = iter(outs)
+            grads = [next(outs) if g is not None else None for g in grads]
+        g0 = grads[0].reshape(shape).to(dtype) if grads[0] is not None else None
+        g1 = grads[1].reshape(shape).to(tdtype) if grads[1] is not None else None
+        return g0, g1, None
+
+
+class FIRFilter(torch.nn.Module):
+    """auraloss.perceptual.FIRFilter(filter_type="hp", coef=0.85, fs=44100, ntaps=101): forward(input, target) returns both signals
+    filtered, for ESRLoss()(*FIRFilter("hp")(y_hat, y)). Taps under conv1d's cross-correlation convention, y[n] = sum_k taps[k] x[n + k -
+    ntaps // 2]: "hp" [1, -coef, 0] (first-order pre-emphasis), "fd" [1, 0, -coef] (folded differentiator), "aw" the 101 A-weighting
+    taps of a_weighting_taps(fs) (ntaps must be 101). ntaps is odd. This library's definition of the length: the output has seq_len
+    samples, the signal taken as zero outside the row ("same" padding, conv1d(padding=ntaps // 2)). Both signals go through one launch
+    (dasp_fir_same_forward); the backward is the filter's adjoint."""
+
+    def __init__(self, filter_type: str = "hp", coef: float = 0.85, fs: float = 44100, ntaps: int = 101):
+        super().__init__()
+        ntaps = operator.index(ntaps)
+        if ntaps % 2 == 0:
+            raise ValueError(f"ntaps must be odd (default is 101), got {ntaps}")
+        if filter_type not in ("hp", "fd", "aw"):
+            raise ValueError(f"Invalid filter_type: {filter_type!r} (one of 'hp', 'fd', 'aw')")
+        coef = float(coef)
+        if not math.isfinite(coef):
+            raise ValueError(f"FIRFilter: coef must be finite, got {coef!r}")
+        self.filter_type, self.coef, self.fs, self.ntaps = filter_type, coef, fs, ntaps
+        if filter_type == "aw":
+            if ntaps != AW_TAPS:
+                raise NotImplementedError(f"FIRFilter: filter_type='aw' is implemented for ntaps={AW_TAPS} only, got {ntaps}")
+            taps = a_weighting_taps(float(fs))
+        else:
+            taps = np.array([1.0, -coef, 0.0] if filter_type == "hp" else [1.0, 0.0, -coef], dtype=np.float32)
+            taps.flags.writeable = False
+        self._taps = taps
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor):
+        _check_pair(input, target)
+        return _FIRPairFunction.apply(input, target, self._taps)

@@ -498,6 +498,36 @@ int dasp_mrstft_sd_mel_backward_target(const float* pred, const float* target, c
                                        int n_bins, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Time-domain losses.  Replaces auraloss.time.ESRLoss, DCLoss, LogCoshLoss, SNRLoss, SISDRLoss and SDSDRLoss (auraloss 0.4.0; not
+ * vendored by the reference - restated in tests/auraloss_time_restated.py) and the MSE term of the reference's
+ * examples/virtual_analog.py:299,324-326, as ONE weighted sum from one pass (csrc/tdloss.hip). Per row of N samples, d = p - t:
+ *   esr      sum d^2 / (sum t^2 + eps)                      dc    mean(d)^2 / (mean(t^2) + eps)
+ *   log_cosh mean(log(cosh(a d) + eps)) / a                 mse   mean(d^2)
+ *   snr      -10 log10(sum t^2 / (sum d^2 + eps) + eps)
+ *   si_sdr   alpha = sum p t / (sum t^2 + eps);  -10 log10(sum (alpha t)^2 / (sum (p - alpha t)^2 + eps) + eps)
+ *   sd_sdr   same alpha;                         -10 log10(sum (alpha t)^2 / (sum d^2 + eps) + eps)
+ * zero_mean != 0: snr, si_sdr and sd_sdr are taken on the signals minus their row means. A weight of exactly 0 leaves its term out of the
+ * value and the gradient (no 0 * inf); the weights, a > 0 and eps must be finite and one weight non-zero (DASP_ERR_ARG otherwise).
+ * reduction: 0 = none, 1 = mean over the rows, 2 = sum over the rows (of the per-row values: the mse term stays a per-row mean).
+ *   pred, target  (rows, N) fp32, contiguous; any 4-byte aligned address
+ *   scratch       dasp_tdloss_scratch_doubles(rows, N) doubles (-1: sizes not supported), written and read by the forward call only
+ *   moments       6 * rows doubles, [row][sum d, sum t, sum d^2, sum t^2, sum d t, sum log(cosh(a d) + eps)] (forward -> backward; the
+ *                 last one is 0 when w_log_cosh = 0)
+ *   row_loss      rows floats, the weighted loss of every row;  loss: 1 float, their mean / sum (not written, may be NULL, for reduction 0)
+ *   gloss         the upstream gradient on the device: 1 float for reduction 1 / 2, rows floats for reduction 0
+ *   gpred, gtarget  (rows, N) fp32, overwritten with gloss * d loss / d pred and d loss / d target in one launch; either may be NULL
+ * The backward call takes the options of the forward call that wrote `moments`. No atomics and nothing zeroed: loss and gradients are
+ * bit-identical run to run, and both calls are plain kernel launches on `stream` (capturable into a graph).
+ * ------------------------------------------------------------------------------------------- */
+long dasp_tdloss_scratch_doubles(long rows, long N);
+int dasp_tdloss_forward(const float* pred, const float* target, double* scratch, double* moments, float* row_loss, float* loss, long rows,
+                        long N, double w_esr, double w_dc, double w_log_cosh, double w_snr, double w_si_sdr, double w_sd_sdr, double w_mse,
+                        double a, double eps, int zero_mean, int reduction, void* stream);
+int dasp_tdloss_backward(const float* pred, const float* target, const double* moments, const float* gloss, float* gpred, float* gtarget,
+                         long rows, long N, double w_esr, double w_dc, double w_log_cosh, double w_snr, double w_si_sdr, double w_sd_sdr,
+                         double w_mse, double a, double eps, int zero_mean, int reduction, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Filters longer than one biquad.  Replaces dasp_pytorch.signal.lfilter_via_fsm (dasp_pytorch/signal.py:95-133) for K = 4 .. 16
  * coefficients per row (orders 3 .. 15; K <= 3 goes through the cascaded-biquad entry points above; the reference's only caller uses
  * K = 2, functional.py:372-380). Exact recurrence in double arithmetic, one thread per (row, chunk of time); the chunks run side by side
