@@ -87,33 +87,19 @@ SIGNATURES = {
     "dasp_panner_backward": (_i, [_p] * 6 + [_i, _i, _l, _p]),
     "dasp_bus_forward": (_i, [_p, _p, _p, _i, _i, _l, _p]),
     "dasp_bus_backward": (_i, [_p] * 6 + [_i, _i, _l, _p]),
-    "dasp_mrstft_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dasp_mrstft_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i]),
     "dasp_mrstft_table": (_i, [_p, _p]),
-    "dasp_mrstft_forward": (_i, [_p] * 6 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_float, _p]),
-    "dasp_mrstft_backward": (_i, [_p] * 6 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_float, _p]),
-    "dasp_mrstft_backward_target": (_i, [_p] * 6 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_float, _p]),
-    "dasp_mrstft_weighted_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
-    "dasp_mrstft_weighted_forward": (_i, [_p] * 6 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_p]),
-    "dasp_mrstft_weighted_backward": (_i, [_p] * 6 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_p]),
-    "dasp_mrstft_weighted_backward_target": (_i, [_p] * 6 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_p]),
+    "dasp_mrstft_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
+    "dasp_mrstft_backward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _i, _p]),
     "dasp_fir_same_forward": (_i, [_p] * 5 + [_i, _i, _i, _p]),
     "dasp_fir_same_adjoint": (_i, [_p] * 5 + [_i, _i, _i, _p]),
     "dasp_fir_taps_store": (_i, [_p, _p, _i, _p]),
     "dasp_mel_table_floats": (_l, [_i, _i]),
     "dasp_mel_table_store": (_i, [_p, _p, _d, _i, _i, _p]),
     "dasp_mel_table_dense": (_i, [_p, _p, _i, _i, _p]),
-    "dasp_mrstft_mel_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i]),
-    "dasp_mrstft_mel_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
-    "dasp_mrstft_mel_backward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
-    "dasp_mrstft_mel_backward_target": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
-    "dasp_mrstft_sd_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
-    "dasp_mrstft_sd_forward": (_i, [_p] * 6 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_p]),
-    "dasp_mrstft_sd_backward": (_i, [_p] * 6 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_p]),
-    "dasp_mrstft_sd_backward_target": (_i, [_p] * 6 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_p]),
-    "dasp_mrstft_sd_mel_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i]),
-    "dasp_mrstft_sd_mel_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
-    "dasp_mrstft_sd_mel_backward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
-    "dasp_mrstft_sd_mel_backward_target": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
+    "dasp_mrstft_sd_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i]),
+    "dasp_mrstft_sd_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
+    "dasp_mrstft_sd_backward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _i, _p]),
     "dasp_tdloss_scratch_doubles": (_l, [_l, _l]),
     "dasp_tdloss_forward": (_i, [_p] * 6 + [_l, _l] + [_d] * 9 + [_i, _i, _p]),
     "dasp_tdloss_backward": (_i, [_p] * 6 + [_l, _l] + [_d] * 9 + [_i, _i, _p]),

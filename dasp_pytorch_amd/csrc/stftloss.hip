@@ -174,16 +174,17 @@ mrstft_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ targ
         partials[(((size_t)res * gridDim.y + row) * spec.groups + blockIdx.x) * 4 + threadIdx.x] = a;
     }
 }
-// step 1, one workgroup per (resolution, sum): stats[res * 4 + c] = S_c, added up in fp64. 16 waves walk the rows, the lanes the
-// frame groups of a row, four loads in flight per lane (one thread per element with an index division: 17 us; this: ~5)
+// step 1, one workgroup per (half, resolution, sum): stats[(half * nres + res) * 4 + c] = S_c, added up in fp64; the mono loss has one
+// half, the sum / difference loss two (gridDim.x = halves * nres * 4). 16 waves walk the rows (items), the lanes the frame groups of a row,
+// four loads in flight per lane (one thread per element with an index division: 17 us; this: ~5)
 __global__ void __launch_bounds__(1024)
 mrstft_reduce_kernel(const float* __restrict__ partials, StftSpec spec, int rows, float* __restrict__ stats) {
     __shared__ double red[16];
-    const int res = blockIdx.x / 4, c = blockIdx.x % 4, l = lane_id(), wv = wave_id();
+    const int hr = blockIdx.x / 4, c = blockIdx.x % 4, res = hr % spec.nres, l = lane_id(), wv = wave_id();
     const int TC = frames_per_group(spec.r[res].logF), ng = (spec.r[res].frames + TC - 1) / TC;
     double s = 0.0;
     for (int row = wv; row < rows; row += 16) {
-        const float* p = partials + ((size_t)res * rows + row) * spec.groups * 4 + c;
+        const float* p = partials + ((size_t)hr * rows + row) * spec.groups * 4 + c;
         for (int g0 = l; g0 < ng; g0 += 256) {
             float v[4];
 #pragma unroll
@@ -198,26 +199,30 @@ mrstft_reduce_kernel(const float* __restrict__ partials, StftSpec spec, int rows
     if (threadIdx.x == 0) {
         double t = 0.0;
         for (int v = 0; v < 16; ++v) t += red[v];
-        stats[res * 4 + c] = (float)t;
+        stats[hr * 4 + c] = (float)t;
     }
 }
-// step 2: stats[res] = (sqrt S1, sqrt S2, count, S3); loss[0] = mean over resolutions of
-// w_sc sqrt(S1)/sqrt(S2) + w_lm S3/count + w_lin S4/count, a term with weight 0 left out (weights 1, 1, 0: the sum of the first two as before)
-__global__ void mrstft_finalize_kernel(StftSpec spec, int rows, float* __restrict__ stats, float* __restrict__ loss) {
-    if (threadIdx.x != 0) return;
+// step 2, thread h < halves for half h: stats[(h * nres + res) * 4 ..] = (sqrt S1, sqrt S2, count, S3); loss[h] = mean over resolutions of
+// w_sc sqrt(S1)/sqrt(S2) + w_lm S3/count + w_lin S4/count, a term with weight 0 left out. count = rows x frames x (n_fft / 2 + 1), or
+// rows x frames x n_bins on mel-scaled magnitudes (nbins > 0)
+__global__ void mrstft_finalize_kernel(StftSpec spec, int rows, int nbins, int halves, float* __restrict__ stats, float* __restrict__ loss) {
+    if ((int)threadIdx.x >= halves) return;
+    const int half = threadIdx.x;
+    float* st = stats + half * spec.nres * 4;
     double total = 0.0;
     for (int res = 0; res < spec.nres; ++res) {
-        const double F = (double)(1 << spec.r[res].logF), count = (double)rows * spec.r[res].frames * (F / 2 + 1);
-        const double s1 = sqrt((double)stats[res * 4 + 0]), s2 = sqrt((double)stats[res * 4 + 1]), s3 = (double)stats[res * 4 + 2];
-        const double s4 = (double)stats[res * 4 + 3];
-        stats[res * 4 + 0] = (float)s1; stats[res * 4 + 1] = (float)s2; stats[res * 4 + 2] = (float)count; stats[res * 4 + 3] = (float)s3;
+        const double F = (double)(1 << spec.r[res].logF);
+        const double count = (double)rows * spec.r[res].frames * (nbins > 0 ? (double)nbins : F / 2 + 1);
+        const double s1 = sqrt((double)st[res * 4 + 0]), s2 = sqrt((double)st[res * 4 + 1]), s3 = (double)st[res * 4 + 2];
+        const double s4 = (double)st[res * 4 + 3];
+        st[res * 4 + 0] = (float)s1; st[res * 4 + 1] = (float)s2; st[res * 4 + 2] = (float)count; st[res * 4 + 3] = (float)s3;
         double l = 0.0;
         if (spec.w_sc != 0.f) l += (double)spec.w_sc * (s1 / s2);
         if (spec.w_lm != 0.f) l += (double)spec.w_lm * (s3 / count);
         if (spec.w_lin != 0.f) l += (double)spec.w_lin * (s4 / count);
         total += l;
     }
-    loss[0] = (float)(total / spec.nres);
+    loss[half] = (float)(total / spec.nres);
 }
 
 // gpred (rows, N) must be zero on entry; gloss = d(objective)/d(loss), a device scalar
@@ -648,23 +653,6 @@ mrstft_mel_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ 
         partials[(((size_t)res * gridDim.y + row) * spec.groups + blockIdx.x) * 4 + threadIdx.x] = a;
     }
 }
-// mrstft_finalize_kernel with count = rows x frames x n_bins
-__global__ void mrstft_mel_finalize_kernel(StftSpec spec, int rows, int nbins, float* __restrict__ stats, float* __restrict__ loss) {
-    if (threadIdx.x != 0) return;
-    double total = 0.0;
-    for (int res = 0; res < spec.nres; ++res) {
-        const double count = (double)rows * spec.r[res].frames * (double)nbins;
-        const double s1 = sqrt((double)stats[res * 4 + 0]), s2 = sqrt((double)stats[res * 4 + 1]), s3 = (double)stats[res * 4 + 2];
-        const double s4 = (double)stats[res * 4 + 3];
-        stats[res * 4 + 0] = (float)s1; stats[res * 4 + 1] = (float)s2; stats[res * 4 + 2] = (float)count; stats[res * 4 + 3] = (float)s3;
-        double l = 0.0;
-        if (spec.w_sc != 0.f) l += (double)spec.w_sc * (s1 / s2);
-        if (spec.w_lm != 0.f) l += (double)spec.w_lm * (s3 / count);
-        if (spec.w_lin != 0.f) l += (double)spec.w_lin * (s4 / count);
-        total += l;
-    }
-    loss[0] = (float)(total / spec.nres);
-}
 
 // dL/dM_P[m][c] goes to LDS behind the magnitudes (dm[m TC + c], n_bins TC <= (F/2 + 1) TC floats: 7680 (8450) of the buffer in all), each
 // thread then gathers dL/d|P| of its bins from its at most two filters; the rest is mrstft_bwd_kernel
@@ -738,30 +726,68 @@ inline int sl_check() {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? DASP_OK : (int)e;
 }
-// maxlog: 12 for the entry points of the default loss (n_fft <= 4096), 13 for the weighted ones (n_fft <= 8192)
-bool sl_spec(int N, int nres, const int* fft, const int* hop, const int* win, float eps, StftSpec* out, int maxlog = 12,
-             float w_sc = 1.f, float w_lm = 1.f, float w_lin = 0.f) {
+// log2 of a frame length the transforms take (a power of two in 8..8192), else -1
+int fft_log2(int n_fft) {
+    int lg = 0;
+    while (lg < 30 && (1 << lg) < n_fft) ++lg;
+    return (1 << lg) == n_fft && lg >= 3 && lg <= 13 ? lg : -1;
+}
+bool mel_bins_ok(int n_fft, int n_bins) {
+    return fft_log2(n_fft) >= 0 && n_bins >= 1 && n_bins <= MEL_MAXBINS && n_bins <= n_fft / 2 + 1;
+}
+// the workgroups of resolution r: frame groups x rows (items of the sum / difference loss)
+dim3 res_grid(const StftSpec& s, int r, int rows) {
+    const int TC = frames_per_group(s.r[r].logF);
+    return dim3((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
+}
+// n_bins: 0 for linear bins, else the mel filters of every resolution
+bool stft_spec(int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_lm, float w_lin, int n_bins,
+               StftSpec* out) {
     if (nres <= 0 || nres > SL_MAXRES || !fft || !hop || !win) return false;
     if (!std::isfinite(w_sc) || !std::isfinite(w_lm) || !std::isfinite(w_lin)) return false;
     StftSpec s = {};
     s.nres = nres; s.eps = eps; s.groups = 0; s.w_sc = w_sc; s.w_lm = w_lm; s.w_lin = w_lin;
     for (int r = 0; r < nres; ++r) {
-        int lg = 0;
-        while (lg < 30 && (1 << lg) < fft[r]) ++lg;
-        if ((1 << lg) != fft[r] || lg < 3 || lg > maxlog || hop[r] <= 0 || win[r] <= 0 || win[r] > fft[r] || fft[r] / 2 >= N) return false;
+        const int lg = fft_log2(fft[r]);
+        if (lg < 0 || hop[r] <= 0 || win[r] <= 0 || win[r] > fft[r] || fft[r] / 2 >= N) return false;
+        if (n_bins != 0 && !mel_bins_ok(fft[r], n_bins)) return false;
         s.r[r] = StftRes{lg, hop[r], win[r], 1 + N / hop[r]};
-        const int TC = frames_per_group(lg), ng = (s.r[r].frames + TC - 1) / TC;
+        const int ng = (int)res_grid(s, r, 1).x;
         if (ng > s.groups) s.groups = ng;
     }
     *out = s;
     return true;
 }
+// tab: the resolution's mel table, or null for linear bins. 512 / 1024 / 2048-point frames on linear bins: 1 / 2 / 4 waves per frame;
+// 8192 points: 16 waves; anything else: col_fft
+void mrstft_fwd_launch(const float* pred, const float* target, const void* tw, const float* tab, float* partials, const StftSpec& s, int rows,
+                       int N, int r, int n_bins, hipStream_t st) {
+    const dim3 grid = res_grid(s, r, rows);
+    const int lg = s.r[r].logF;
+    if (tab) {
+        if (lg == 13) hipLaunchKernelGGL(mrstft_mel_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
+        else hipLaunchKernelGGL(mrstft_mel_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
+        return;
+    }
+    switch (lg) {
+        case 9: hipLaunchKernelGGL(mrstft_fwd_split_kernel<1>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
+        case 10: hipLaunchKernelGGL(mrstft_fwd_split_kernel<2>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
+        case 11: hipLaunchKernelGGL(mrstft_fwd_split_kernel<4>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
+        case 13: hipLaunchKernelGGL(mrstft_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
+        default: hipLaunchKernelGGL(mrstft_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
+    }
+}
 template <bool LIN>
-void mrstft_bwd_launch(const float* first, const float* second, const void* tw, const float* stats, const float* gloss, float* gfirst,
-                              const StftSpec& s, int rows, int N, int r, int wrt_second, hipStream_t st) {
-    const int TC = frames_per_group(s.r[r].logF);
-    const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
-    switch (s.r[r].logF) {
+void mrstft_bwd_launch(const float* first, const float* second, const void* tw, const float* tab, const float* stats, const float* gloss,
+                       float* gfirst, const StftSpec& s, int rows, int N, int r, int n_bins, int wrt_second, hipStream_t st) {
+    const dim3 grid = res_grid(s, r, rows);
+    const int lg = s.r[r].logF;
+    if (tab) {
+        if (lg == 13) hipLaunchKernelGGL((mrstft_mel_bwd_kernel<13, LIN>), grid, dim3(1024), 0, st, first, second, (const f2*)tw, tab, stats, gloss, gfirst, s, N, r, n_bins, wrt_second);
+        else hipLaunchKernelGGL((mrstft_mel_bwd_kernel<12, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, tab, stats, gloss, gfirst, s, N, r, n_bins, wrt_second);
+        return;
+    }
+    switch (lg) {
         case 9: hipLaunchKernelGGL((mrstft_bwd_split_kernel<1, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
         case 10: hipLaunchKernelGGL((mrstft_bwd_split_kernel<2, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
         case 11: hipLaunchKernelGGL((mrstft_bwd_split_kernel<4, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second); break;
@@ -769,106 +795,15 @@ void mrstft_bwd_launch(const float* first, const float* second, const void* tw, 
         default: hipLaunchKernelGGL((mrstft_bwd_kernel<12, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second);
     }
 }
-template <bool LIN>
-void mrstft_mel_bwd_launch(const float* first, const float* second, const void* tw, const float* tab, const float* stats, const float* gloss,
-                                  float* gfirst, const StftSpec& s, int rows, int N, int r, int n_bins, int wrt_second, hipStream_t st) {
-    const int TC = frames_per_group(s.r[r].logF);
-    const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
-    if (s.r[r].logF == 13)
-        hipLaunchKernelGGL((mrstft_mel_bwd_kernel<13, LIN>), grid, dim3(1024), 0, st, first, second, (const f2*)tw, tab, stats, gloss, gfirst, s, N, r, n_bins, wrt_second);
-    else
-        hipLaunchKernelGGL((mrstft_mel_bwd_kernel<12, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, tab, stats, gloss, gfirst, s, N, r, n_bins, wrt_second);
-}
 }  // namespace
 
 extern "C" {
 
-/* floats of `partials` for rows signals of N samples; -1 if the resolutions are not supported (n_fft a power of two in 8..4096,
- * win <= n_fft, n_fft / 2 < N, at most 8 resolutions) */
-long dasp_mrstft_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win) {
-    StftSpec s;
-    if (!sl_spec(N, nres, fft, hop, win, 0.f, &s)) return -1;
-    return (long)nres * rows * s.groups * 4;
-}
-/* the same for the weighted entry points: n_fft a power of two in 8..8192 */
-long dasp_mrstft_weighted_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win) {
-    StftSpec s;
-    if (!sl_spec(N, nres, fft, hop, win, 0.f, &s, 13)) return -1;
-    return (long)nres * rows * s.groups * 4;
-}
 /* tw: 4096 complex (8192 floats), the twiddle table the transforms read */
 int dasp_mrstft_table(void* tw, void* stream) {
     if (!tw) return DASP_ERR_ARG;
     hipLaunchKernelGGL(stft_twiddle_kernel, dim3(FFT_N / 256), dim3(256), 0, (hipStream_t)stream, (f2*)tw);
     return sl_check();
-}
-static int mrstft_forward_impl(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int rows,
-                               int N, int nres, const int* fft, const int* hop, const int* win, float eps, int maxlog, float w_sc, float w_lm,
-                               float w_lin, void* stream) {
-    if (!pred || !target || !tw || !partials || !stats || !loss || rows <= 0 || N <= 0) return DASP_ERR_ARG;
-    StftSpec s;
-    if (!sl_spec(N, nres, fft, hop, win, eps, &s, maxlog, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
-    if (rows > 65535) return DASP_ERR_UNSUPPORTED;
-    for (int r = 0; r < nres; ++r) {
-        const int TC = frames_per_group(s.r[r].logF);
-        const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
-        hipStream_t st = (hipStream_t)stream;
-        switch (s.r[r].logF) {          // 512 / 1024 / 2048-point frames: 1 / 2 / 4 waves per frame; 8192: 16 waves; any other power of two: col_fft
-            case 9: hipLaunchKernelGGL(mrstft_fwd_split_kernel<1>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
-            case 10: hipLaunchKernelGGL(mrstft_fwd_split_kernel<2>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
-            case 11: hipLaunchKernelGGL(mrstft_fwd_split_kernel<4>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
-            case 13: hipLaunchKernelGGL(mrstft_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, partials, s, N, r); break;
-            default: hipLaunchKernelGGL(mrstft_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
-        }
-    }
-    hipLaunchKernelGGL(mrstft_reduce_kernel, dim3((unsigned)(nres * 4)), dim3(1024), 0, (hipStream_t)stream, (const float*)partials, s, rows, stats);
-    hipLaunchKernelGGL(mrstft_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, s, rows, stats, loss);
-    return sl_check();
-}
-/* pred, target (rows, N); stats (4 * nres floats, kept for the backward); loss: 1 float */
-int dasp_mrstft_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int rows, int N,
-                        int nres, const int* fft, const int* hop, const int* win, float eps, void* stream) {
-    return mrstft_forward_impl(pred, target, tw, partials, stats, loss, rows, N, nres, fft, hop, win, eps, 12, 1.f, 1.f, 0.f, stream);
-}
-int dasp_mrstft_weighted_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int rows,
-                                 int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_log_mag,
-                                 float w_lin_mag, void* stream) {
-    return mrstft_forward_impl(pred, target, tw, partials, stats, loss, rows, N, nres, fft, hop, win, eps, 13, w_sc, w_log_mag, w_lin_mag, stream);
-}
-/* gpred (rows, N) is overwritten with gloss * d loss / d pred (gloss: device scalar); dasp_mrstft_backward_target: the same for the
- * second signal, gtarget = gloss * d loss / d target (auraloss differentiates both arguments: a consistency loss between two model
- * outputs needs it; the reference's call sites pass the reference signal there and never ask) */
-static int mrstft_backward_impl(const float* first, const float* second, const void* tw, const float* stats, const float* gloss, float* gfirst,
-                                int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, int wrt_second, void* stream,
-                                int maxlog = 12, float w_sc = 1.f, float w_lm = 1.f, float w_lin = 0.f) {
-    if (!first || !second || !tw || !stats || !gloss || !gfirst || rows <= 0 || N <= 0) return DASP_ERR_ARG;
-    StftSpec s;
-    if (!sl_spec(N, nres, fft, hop, win, eps, &s, maxlog, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
-    if (rows > 65535) return DASP_ERR_UNSUPPORTED;
-    if (zero_async(gfirst, (size_t)rows * N * sizeof(float), (hipStream_t)stream) != hipSuccess) return sl_check();
-    for (int r = 0; r < nres; ++r) {
-        if (s.w_lin != 0.f) mrstft_bwd_launch<true>(first, second, tw, stats, gloss, gfirst, s, rows, N, r, wrt_second, (hipStream_t)stream);
-        else mrstft_bwd_launch<false>(first, second, tw, stats, gloss, gfirst, s, rows, N, r, wrt_second, (hipStream_t)stream);
-    }
-    return sl_check();
-}
-int dasp_mrstft_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gpred, int rows,
-                         int N, int nres, const int* fft, const int* hop, const int* win, float eps, void* stream) {
-    return mrstft_backward_impl(pred, target, tw, stats, gloss, gpred, rows, N, nres, fft, hop, win, eps, 0, stream);
-}
-int dasp_mrstft_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gtarget,
-                                int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, void* stream) {
-    return mrstft_backward_impl(target, pred, tw, stats, gloss, gtarget, rows, N, nres, fft, hop, win, eps, 1, stream);
-}
-int dasp_mrstft_weighted_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gpred,
-                                  int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
-                                  float w_log_mag, float w_lin_mag, void* stream) {
-    return mrstft_backward_impl(pred, target, tw, stats, gloss, gpred, rows, N, nres, fft, hop, win, eps, 0, stream, 13, w_sc, w_log_mag, w_lin_mag);
-}
-int dasp_mrstft_weighted_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
-                                         float* gtarget, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
-                                         float w_sc, float w_log_mag, float w_lin_mag, void* stream) {
-    return mrstft_backward_impl(target, pred, tw, stats, gloss, gtarget, rows, N, nres, fft, hop, win, eps, 1, stream, 13, w_sc, w_log_mag, w_lin_mag);
 }
 
 static int fir_same_launch(const float* a, const float* b, float* ya, float* yb, const float* taps, int ntaps, int rows, int N, int flip,
@@ -896,18 +831,6 @@ int dasp_fir_taps_store(float* dst, const float* host_taps, int ntaps, void* str
 }
 
 /* ---- scale="mel" ---- */
-static bool mel_bins_ok(int n_fft, int n_bins) {
-    int lg = 0;
-    while (lg < 30 && (1 << lg) < n_fft) ++lg;
-    return (1 << lg) == n_fft && lg >= 3 && lg <= 13 && n_bins >= 1 && n_bins <= MEL_MAXBINS && n_bins <= n_fft / 2 + 1;
-}
-static bool mel_spec(int N, int nres, const int* fft, const int* hop, const int* win, float eps, int n_bins, StftSpec* out, float w_sc = 1.f,
-                     float w_lm = 1.f, float w_lin = 0.f) {
-    if (!sl_spec(N, nres, fft, hop, win, eps, out, 13, w_sc, w_lm, w_lin)) return false;
-    for (int r = 0; r < nres; ++r)
-        if (!mel_bins_ok(fft[r], n_bins)) return false;
-    return true;
-}
 /* floats of one resolution's mel table; -1: n_fft not a power of two in 8..8192, or n_bins outside 1..min(256, n_fft / 2 + 1) */
 long dasp_mel_table_floats(int n_fft, int n_bins) {
     return mel_bins_ok(n_fft, n_bins) ? mel_table_len(n_fft, n_bins) : -1;
@@ -933,62 +856,6 @@ int dasp_mel_table_dense(const float* table, float* dense, int n_fft, int n_bins
     const int K = n_fft / 2 + 1;
     hipLaunchKernelGGL(mel_dense_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)n_bins), dim3(256), 0, (hipStream_t)stream, table, dense, n_fft, n_bins);
     return sl_check();
-}
-long dasp_mrstft_mel_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins) {
-    StftSpec s;
-    if (!mel_spec(N, nres, fft, hop, win, 0.f, n_bins, &s)) return -1;
-    return (long)nres * rows * s.groups * 4;
-}
-/* mel_tables: nres device pointers (a host array), table r built by dasp_mel_table_store for fft[r] and n_bins */
-int dasp_mrstft_mel_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials, float* stats,
-                            float* loss, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
-                            float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
-    if (!pred || !target || !tw || !mel_tables || !partials || !stats || !loss || rows <= 0 || N <= 0) return DASP_ERR_ARG;
-    StftSpec s;
-    if (!mel_spec(N, nres, fft, hop, win, eps, n_bins, &s, w_sc, w_log_mag, w_lin_mag)) return DASP_ERR_UNSUPPORTED;
-    if (rows > 65535) return DASP_ERR_UNSUPPORTED;
-    for (int r = 0; r < nres; ++r)
-        if (!mel_tables[r]) return DASP_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    for (int r = 0; r < nres; ++r) {
-        const int TC = frames_per_group(s.r[r].logF);
-        const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)rows);
-        const float* tab = (const float*)mel_tables[r];
-        if (s.r[r].logF == 13) hipLaunchKernelGGL(mrstft_mel_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
-        else hipLaunchKernelGGL(mrstft_mel_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
-    }
-    hipLaunchKernelGGL(mrstft_reduce_kernel, dim3((unsigned)(nres * 4)), dim3(1024), 0, st, (const float*)partials, s, rows, stats);
-    hipLaunchKernelGGL(mrstft_mel_finalize_kernel, dim3(1), dim3(64), 0, st, s, rows, n_bins, stats, loss);
-    return sl_check();
-}
-static int mrstft_mel_backward_impl(const float* first, const float* second, const void* tw, const void* const* mel_tables, const float* stats,
-                                    const float* gloss, float* gfirst, int rows, int N, int nres, const int* fft, const int* hop, const int* win,
-                                    float eps, float w_sc, float w_lm, float w_lin, int n_bins, int wrt_second, void* stream) {
-    if (!first || !second || !tw || !mel_tables || !stats || !gloss || !gfirst || rows <= 0 || N <= 0) return DASP_ERR_ARG;
-    StftSpec s;
-    if (!mel_spec(N, nres, fft, hop, win, eps, n_bins, &s, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
-    if (rows > 65535) return DASP_ERR_UNSUPPORTED;
-    for (int r = 0; r < nres; ++r)
-        if (!mel_tables[r]) return DASP_ERR_ARG;
-    if (zero_async(gfirst, (size_t)rows * N * sizeof(float), (hipStream_t)stream) != hipSuccess) return sl_check();
-    for (int r = 0; r < nres; ++r) {
-        const float* tab = (const float*)mel_tables[r];
-        if (s.w_lin != 0.f) mrstft_mel_bwd_launch<true>(first, second, tw, tab, stats, gloss, gfirst, s, rows, N, r, n_bins, wrt_second, (hipStream_t)stream);
-        else mrstft_mel_bwd_launch<false>(first, second, tw, tab, stats, gloss, gfirst, s, rows, N, r, n_bins, wrt_second, (hipStream_t)stream);
-    }
-    return sl_check();
-}
-int dasp_mrstft_mel_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
-                             const float* gloss, float* gpred, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
-                             float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
-    return mrstft_mel_backward_impl(pred, target, tw, mel_tables, stats, gloss, gpred, rows, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag,
-                                    n_bins, 0, stream);
-}
-int dasp_mrstft_mel_backward_target(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
-                                    const float* gloss, float* gtarget, int rows, int N, int nres, const int* fft, const int* hop, const int* win,
-                                    float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
-    return mrstft_mel_backward_impl(target, pred, tw, mel_tables, stats, gloss, gtarget, rows, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag,
-                                    n_bins, 1, stream);
 }
 
 }  // extern "C"
@@ -1117,53 +984,6 @@ mrstft_sd_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ t
     for (int q = 0; q < 8; ++q)
         if (live && g2.j + g2.T * q <= F / 2) loss_terms(split_bin(r[q], i[q], mr[q], mi[q]), spec.eps, s[4], s[5], s[6], s[7]);
     sd_write_partials<NW>(s, red, partials, spec, res);
-}
-// mrstft_reduce_kernel over 2 nres (half, resolution) pairs: one workgroup per (half, resolution, sum), fp64, fixed order
-__global__ void __launch_bounds__(1024)
-mrstft_sd_reduce_kernel(const float* __restrict__ partials, StftSpec spec, int items, float* __restrict__ stats) {
-    __shared__ double red[16];
-    const int hr = blockIdx.x / 4, c = blockIdx.x % 4, res = hr % spec.nres, l = lane_id(), wv = wave_id();
-    const int TC = frames_per_group(spec.r[res].logF), ng = (spec.r[res].frames + TC - 1) / TC;
-    double s = 0.0;
-    for (int row = wv; row < items; row += 16) {
-        const float* p = partials + ((size_t)hr * items + row) * spec.groups * 4 + c;
-        for (int g0 = l; g0 < ng; g0 += 256) {
-            float v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { const int gi = g0 + 64 * u; v[u] = p[(size_t)(gi < ng ? gi : ng - 1) * 4]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) s += g0 + 64 * u < ng ? (double)v[u] : 0.0;
-        }
-    }
-    s = wave_sum(s);
-    if (l == 0) red[wv] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int v = 0; v < 16; ++v) t += red[v];
-        stats[hr * 4 + c] = (float)t;
-    }
-}
-// thread `half` finalizes its half as mrstft_finalize_kernel does: stats[(half nres + res) 4 ..] = (sqrt S1, sqrt S2, count, S3), loss[half];
-// count = items x frames x (n_fft / 2 + 1), or items x frames x n_bins on mel-scaled magnitudes (nbins > 0)
-__global__ void mrstft_sd_finalize_kernel(StftSpec spec, int items, int nbins, float* __restrict__ stats, float* __restrict__ loss) {
-    if (threadIdx.x >= 2) return;
-    const int half = threadIdx.x;
-    float* st = stats + half * spec.nres * 4;
-    double total = 0.0;
-    for (int res = 0; res < spec.nres; ++res) {
-        const double F = (double)(1 << spec.r[res].logF);
-        const double count = (double)items * spec.r[res].frames * (nbins > 0 ? (double)nbins : F / 2 + 1);
-        const double s1 = sqrt((double)st[res * 4 + 0]), s2 = sqrt((double)st[res * 4 + 1]), s3 = (double)st[res * 4 + 2];
-        const double s4 = (double)st[res * 4 + 3];
-        st[res * 4 + 0] = (float)s1; st[res * 4 + 1] = (float)s2; st[res * 4 + 2] = (float)count; st[res * 4 + 3] = (float)s3;
-        double l = 0.0;
-        if (spec.w_sc != 0.f) l += (double)spec.w_sc * (s1 / s2);
-        if (spec.w_lm != 0.f) l += (double)spec.w_lm * (s3 / count);
-        if (spec.w_lin != 0.f) l += (double)spec.w_lin * (s4 / count);
-        total += l;
-    }
-    loss[half] = (float)(total / spec.nres);
 }
 
 // slot k of the Hermitian spectrum G from the one-sided gradient bin H of bin k (k <= F/2) or F - k (k > F/2)
@@ -1365,12 +1185,10 @@ mrstft_sd_mel_bwd_kernel(const float* __restrict__ first, const float* __restric
 }  // namespace dasp
 
 namespace {
-// tab: one resolution's mel table, or null for the plain loss
 template <bool LIN>
 void mrstft_sd_bwd_launch(const float* first, const float* second, const void* tw, const float* tab, const float* stats, const float* gloss,
                           float* gfirst, const StftSpec& s, int items, int N, int r, int n_bins, int wrt_second, hipStream_t st) {
-    const int TC = frames_per_group(s.r[r].logF);
-    const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)items);
+    const dim3 grid = res_grid(s, r, items);
     const bool big = s.r[r].logF == 13;
     if (tab) {
         if (big) hipLaunchKernelGGL((mrstft_sd_mel_bwd_kernel<13, LIN>), grid, dim3(1024), 0, st, first, second, (const f2*)tw, tab, stats, gloss, gfirst, s, N, r, n_bins, wrt_second);
@@ -1380,52 +1198,68 @@ void mrstft_sd_bwd_launch(const float* first, const float* second, const void* t
         else hipLaunchKernelGGL((mrstft_sd_bwd_kernel<12, LIN>), grid, dim3(512), 0, st, first, second, (const f2*)tw, stats, gloss, gfirst, s, N, r, wrt_second);
     }
 }
-// mel_tables null: the plain loss (n_bins ignored)
-bool sd_spec(int N, int nres, const int* fft, const int* hop, const int* win, float eps, const void* const* mel_tables, int n_bins, StftSpec* s,
-             float w_sc = 1.f, float w_lm = 1.f, float w_lin = 0.f) {
-    return mel_tables ? mel_spec(N, nres, fft, hop, win, eps, n_bins, s, w_sc, w_lm, w_lin) : sl_spec(N, nres, fft, hop, win, eps, s, 13, w_sc, w_lm, w_lin);
+void mrstft_sd_fwd_launch(const float* pred, const float* target, const void* tw, const float* tab, float* partials, const StftSpec& s, int items,
+                          int N, int r, int n_bins, hipStream_t st) {
+    const dim3 grid = res_grid(s, r, items);
+    const bool big = s.r[r].logF == 13;
+    if (tab) {
+        if (big) hipLaunchKernelGGL(mrstft_sd_mel_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
+        else hipLaunchKernelGGL(mrstft_sd_mel_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
+    } else {
+        if (big) hipLaunchKernelGGL(mrstft_sd_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
+        else hipLaunchKernelGGL(mrstft_sd_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
+    }
 }
-int sd_forward_impl(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials, float* stats, float* loss,
-                    int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_lm, float w_lin,
-                    int n_bins, void* stream) {
-    if (!pred || !target || !tw || !partials || !stats || !loss || items <= 0 || N <= 0) return DASP_ERR_ARG;
+// The two layouts of the loss share everything but the kernels of a resolution: halves = 1, the mono loss on `rows` signals; halves = 2, the
+// sum / difference loss on `rows` items of two channel rows each. n_bins and mel_tables: both zero (linear bins) or both set (mel).
+long partial_floats(int halves, long rows, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins) {
     StftSpec s;
-    if (!sd_spec(N, nres, fft, hop, win, eps, mel_tables, n_bins, &s, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
-    if (items > 65535) return DASP_ERR_UNSUPPORTED;
+    if (!stft_spec(N, nres, fft, hop, win, 0.f, 1.f, 1.f, 0.f, n_bins, &s)) return -1;
+    return (long)halves * nres * rows * s.groups * 4;
+}
+// the checks of both directions, in the order of their statuses; io: the direction's own three buffers
+int stft_check(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const void* io0, const void* io1,
+               const void* io2, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_lm,
+               float w_lin, int n_bins, StftSpec* s) {
+    if (!pred || !target || !tw || !io0 || !io1 || !io2 || rows <= 0 || N <= 0 || (n_bins != 0) != (mel_tables != nullptr)) return DASP_ERR_ARG;
+    if (!stft_spec(N, nres, fft, hop, win, eps, w_sc, w_lm, w_lin, n_bins, s) || rows > 65535) return DASP_ERR_UNSUPPORTED;
     for (int r = 0; mel_tables && r < nres; ++r)
         if (!mel_tables[r]) return DASP_ERR_ARG;
+    return DASP_OK;
+}
+int stft_forward(int halves, const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials, float* stats,
+                 float* loss, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_lm,
+                 float w_lin, int n_bins, void* stream) {
+    StftSpec s;
+    const int bad = stft_check(pred, target, tw, mel_tables, partials, stats, loss, rows, N, nres, fft, hop, win, eps, w_sc, w_lm, w_lin, n_bins, &s);
+    if (bad) return bad;
     hipStream_t st = (hipStream_t)stream;
     for (int r = 0; r < nres; ++r) {
-        const int TC = frames_per_group(s.r[r].logF);
-        const dim3 grid((unsigned)((s.r[r].frames + TC - 1) / TC), (unsigned)items);
-        const bool big = s.r[r].logF == 13;
-        if (mel_tables) {
-            const float* tab = (const float*)mel_tables[r];
-            if (big) hipLaunchKernelGGL(mrstft_sd_mel_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
-            else hipLaunchKernelGGL(mrstft_sd_mel_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, tab, partials, s, N, r, n_bins);
-        } else {
-            if (big) hipLaunchKernelGGL(mrstft_sd_fwd_kernel<13>, grid, dim3(1024), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
-            else hipLaunchKernelGGL(mrstft_sd_fwd_kernel<12>, grid, dim3(512), 0, st, pred, target, (const f2*)tw, partials, s, N, r);
-        }
+        const float* tab = mel_tables ? (const float*)mel_tables[r] : nullptr;
+        if (halves == 2) mrstft_sd_fwd_launch(pred, target, tw, tab, partials, s, rows, N, r, n_bins, st);
+        else mrstft_fwd_launch(pred, target, tw, tab, partials, s, rows, N, r, n_bins, st);
     }
-    hipLaunchKernelGGL(mrstft_sd_reduce_kernel, dim3((unsigned)(nres * 8)), dim3(1024), 0, st, (const float*)partials, s, items, stats);
-    hipLaunchKernelGGL(mrstft_sd_finalize_kernel, dim3(1), dim3(64), 0, st, s, items, mel_tables ? n_bins : 0, stats, loss);
+    hipLaunchKernelGGL(mrstft_reduce_kernel, dim3((unsigned)(halves * nres * 4)), dim3(1024), 0, st, (const float*)partials, s, rows, stats);
+    hipLaunchKernelGGL(mrstft_finalize_kernel, dim3(1), dim3(64), 0, st, s, rows, n_bins, halves, stats, loss);
     return sl_check();
 }
-int sd_backward_impl(const float* first, const float* second, const void* tw, const void* const* mel_tables, const float* stats, const float* gloss,
-                     float* gfirst, int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_lm,
-                     float w_lin, int n_bins, int wrt_second, void* stream) {
-    if (!first || !second || !tw || !stats || !gloss || !gfirst || items <= 0 || N <= 0) return DASP_ERR_ARG;
+// wrt_target: the same kernels with the two signals swapped (grad_bin)
+int stft_backward(int halves, const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                  const float* gloss, float* grad, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
+                  float w_lm, float w_lin, int n_bins, int wrt_target, void* stream) {
+    if (wrt_target != 0 && wrt_target != 1) return DASP_ERR_ARG;
     StftSpec s;
-    if (!sd_spec(N, nres, fft, hop, win, eps, mel_tables, n_bins, &s, w_sc, w_lm, w_lin)) return DASP_ERR_UNSUPPORTED;
-    if (items > 65535) return DASP_ERR_UNSUPPORTED;
-    for (int r = 0; mel_tables && r < nres; ++r)
-        if (!mel_tables[r]) return DASP_ERR_ARG;
-    if (zero_async(gfirst, (size_t)2 * items * N * sizeof(float), (hipStream_t)stream) != hipSuccess) return sl_check();
+    const int bad = stft_check(pred, target, tw, mel_tables, stats, gloss, grad, rows, N, nres, fft, hop, win, eps, w_sc, w_lm, w_lin, n_bins, &s);
+    if (bad) return bad;
+    const float* first = wrt_target ? target : pred;
+    const float* second = wrt_target ? pred : target;
+    hipStream_t st = (hipStream_t)stream;
+    if (zero_async(grad, (size_t)halves * rows * N * sizeof(float), st) != hipSuccess) return sl_check();
     for (int r = 0; r < nres; ++r) {
         const float* tab = mel_tables ? (const float*)mel_tables[r] : nullptr;
-        if (s.w_lin != 0.f) mrstft_sd_bwd_launch<true>(first, second, tw, tab, stats, gloss, gfirst, s, items, N, r, n_bins, wrt_second, (hipStream_t)stream);
-        else mrstft_sd_bwd_launch<false>(first, second, tw, tab, stats, gloss, gfirst, s, items, N, r, n_bins, wrt_second, (hipStream_t)stream);
+        const bool lin = s.w_lin != 0.f;
+        if (halves == 2) (lin ? mrstft_sd_bwd_launch<true> : mrstft_sd_bwd_launch<false>)(first, second, tw, tab, stats, gloss, grad, s, rows, N, r, n_bins, wrt_target, st);
+        else (lin ? mrstft_bwd_launch<true> : mrstft_bwd_launch<false>)(first, second, tw, tab, stats, gloss, grad, s, rows, N, r, n_bins, wrt_target, st);
     }
     return sl_check();
 }
@@ -1433,54 +1267,46 @@ int sd_backward_impl(const float* first, const float* second, const void* tw, co
 
 extern "C" {
 
-/* floats of `partials` for items stereo pairs of N samples: 2 halves x nres x items x groups x 4; -1 as dasp_mrstft_weighted_partial_floats */
-long dasp_mrstft_sd_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win) {
-    StftSpec s;
-    if (items <= 0 || !sl_spec(N, nres, fft, hop, win, 0.f, &s, 13)) return -1;
-    return 2L * nres * items * s.groups * 4;
+/* floats of `partials` for rows signals of N samples; -1 if the resolutions are not supported (n_fft a power of two in 8..8192,
+ * win <= n_fft, n_fft / 2 < N, at most 8 resolutions; n_bins 0, or 1..min(256, n_fft / 2 + 1) mel filters) */
+long dasp_mrstft_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins) {
+    return partial_floats(1, rows, N, nres, fft, hop, win, n_bins);
 }
-long dasp_mrstft_sd_mel_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins) {
-    StftSpec s;
-    if (items <= 0 || !mel_spec(N, nres, fft, hop, win, 0.f, n_bins, &s)) return -1;
-    return 2L * nres * items * s.groups * 4;
+/* pred, target (rows, N); stats (4 * nres floats, kept for the backward); loss: 1 float. mel_tables: null with n_bins = 0 (linear bins), or
+ * nres device pointers (a host array), table r built by dasp_mel_table_store for fft[r] and n_bins */
+int dasp_mrstft_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials, float* stats,
+                        float* loss, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
+                        float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
+    return stft_forward(1, pred, target, tw, mel_tables, partials, stats, loss, rows, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins,
+                        stream);
+}
+/* grad (rows, N) is overwritten with gloss * d loss / d pred (gloss: device scalar), or with wrt_target = 1 gloss * d loss / d target
+ * (auraloss differentiates both arguments: a consistency loss between two model outputs needs it; the reference's call sites pass the
+ * reference signal there and never ask) */
+int dasp_mrstft_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                         const float* gloss, float* grad, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
+                         float w_sc, float w_log_mag, float w_lin_mag, int n_bins, int wrt_target, void* stream) {
+    return stft_backward(1, pred, target, tw, mel_tables, stats, gloss, grad, rows, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins,
+                         wrt_target, stream);
+}
+/* floats of `partials` for items stereo pairs of N samples: 2 halves x nres x items x groups x 4; -1 as dasp_mrstft_partial_floats */
+long dasp_mrstft_sd_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins) {
+    return items <= 0 ? -1 : partial_floats(2, items, N, nres, fft, hop, win, n_bins);
 }
 /* pred, target (items, 2, N); stats: 8 * nres floats (kept for the backward); loss: 2 floats (sum_loss, diff_loss) */
-int dasp_mrstft_sd_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int items, int N,
-                           int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_log_mag, float w_lin_mag,
-                           void* stream) {
-    return sd_forward_impl(pred, target, tw, nullptr, partials, stats, loss, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, 0, stream);
+int dasp_mrstft_sd_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials, float* stats,
+                           float* loss, int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
+                           float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
+    return stft_forward(2, pred, target, tw, mel_tables, partials, stats, loss, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins,
+                        stream);
 }
-/* gpred (items, 2, N) is overwritten with gloss[0] d sum_loss / d pred + gloss[1] d diff_loss / d pred (gloss: two device floats) */
-int dasp_mrstft_sd_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gpred, int items,
-                            int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_log_mag,
-                            float w_lin_mag, void* stream) {
-    return sd_backward_impl(pred, target, tw, nullptr, stats, gloss, gpred, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, 0, 0, stream);
-}
-int dasp_mrstft_sd_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gtarget,
-                                   int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
-                                   float w_log_mag, float w_lin_mag, void* stream) {
-    return sd_backward_impl(target, pred, tw, nullptr, stats, gloss, gtarget, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, 0, 1, stream);
-}
-int dasp_mrstft_sd_mel_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials, float* stats,
-                               float* loss, int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
-                               float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
-    if (!mel_tables) return DASP_ERR_ARG;
-    return sd_forward_impl(pred, target, tw, mel_tables, partials, stats, loss, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins,
-                           stream);
-}
-int dasp_mrstft_sd_mel_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
-                                const float* gloss, float* gpred, int items, int N, int nres, const int* fft, const int* hop, const int* win,
-                                float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
-    if (!mel_tables) return DASP_ERR_ARG;
-    return sd_backward_impl(pred, target, tw, mel_tables, stats, gloss, gpred, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins, 0,
-                            stream);
-}
-int dasp_mrstft_sd_mel_backward_target(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
-                                       const float* gloss, float* gtarget, int items, int N, int nres, const int* fft, const int* hop, const int* win,
-                                       float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream) {
-    if (!mel_tables) return DASP_ERR_ARG;
-    return sd_backward_impl(target, pred, tw, mel_tables, stats, gloss, gtarget, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins, 1,
-                            stream);
+/* grad (items, 2, N) is overwritten with gloss[0] d sum_loss / d x + gloss[1] d diff_loss / d x, x = pred or (wrt_target = 1) target
+ * (gloss: two device floats) */
+int dasp_mrstft_sd_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                            const float* gloss, float* grad, int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
+                            float w_sc, float w_log_mag, float w_lin_mag, int n_bins, int wrt_target, void* stream) {
+    return stft_backward(2, pred, target, tw, mel_tables, stats, gloss, grad, items, N, nres, fft, hop, win, eps, w_sc, w_log_mag, w_lin_mag, n_bins,
+                         wrt_target, stream);
 }
 
 }  // extern "C"

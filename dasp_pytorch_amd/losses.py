@@ -5,7 +5,9 @@ w_sc * spectral convergence + w_log_mag * log-magnitude L1 + w_lin_mag * linear-
 perceptual_weighting=True both signals first go through auraloss's 101-tap A-weighting FIR; with scale="mel", n_bins and sample_rate
 the three terms are taken on mel-scaled magnitudes W |X| (librosa's Slaney filterbank, mel_filterbank below), which is also what
 MelSTFTLoss computes. SumAndDifferenceSTFTLoss is that loss on the sum and on the difference of a stereo pair, from kernels whose workgroups own
-both channels of an item. Both arguments receive gradients.
+both channels of an item. Both arguments receive gradients. The two losses are one forward and one backward body (_stft_forward,
+_stft_backward) over the entry points dasp_mrstft_* and dasp_mrstft_sd_*, which take the term weights, n_bins (0: linear bins) with the
+mel tables, and in the backward which argument to differentiate.
 
 The time-domain half of auraloss (auraloss.time: ESRLoss, DCLoss, LogCoshLoss, SNRLoss, SISDRLoss, SDSDRLoss) and the MSE term of the
 reference's examples/virtual_analog.py:299,324-326 are one weighted sum, time_domain_loss, from one moment pass over both signals
@@ -146,246 +148,180 @@ def _mel_options(what, options, fft_sizes):
     return nb, sr
 
 
+def _device_constant(cache, limit, key, device, build):
+    """A device constant, one per (key, device, stream): build() allocates it and launches the kernel that writes it from its arguments.
+    Inside a HIP-graph capture it is built fresh and not kept: memory allocated while capturing belongs to that graph's pool, and the
+    fill kernel only runs on replay (the same rule as ops._filter_spectrum); filled from arguments, it is then a kernel node, not a copy
+    from host memory. Keyed by stream as well: the fill is ordered only against work on the stream it was launched on. A full cache is
+    cleared."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    key = key + (device.index, int(torch.cuda.current_stream(device).cuda_stream))
+    if not capturing and key in cache:
+        return cache[key]
+    t = build()
+    if not capturing:
+        if len(cache) >= limit:
+            cache.clear()
+        cache[key] = t
+    return t
+
+
+_TW, _MEL_DEV, _FIR_DEV = {}, {}, {}
+
+
+def _twiddles(device):
+    """The 4096-entry twiddle table (dasp_mrstft_table)."""
+    def build():
+        tw = torch.empty(2 * 4096, dtype=torch.float32, device=device)
+        call("dasp_mrstft_table", ptr(tw), stream())
+        return tw
+    return _device_constant(_TW, 16, (), device, build)
+
+
+def _fir_taps(host, device):
+    """Host float32 taps on the device (dasp_fir_taps_store)."""
+    def build():
+        taps = torch.empty(len(host), dtype=torch.float32, device=device)
+        call("dasp_fir_taps_store", ptr(taps), host.ctypes.data_as(ctypes.c_void_p), len(host), stream())
+        return taps
+    return _device_constant(_FIR_DEV, 16, (host.tobytes(),), device, build)
+
+
+def _mel_table(sample_rate, n_fft, n_bins, device):
+    """One resolution's mel table (per bin: first filter and two weights; per filter: first bin and bin count), built on the device in
+    fp64 from the edge frequencies (dasp_mel_table_store)."""
+    def build():
+        nfl = _lib.lib().dasp_mel_table_floats(int(n_fft), int(n_bins))
+        if nfl < 0:
+            raise _lib.DaspHipError(f"unsupported mel table: n_fft={n_fft}, n_bins={n_bins}")
+        edges = mel_edges(float(sample_rate), int(n_bins))
+        tab = torch.empty(nfl, dtype=torch.float32, device=device)
+        call("dasp_mel_table_store", ptr(tab), edges.ctypes.data_as(ctypes.c_void_p), float(sample_rate), int(n_fft), int(n_bins), stream())
+        return tab
+    return _device_constant(_MEL_DEV, 64, (float(sample_rate), int(n_fft), int(n_bins)), device, build)
+
+
+def _pair_rows(inp, target, what):
+    """The entry checks of a loss on two signals (both on one GPU, a dtype the float32 kernels take, one shape), then both as
+    contiguous float32 (rows, seq_len). The shape check is _MRSTFTFunction's: the other callers have compared the shapes before their
+    device checks (_check_pair, _sum_diff) and cannot fail it."""
+    _lib.require_device(inp, "input")
+    _lib.require_device(target, "target")
+    _lib.require_same_device(inp, target=target)
+    from .ops64 import require_fp32_ok
+    require_fp32_ok(inp, what)
+    if inp.shape != target.shape:
+        raise RuntimeError(f"input {tuple(inp.shape)} and target {tuple(target.shape)} must have the same shape")
+    N = inp.shape[-1]
+    return tuple(x.detach().reshape(-1, N).to(torch.float32).contiguous() for x in (inp, target))
+
+
+def _fir_pair(name, a, b, taps):
+    """dasp_fir_same_forward or dasp_fir_same_adjoint (name) in one launch on whichever of the (rows, N) tensors a, b exist -> (a, b)
+    filtered, None where there was None."""
+    live = [x for x in (a, b) if x is not None]
+    if not live:
+        return a, b
+    outs = [torch.empty_like(x) for x in live]
+    rows, N = live[0].shape
+    call(name, ptr(live[0]), ptr(live[1] if len(live) > 1 else None), ptr(outs[0]), ptr(outs[1] if len(outs) > 1 else None), ptr(taps),
+         taps.numel(), rows, N, stream())
+    outs = iter(outs)
+    return tuple(next(outs) if x is not None else None for x in (a, b))
+
+
+def _as_arguments(g, gt, shape, dtype, tdtype):
+    """A pair of float32 row tensors (outputs or gradients, None allowed) in the shape and the dtypes of the two arguments."""
+    return (g.reshape(shape).to(dtype) if g is not None else None), (gt.reshape(shape).to(tdtype) if gt is not None else None)
+
+
+# the two layouts of the STFT loss: (entry-point prefix, signal rows per unit the kernels own, shape of the loss, name in error messages);
+# the library keeps 4 stats per resolution and loss
+_MONO = ("dasp_mrstft_", 1, (), "MultiResolutionSTFTLoss")
+_STEREO = ("dasp_mrstft_sd_", 2, (2,), "SumAndDifferenceSTFTLoss")
+
+
+def _stft_forward(ctx, layout, inp, target, res, eps, opts, mel):
+    """opts: None or (w_sc, w_log_mag, w_lin_mag, sample_rate or None), None meaning (1, 1, 0, None); with a sample rate the A-weighting
+    FIR goes in front (per channel row: it is linear, the sum and difference are formed behind it) and the STFTs and the backward see
+    the filtered pair. mel: None or (n_bins, sample_rate), the terms on mel-scaled magnitudes."""
+    prefix, halves, loss_shape, what = layout
+    p32, t32 = _pair_rows(inp, target, what)
+    rows, N = p32.shape
+    units, nres = rows // halves, len(res)
+    arr = [(ctypes.c_int * nres)(*[int(r[i]) for r in res]) for i in range(3)]
+    *wts, sr = opts if opts is not None else (1.0, 1.0, 0.0, None)
+    nb = 0 if mel is None else int(mel[0])
+    nfl = getattr(_lib.lib(), prefix + "partial_floats")(units, N, nres, *arr, nb)
+    if nfl < 0:
+        raise _lib.DaspHipError("unsupported STFT resolutions (fft a power of two in 8..8192, win <= fft, fft / 2 < seq_len, <= 8 of them"
+                                + ("" if mel is None else f"; n_bins <= {MEL_MAX_BINS} and <= fft / 2 + 1") + ")")
+    dev = inp.device
+    with torch.cuda.device(dev):
+        tw = _twiddles(dev)
+        taps = None
+        if sr is not None:
+            taps = _fir_taps(a_weighting_taps(float(sr)), dev)
+            p32, t32 = _fir_pair("dasp_fir_same_forward", p32, t32, taps)
+        partials = torch.empty(nfl, dtype=torch.float32, device=dev)
+        stats = torch.empty(4 * halves * nres, dtype=torch.float32, device=dev)
+        loss = torch.empty(loss_shape, dtype=torch.float32, device=dev)
+        tables, tabs = (), None
+        if mel is not None:
+            tables = tuple(_mel_table(mel[1], int(r[0]), nb, dev) for r in res)
+            tabs = (ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables])
+        call(prefix + "forward", ptr(p32), ptr(t32), ptr(tw), tabs, ptr(partials), ptr(stats), ptr(loss), units, N, nres, *arr, float(eps), *wts,
+             nb, stream())
+    ctx.save_for_backward(p32, t32, stats, tw, taps, *tables)
+    ctx.cfg = (prefix, units, N, nres, arr, float(eps), wts, nb, inp.shape, inp.dtype, target.dtype)
+    return loss.to(inp.dtype)
+
+
+def _stft_backward(ctx, gloss):
+    """gloss: the upstream gradients as float32, one per loss. One call per requested gradient (auraloss differentiates both arguments: a
+    consistency loss between two model outputs), then both through the A-weighting FIR's adjoint in one launch."""
+    p32, t32, stats, tw, taps, *tables = ctx.saved_tensors
+    prefix, units, N, nres, arr, eps, wts, nb, shape, dtype, tdtype = ctx.cfg
+    tabs = (ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables]) if tables else None
+    grads = [None, None]
+    with torch.cuda.device(p32.device):
+        gloss = gloss.contiguous()
+        for wrt_target in (0, 1):
+            if ctx.needs_input_grad[wrt_target]:
+                grads[wrt_target] = g = torch.empty_like(p32)
+                call(prefix + "backward", ptr(p32), ptr(t32), ptr(tw), tabs, ptr(stats), ptr(gloss), ptr(g), units, N, nres, *arr, eps, *wts, nb,
+                     wrt_target, stream())
+        if taps is not None:
+            grads = _fir_pair("dasp_fir_same_adjoint", *grads, taps)
+    return _as_arguments(*grads, shape, dtype, tdtype)
+
+
 class _MRSTFTFunction(torch.autograd.Function):
-    """opts: None (the default loss: the unweighted entry points) or (w_sc, w_log_mag, w_lin_mag, sample_rate or None) - the
-    weighted entry points, which also take 8192-point frames, and with a sample rate the A-weighting FIR in front (and its adjoint behind).
-    mel: None or (n_bins, sample_rate) - the mel entry points (scale="mel"), with opts' weights and A-weighting, (1, 1, 0) and none if opts is None."""
+    """The loss of (..., N) signals (dasp_mrstft_*); opts and mel as _stft_forward's."""
 
     @staticmethod
     def forward(ctx, inp, target, res, eps, opts=None, mel=None):
-        _lib.require_device(inp, "input")
-        _lib.require_device(target, "target")
-        _lib.require_same_device(inp, target=target)
-        from .ops64 import require_fp32_ok
-        require_fp32_ok(inp, "MultiResolutionSTFTLoss")
-        if inp.shape != target.shape:
-            raise RuntimeError(f"input {tuple(inp.shape)} and target {tuple(target.shape)} must have the same shape")
-        L = _lib.lib()
-        N = inp.shape[-1]
-        p32 = inp.detach().reshape(-1, N).to(torch.float32).contiguous()
-        t32 = target.detach().reshape(-1, N).to(torch.float32).contiguous()
-        rows = p32.shape[0]
-        nres = len(res)
-        arr = [(ctypes.c_int * nres)(*[int(r[i]) for r in res]) for i in range(3)]
-        if opts is None and (mel is not None or any(int(r[0]) > 4096 for r in res)):
-            opts = (1.0, 1.0, 0.0, None)                # 8192-point frames: only the weighted entry points take them
-        weighted = opts is not None
-        if mel is not None:
-            nfl = L.dasp_mrstft_mel_partial_floats(rows, N, nres, *arr, int(mel[0]))
-        else:
-            nfl = (L.dasp_mrstft_weighted_partial_floats if weighted else L.dasp_mrstft_partial_floats)(rows, N, nres, *arr)
-        if nfl < 0:
-            raise _lib.DaspHipError(f"unsupported STFT resolutions (fft a power of two in 8..{8192 if weighted else 4096}, win <= fft, "
-                                    "fft / 2 < seq_len, <= 8 of them" + ("" if mel is None else f"; n_bins <= {MEL_MAX_BINS} and <= fft / 2 + 1") + ")")
-        dev = inp.device
-        with torch.cuda.device(dev):
-            tw = _twiddles(dev)
-            taps = None
-            if weighted and opts[3] is not None:         # A-weighting of both signals; the STFTs and the backward see the filtered pair
-                taps = _aw_taps(opts[3], dev)
-                pf, tf = torch.empty_like(p32), torch.empty_like(t32)
-                call("dasp_fir_same_forward", ptr(p32), ptr(t32), ptr(pf), ptr(tf), ptr(taps), AW_TAPS, rows, N, stream())
-                p32, t32 = pf, tf
-            partials = torch.empty(nfl, dtype=torch.float32, device=dev)
-            stats = torch.empty(4 * nres, dtype=torch.float32, device=dev)
-            loss = torch.empty((), dtype=torch.float32, device=dev)
-            tables = ()
-            if mel is not None:
-                tables = tuple(_mel_table(mel[1], int(r[0]), int(mel[0]), dev) for r in res)
-                tabs = (ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables])
-                call("dasp_mrstft_mel_forward", ptr(p32), ptr(t32), ptr(tw), tabs, ptr(partials), ptr(stats), ptr(loss), rows, N, nres, *arr,
-                     float(eps), *opts[:3], int(mel[0]), stream())
-            elif weighted:
-                call("dasp_mrstft_weighted_forward", ptr(p32), ptr(t32), ptr(tw), ptr(partials), ptr(stats), ptr(loss), rows, N, nres, *arr, float(eps),
-                     *opts[:3], stream())
-            else:
-                call("dasp_mrstft_forward", ptr(p32), ptr(t32), ptr(tw), ptr(partials), ptr(stats), ptr(loss), rows, N, nres, *arr, float(eps), stream())
-        ctx.save_for_backward(p32, t32, stats, tw, taps, *tables)
-        ctx.nbins = None if mel is None else int(mel[0])
-        ctx.cfg = (rows, N, nres, arr, float(eps), inp.shape, inp.dtype)
-        ctx.opts = opts
-        ctx.tdtype = target.dtype
-        return loss.to(inp.dtype)
+        return _stft_forward(ctx, _MONO, inp, target, res, eps, opts, mel)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gloss):
-        p32, t32, stats, tw, taps, *tables = ctx.saved_tensors
-        rows, N, nres, arr, eps, shape, dtype = ctx.cfg
-        opts = ctx.opts
-        name, wts = ("dasp_mrstft_weighted_backward", tuple(opts[:3])) if opts is not None else ("dasp_mrstft_backward", ())
-        pre = ()
-        if ctx.nbins is not None:
-            name, wts = "dasp_mrstft_mel_backward", wts + (ctx.nbins,)
-            pre = ((ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables]),)
-        g = gt = None
-        with torch.cuda.device(p32.device):
-            gl = gloss.detach().reshape(1).to(torch.float32).contiguous()
-            if ctx.needs_input_grad[0]:
-                g = torch.empty_like(p32)
-                call(name, ptr(p32), ptr(t32), ptr(tw), *pre, ptr(stats), ptr(gl), ptr(g), rows, N, nres, *arr, eps, *wts, stream())
-            if ctx.needs_input_grad[1]:      # auraloss differentiates both arguments (a consistency loss between two model outputs)
-                gt = torch.empty_like(t32)
-                call(name + "_target", ptr(p32), ptr(t32), ptr(tw), *pre, ptr(stats), ptr(gl), ptr(gt), rows, N, nres, *arr, eps, *wts, stream())
-            if taps is not None and (g is not None or gt is not None):        # through the A-weighting FIR: its adjoint, one launch for both
-                first, second = (g, gt) if g is not None else (gt, None)
-                o1, o2 = torch.empty_like(first), (torch.empty_like(second) if second is not None else None)
-                call("dasp_fir_same_adjoint", ptr(first), ptr(second), ptr(o1), ptr(o2), ptr(taps), AW_TAPS, rows, N, stream())
-                g, gt = (o1, o2) if g is not None else (None, o1)
-        if g is not None:
-            g = g.reshape(shape).to(dtype)
-        if gt is not None:
-            gt = gt.reshape(shape).to(ctx.tdtype)
-        return g, gt, None, None, None, None
+        return _stft_backward(ctx, gloss.detach().reshape(1).to(torch.float32)) + (None,) * 4
 
 
 class _SumDiffFunction(torch.autograd.Function):
-    """(sum_loss, diff_loss) of (bs, 2, N) signals from the item-owned kernels (dasp_mrstft_sd_*): opts and mel as _MRSTFTFunction's. The
+    """(sum_loss, diff_loss) of (bs, 2, N) signals from the item-owned kernels (dasp_mrstft_sd_*); opts and mel as _stft_forward's. The
     backward hands the kernels the two upstream gradients as a two-element gloss, so either output may be differentiated alone."""
 
     @staticmethod
     def forward(ctx, inp, target, res, eps, opts=None, mel=None):
-        _lib.require_device(inp, "input")
-        _lib.require_device(target, "target")
-        _lib.require_same_device(inp, target=target)
-        from .ops64 import require_fp32_ok
-        require_fp32_ok(inp, "SumAndDifferenceSTFTLoss")
-        L = _lib.lib()
-        bs, _, N = inp.shape
-        p32 = inp.detach().reshape(2 * bs, N).to(torch.float32).contiguous()
-        t32 = target.detach().reshape(2 * bs, N).to(torch.float32).contiguous()
-        nres = len(res)
-        arr = [(ctypes.c_int * nres)(*[int(r[i]) for r in res]) for i in range(3)]
-        if opts is None:
-            opts = (1.0, 1.0, 0.0, None)
-        if mel is not None:
-            nfl = L.dasp_mrstft_sd_mel_partial_floats(bs, N, nres, *arr, int(mel[0]))
-        else:
-            nfl = L.dasp_mrstft_sd_partial_floats(bs, N, nres, *arr)
-        if nfl < 0:
-            raise _lib.DaspHipError("unsupported STFT resolutions (fft a power of two in 8..8192, win <= fft, fft / 2 < seq_len, <= 8 of them"
-                                    + ("" if mel is None else f"; n_bins <= {MEL_MAX_BINS} and <= fft / 2 + 1") + ")")
-        dev = inp.device
-        with torch.cuda.device(dev):
-            tw = _twiddles(dev)
-            taps = None
-            if opts[3] is not None:                      # the FIR is linear: per channel here, the sum and difference are formed behind it
-                taps = _aw_taps(opts[3], dev)
-                pf, tf = torch.empty_like(p32), torch.empty_like(t32)
-                call("dasp_fir_same_forward", ptr(p32), ptr(t32), ptr(pf), ptr(tf), ptr(taps), AW_TAPS, 2 * bs, N, stream())
-                p32, t32 = pf, tf
-            partials = torch.empty(nfl, dtype=torch.float32, device=dev)
-            stats = torch.empty(8 * nres, dtype=torch.float32, device=dev)
-            losses = torch.empty(2, dtype=torch.float32, device=dev)
-            tables = ()
-            if mel is not None:
-                tables = tuple(_mel_table(mel[1], int(r[0]), int(mel[0]), dev) for r in res)
-                tabs = (ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables])
-                call("dasp_mrstft_sd_mel_forward", ptr(p32), ptr(t32), ptr(tw), tabs, ptr(partials), ptr(stats), ptr(losses), bs, N, nres, *arr,
-                     float(eps), *opts[:3], int(mel[0]), stream())
-            else:
-                call("dasp_mrstft_sd_forward", ptr(p32), ptr(t32), ptr(tw), ptr(partials), ptr(stats), ptr(losses), bs, N, nres, *arr, float(eps),
-                     *opts[:3], stream())
-        ctx.save_for_backward(p32, t32, stats, tw, taps, *tables)
-        ctx.nbins = None if mel is None else int(mel[0])
-        ctx.cfg = (bs, N, nres, arr, float(eps), inp.shape, inp.dtype)
-        ctx.wts = tuple(opts[:3])
-        ctx.tdtype = target.dtype
-        out = losses.to(inp.dtype)
-        return out[0], out[1]
+        return tuple(_stft_forward(ctx, _STEREO, inp, target, res, eps, opts, mel))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gsum, gdiff):
-        p32, t32, stats, tw, taps, *tables = ctx.saved_tensors
-        bs, N, nres, arr, eps, shape, dtype = ctx.cfg
-        name, wts, pre = "dasp_mrstft_sd_backward", ctx.wts, ()
-        if ctx.nbins is not None:
-            name, wts = "dasp_mrstft_sd_mel_backward", wts + (ctx.nbins,)
-            pre = ((ctypes.c_void_p * nres)(*[t.data_ptr() for t in tables]),)
-        g = gt = None
-        with torch.cuda.device(p32.device):
-            gl = torch.stack((gsum.detach().reshape(()), gdiff.detach().reshape(()))).to(torch.float32).contiguous()
-            if ctx.needs_input_grad[0]:
-                g = torch.empty_like(p32)
-                call(name, ptr(p32), ptr(t32), ptr(tw), *pre, ptr(stats), ptr(gl), ptr(g), bs, N, nres, *arr, eps, *wts, stream())
-            if ctx.needs_input_grad[1]:
-                gt = torch.empty_like(t32)
-                call(name + "_target", ptr(p32), ptr(t32), ptr(tw), *pre, ptr(stats), ptr(gl), ptr(gt), bs, N, nres, *arr, eps, *wts, stream())
-            if taps is not None and (g is not None or gt is not None):
-                first, second = (g, gt) if g is not None else (gt, None)
-                o1, o2 = torch.empty_like(first), (torch.empty_like(second) if second is not None else None)
-                call("dasp_fir_same_adjoint", ptr(first), ptr(second), ptr(o1), ptr(o2), ptr(taps), AW_TAPS, 2 * bs, N, stream())
-                g, gt = (o1, o2) if g is not None else (None, o1)
-        if g is not None:
-            g = g.reshape(shape).to(dtype)
-        if gt is not None:
-            gt = gt.reshape(shape).to(ctx.tdtype)
-        return g, gt, None, None, None, None
-
-
-_TW = {}
-
-
-def _twiddles(device):
-    """The 4096-entry twiddle table, one per (device, stream). Inside a HIP-graph capture the table is built fresh and not kept: memory
-    allocated while capturing belongs to that graph's pool, and its fill kernel only runs on replay (the same rule as
-    ops._filter_spectrum). Keyed by stream as well: the fill is ordered only against work on the stream it was launched on."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (device.type, device.index, int(torch.cuda.current_stream(device).cuda_stream))
-    if not capturing and key in _TW:
-        return _TW[key]
-    tw = torch.empty(2 * 4096, dtype=torch.float32, device=device)
-    call("dasp_mrstft_table", ptr(tw), stream())
-    if not capturing:
-        if len(_TW) >= 16:
-            _TW.clear()
-        _TW[key] = tw
-    return tw
-
-
-_AW_DEV = {}
-
-
-def _aw_taps(sample_rate, device):
-    """The A-weighting taps on the device, one copy per (sample_rate, device, stream), under _twiddles' capture rule. They are written by
-    a kernel that gets them as arguments (dasp_fir_taps_store), so building them inside a capture needs no copy from host memory."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (float(sample_rate), device.index, int(torch.cuda.current_stream(device).cuda_stream))
-    if not capturing and key in _AW_DEV:
-        return _AW_DEV[key]
-    host = a_weighting_taps(float(sample_rate))
-    taps = torch.empty(AW_TAPS, dtype=torch.float32, device=device)
-    call("dasp_fir_taps_store", ptr(taps), host.ctypes.data_as(ctypes.c_void_p), AW_TAPS, stream())
-    if not capturing:
-        if len(_AW_DEV) >= 16:
-            _AW_DEV.clear()
-        _AW_DEV[key] = taps
-    return taps
-
-
-_MEL_DEV = {}
-
-
-def _mel_table(sample_rate, n_fft, n_bins, device):
-    """One resolution's mel table on the device (per bin: first filter and two weights; per filter: first bin and bin count), one per
-    (sample_rate, n_fft, n_bins, device, stream) under _twiddles' capture rule. A kernel builds it in fp64 from the edge frequencies it
-    gets as arguments (dasp_mel_table_store), so inside a capture it is a kernel node, not a copy from host memory."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (float(sample_rate), int(n_fft), int(n_bins), device.index, int(torch.cuda.current_stream(device).cuda_stream))
-    if not capturing and key in _MEL_DEV:
-        return _MEL_DEV[key]
-    nfl = _lib.lib().dasp_mel_table_floats(int(n_fft), int(n_bins))
-    if nfl < 0:
-        raise _lib.DaspHipError(f"unsupported mel table: n_fft={n_fft}, n_bins={n_bins}")
-    edges = mel_edges(float(sample_rate), int(n_bins))
-    tab = torch.empty(nfl, dtype=torch.float32, device=device)
-    call("dasp_mel_table_store", ptr(tab), edges.ctypes.data_as(ctypes.c_void_p), float(sample_rate), int(n_fft), int(n_bins), stream())
-    if not capturing:
-        if len(_MEL_DEV) >= 64:
-            _MEL_DEV.clear()
-        _MEL_DEV[key] = tab
-    return tab
+        gloss = torch.stack((gsum.detach().reshape(()), gdiff.detach().reshape(()))).to(torch.float32)
+        return _stft_backward(ctx, gloss) + (None,) * 4
 
 
 class MultiResolutionSTFTLoss(torch.nn.Module):
@@ -535,18 +471,10 @@ class _TimeDomainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inp, target, cfg):
-        _lib.require_device(inp, "input")
-        _lib.require_device(target, "target")
-        _lib.require_same_device(inp, target=target)
-        from .ops64 import require_fp32_ok
-        require_fp32_ok(inp, "time_domain_loss")
+        p32, t32 = _pair_rows(inp, target, "time_domain_loss")
+        rows, N = p32.shape
         w, a, eps, zero_mean, red = cfg
-        L = _lib.lib()
-        N = inp.shape[-1]
-        p32 = inp.detach().reshape(-1, N).to(torch.float32).contiguous()
-        t32 = target.detach().reshape(-1, N).to(torch.float32).contiguous()
-        rows = p32.shape[0]
-        nd = L.dasp_tdloss_scratch_doubles(rows, N)
+        nd = _lib.lib().dasp_tdloss_scratch_doubles(rows, N)
         if nd < 0:
             raise _lib.DaspHipError(f"time_domain_loss: {rows} rows of {N} samples are not supported")
         dev = inp.device
@@ -574,11 +502,7 @@ class _TimeDomainFunction(torch.autograd.Function):
                 gt = torch.empty_like(t32) if ctx.needs_input_grad[1] else None
                 call("dasp_tdloss_backward", ptr(p32), ptr(t32), ptr(moments), ptr(gl), ptr(g), ptr(gt), rows, N, *w, a, eps, int(zero_mean), red,
                      stream())
-        if g is not None:
-            g = g.reshape(shape).to(dtype)
-        if gt is not None:
-            gt = gt.reshape(shape).to(tdtype)
-        return g, gt, None
+        return _as_arguments(g, gt, shape, dtype, tdtype) + (None,)
 
 
 def time_domain_loss(input: torch.Tensor, target: torch.Tensor, *, w_esr: float = 0.0, w_dc: float = 0.0, w_log_cosh: float = 0.0,
@@ -667,64 +591,29 @@ class SDSDRLoss(_TimeLoss):
         self.zero_mean = zero_mean
 
 
-_FIR_DEV = {}
-
-
-def _fir_taps(host, device):
-    """Host float32 taps on the device, one copy per (taps, device, stream), under _twiddles' capture rule (as _aw_taps)."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (host.tobytes(), device.index, int(torch.cuda.current_stream(device).cuda_stream))
-    if not capturing and key in _FIR_DEV:
-        return _FIR_DEV[key]
-    taps = torch.empty(len(host), dtype=torch.float32, device=device)
-    call("dasp_fir_taps_store", ptr(taps), host.ctypes.data_as(ctypes.c_void_p), len(host), stream())
-    if not capturing:
-        if len(_FIR_DEV) >= 16:
-            _FIR_DEV.clear()
-        _FIR_DEV[key] = taps
-    return taps
-
-
 class _FIRPairFunction(torch.autograd.Function):
     """Both signals through dasp_fir_same_forward in one launch; the backward is dasp_fir_same_adjoint on the gradients that exist."""
 
     @staticmethod
     def forward(ctx, inp, target, host_taps):
-        _lib.require_device(inp, "input")
-        _lib.require_device(target, "target")
-        _lib.require_same_device(inp, target=target)
-        from .ops64 import require_fp32_ok
-        require_fp32_ok(inp, "FIRFilter")
-        N = inp.shape[-1]
-        p32 = inp.detach().reshape(-1, N).to(torch.float32).contiguous()
-        t32 = target.detach().reshape(-1, N).to(torch.float32).contiguous()
-        rows = p32.shape[0]
+        p32, t32 = _pair_rows(inp, target, "FIRFilter")
         with torch.cuda.device(inp.device):
             taps = _fir_taps(host_taps, inp.device)
-            pf, tf = torch.empty_like(p32), torch.empty_like(t32)
-            call("dasp_fir_same_forward", ptr(p32), ptr(t32), ptr(pf), ptr(tf), ptr(taps), len(host_taps), rows, N, stream())
+            pf, tf = _fir_pair("dasp_fir_same_forward", p32, t32, taps)
         ctx.save_for_backward(taps)
-        ctx.cfg = (len(host_taps), rows, N, inp.shape, inp.dtype, target.dtype)
-        return pf.reshape(inp.shape).to(inp.dtype), tf.reshape(inp.shape).to(target.dtype)
+        ctx.cfg = (p32.shape, inp.shape, inp.dtype, target.dtype)
+        return _as_arguments(pf, tf, inp.shape, inp.dtype, target.dtype)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gp, gt):
         (taps,) = ctx.saved_tensors
-        ntaps, rows, N, shape, dtype, tdtype = ctx.cfg
-        grads = [g.detach().reshape(rows, N).to(torch.float32).contiguous() if need else None
+        rows_shape, shape, dtype, tdtype = ctx.cfg
+        grads = [g.detach().reshape(rows_shape).to(torch.float32).contiguous() if need else None
                  for g, need in zip((gp, gt), ctx.needs_input_grad[:2])]
-        live = [g for g in grads if g is not None]
-        if live:
-            with torch.cuda.device(taps.device):
-                outs = [torch.empty_like(g) for g in live]
-                call("dasp_fir_same_adjoint", ptr(live[0]), ptr(live[1] if len(live) > 1 else None), ptr(outs[0]),
-                     ptr(outs[1] if len(outs) > 1 else None), ptr(taps), ntaps, rows, N, stream())
-            outs = iter(outs)
-            grads = [next(outs) if g is not None else None for g in grads]
-        g0 = grads[0].reshape(shape).to(dtype) if grads[0] is not None else None
-        g1 = grads[1].reshape(shape).to(tdtype) if grads[1] is not None else None
-        return g0, g1, None
+        with torch.cuda.device(taps.device):
+            grads = _fir_pair("dasp_fir_same_adjoint", *grads, taps)
+        return _as_arguments(*grads, shape, dtype, tdtype) + (None,)
 
 
 class FIRFilter(torch.nn.Module):

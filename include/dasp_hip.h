@@ -403,35 +403,27 @@ int dasp_bus_backward(const float* x, const float* send_db, const float* gy, flo
  * Multi-resolution STFT loss, the op downstream of the effect chain in the reference's training loops
  * (auraloss.freq.MultiResolutionSTFTLoss(): examples/style_transfer.py:341,363, auto_eq.py:252, virtual_analog.py:288; auraloss is
  * not vendored by the reference - its published algorithm is restated in oracle/dasp_oracle.py:mrstft_loss).
- * pred, target: (rows, N) fp32.  Resolutions: nres <= 8 triples (fft, hop, win); fft a power of two in 8..4096, win <= fft, fft/2 < N.
- * tw: 4096 complex twiddles from dasp_mrstft_table.  partials: dasp_mrstft_partial_floats floats.  stats: 4*nres floats
- * (forward -> backward).  loss, gloss: device scalars.  gpred = gloss * d loss / d pred (float atomics: summation order only
- * is not deterministic).
+ * pred, target: (rows, N) fp32.  Resolutions: nres <= 8 triples (fft, hop, win); fft a power of two in 8..8192 (8192: one frame per
+ * 1024-thread workgroup), win <= fft, fft/2 < N.  tw: 4096 complex twiddles from dasp_mrstft_table.
+ * Per resolution w_sc * SC + w_log_mag * LOG + w_lin_mag * LIN (auraloss's term weights; LIN = mean ||X| - |Y||), mean over the
+ * resolutions; a weight of exactly 0 leaves its term out of the loss and the gradient; (1, 1, 0) are auraloss's defaults.
+ * n_bins = 0 and mel_tables = NULL: linear bins. n_bins > 0: the terms on mel-scaled magnitudes (below), 1 <= n_bins <= min(256,
+ * fft / 2 + 1) for every resolution, mel_tables a host array of nres non-null device pointers, table r for fft[r]. One without the other,
+ * a null pointer elsewhere or a wrt_target other than 0 or 1: DASP_ERR_ARG before any launch; resolutions, n_bins or weights that are not
+ * supported (and rows > 65535): DASP_ERR_UNSUPPORTED, and -1 from the size query.
+ * partials: dasp_mrstft_partial_floats floats.  stats: 4*nres floats (forward -> backward).  loss, gloss: device scalars, the loss
+ * bit-identical run to run (fixed summation order).  grad (rows, N) is overwritten with gloss * d loss / d pred, or with wrt_target = 1
+ * gloss * d loss / d target (auraloss differentiates both arguments; the same kernels with the signals swapped), through float atomics:
+ * summation order only is not deterministic.
  * ------------------------------------------------------------------------------------------- */
-long dasp_mrstft_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win);
+long dasp_mrstft_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins);
 int dasp_mrstft_table(void* tw, void* stream);
-int dasp_mrstft_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int rows,
-                        int N, int nres, const int* fft, const int* hop, const int* win, float eps, void* stream);
-int dasp_mrstft_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gpred,
-                         int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, void* stream);
-/* the gradient w.r.t. the second signal (auraloss differentiates both): gtarget (rows, N) = gloss * d loss / d target */
-int dasp_mrstft_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
-                                float* gtarget, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
-                                void* stream);
-/* The loss with auraloss's term weights (MultiResolutionSTFTLoss(w_sc=, w_log_mag=, w_lin_mag=)): per resolution
- * w_sc * SC + w_log_mag * LOG + w_lin_mag * LIN, LIN = mean ||X| - |Y||; a weight of exactly 0 leaves its term out of the loss and the
- * gradient. fft a power of two in 8..8192 (8192: one frame per 1024-thread workgroup); otherwise as above, and the same kernels:
- * weights (1, 1, 0) give the unweighted loss. partials: dasp_mrstft_weighted_partial_floats floats (-1: not supported); stats 4*nres. */
-long dasp_mrstft_weighted_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win);
-int dasp_mrstft_weighted_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss,
-                                 int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
-                                 float w_log_mag, float w_lin_mag, void* stream);
-int dasp_mrstft_weighted_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
-                                  float* gpred, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
-                                  float w_sc, float w_log_mag, float w_lin_mag, void* stream);
-int dasp_mrstft_weighted_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
-                                         float* gtarget, int rows, int N, int nres, const int* fft, const int* hop, const int* win,
-                                         float eps, float w_sc, float w_log_mag, float w_lin_mag, void* stream);
+int dasp_mrstft_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials,
+                        float* stats, float* loss, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
+                        float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
+int dasp_mrstft_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                         const float* gloss, float* grad, int rows, int N, int nres, const int* fft, const int* hop, const int* win,
+                         float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, int wrt_target, void* stream);
 /* The perceptual weighting of the loss (auraloss FIRFilter(filter_type="aw", ntaps=101), applied to both signals before the STFTs):
  * y[n] = sum_k taps[k] x[n + k - ntaps/2] over rows of N samples, zeros outside [0, N) (conv1d(x, taps, padding=ntaps/2)); ntaps odd,
  * <= 101; taps on the device. Fixed summation order: bit-identical run to run. dasp_fir_same_forward filters x0 -> y0 and x1 -> y1;
@@ -442,60 +434,34 @@ int dasp_fir_same_forward(const float* x0, const float* x1, float* y0, float* y1
 int dasp_fir_same_adjoint(const float* g0, const float* g1, float* gx0, float* gx1, const float* taps, int ntaps, int rows, int N,
                           void* stream);
 int dasp_fir_taps_store(float* dst, const float* host_taps, int ntaps, void* stream);
-/* The loss on mel-scaled magnitudes (auraloss scale="mel", n_bins; auraloss.freq.MelSTFTLoss): per frame M = W |X| with
+/* Mel-scaled magnitudes (auraloss scale="mel", n_bins; auraloss.freq.MelSTFTLoss): per frame M = W |X| with
  * W = librosa.filters.mel(sr, n_fft, n_mels) (n_bins x (n_fft / 2 + 1), Slaney scale and normalisation, not clamped after the projection),
- * the sums and the mean over rows x frames x n_bins. 1 <= n_bins <= 256 and n_bins <= n_fft / 2 + 1 for every resolution; resolutions as
- * for the weighted entry points (n_fft a power of two in 8..8192); every size query returns -1 otherwise.
- * One device table per resolution (dasp_mel_table_floats floats): per bin the first filter it lies in and its weights in that filter and
+ * the sums and the mean over rows x frames x n_bins.
+ * One device table per resolution (dasp_mel_table_floats floats; -1: n_fft not a power of two in 8..8192 or n_bins outside 1..min(256,
+ * n_fft / 2 + 1)): per bin the first filter it lies in and its weights in that filter and
  * the next, per filter its first bin and bin count. dasp_mel_table_store builds it on the device in fp64 from the n_bins + 2 edge
  * frequencies in Hz (host fp64, increasing, passed on as kernel arguments: capturable into a graph); dasp_mel_table_dense writes the
- * (n_bins, n_fft / 2 + 1) float matrix a table stands for. mel_tables: a host array of nres device pointers, table r for fft[r].
- * The loss value is bit-identical run to run (fixed summation order); the gradients use float atomics as above. */
+ * (n_bins, n_fft / 2 + 1) float matrix a table stands for. */
 long dasp_mel_table_floats(int n_fft, int n_bins);
 int dasp_mel_table_store(float* table, const double* host_edges, double sample_rate, int n_fft, int n_bins, void* stream);
 int dasp_mel_table_dense(const float* table, float* dense, int n_fft, int n_bins, void* stream);
-long dasp_mrstft_mel_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins);
-int dasp_mrstft_mel_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials,
-                            float* stats, float* loss, int rows, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
-                            float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
-int dasp_mrstft_mel_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
-                             const float* gloss, float* gpred, int rows, int N, int nres, const int* fft, const int* hop, const int* win,
-                             float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
-int dasp_mrstft_mel_backward_target(const float* pred, const float* target, const void* tw, const void* const* mel_tables,
-                                    const float* stats, const float* gloss, float* gtarget, int rows, int N, int nres, const int* fft,
-                                    const int* hop, const int* win, float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins,
-                                    void* stream);
 /* The sum / difference loss of a stereo pair (auraloss.freq.SumAndDifferenceSTFTLoss): the loss above on L + R and on L - R as two
  * separate losses, each with its own sums and its own means over the `items` rows of its half, from one launch per resolution and direction (a workgroup owns both channels of an item).
- * pred, target: (items, 2, N) fp32, channel rows interleaved (row 2 b = left, 2 b + 1 = right of item b). Resolutions, weights and n_bins as
- * for the weighted / mel entry points (n_fft a power of two in 8..8192; every size runs the generic-geometry kernels, one workgroup per
+ * pred, target: (items, 2, N) fp32, channel rows interleaved (row 2 b = left, 2 b + 1 = right of item b). Resolutions, weights, n_bins,
+ * mel_tables, wrt_target and the refusals as for dasp_mrstft_* (every size runs the generic-geometry kernels, one workgroup per
  * frame group of an item). partials: dasp_mrstft_sd_partial_floats floats (2 x nres x items x groups x 4; -1: not supported).
  * stats: 8 * nres floats, [(half * nres + res) * 4 + c], half 0 = sum, 1 = difference (forward -> backward). loss: 2 floats, (sum_loss,
- * diff_loss), bit-identical run to run. gloss: 2 device floats, d objective / d sum_loss and d objective / d diff_loss; gpred / gtarget
- * (items, 2, N) is overwritten with gloss[0] d sum_loss / d x + gloss[1] d diff_loss / d x: both halves' gradient spectra go back to
- * channels in the frequency domain and through one packed inverse transform, one float atomic per sample, frame and channel.
- * Null pointers: DASP_ERR_ARG before any launch. */
-long dasp_mrstft_sd_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win);
-int dasp_mrstft_sd_forward(const float* pred, const float* target, const void* tw, float* partials, float* stats, float* loss, int items,
-                           int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc, float w_log_mag,
-                           float w_lin_mag, void* stream);
-int dasp_mrstft_sd_backward(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss, float* gpred,
-                            int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps, float w_sc,
-                            float w_log_mag, float w_lin_mag, void* stream);
-int dasp_mrstft_sd_backward_target(const float* pred, const float* target, const void* tw, const float* stats, const float* gloss,
-                                   float* gtarget, int items, int N, int nres, const int* fft, const int* hop, const int* win, float eps,
-                                   float w_sc, float w_log_mag, float w_lin_mag, void* stream);
-long dasp_mrstft_sd_mel_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins);
-int dasp_mrstft_sd_mel_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials,
-                               float* stats, float* loss, int items, int N, int nres, const int* fft, const int* hop, const int* win,
-                               float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
-int dasp_mrstft_sd_mel_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
-                                const float* gloss, float* gpred, int items, int N, int nres, const int* fft, const int* hop,
-                                const int* win, float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
-int dasp_mrstft_sd_mel_backward_target(const float* pred, const float* target, const void* tw, const void* const* mel_tables,
-                                       const float* stats, const float* gloss, float* gtarget, int items, int N, int nres, const int* fft,
-                                       const int* hop, const int* win, float eps, float w_sc, float w_log_mag, float w_lin_mag,
-                                       int n_bins, void* stream);
+ * diff_loss), bit-identical run to run. gloss: 2 device floats, d objective / d sum_loss and d objective / d diff_loss; grad
+ * (items, 2, N) is overwritten with gloss[0] d sum_loss / d x + gloss[1] d diff_loss / d x, x = pred or target: both halves' gradient
+ * spectra go back to channels in the frequency domain and through one packed inverse transform, one float atomic per sample, frame and
+ * channel. */
+long dasp_mrstft_sd_partial_floats(long items, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins);
+int dasp_mrstft_sd_forward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, float* partials,
+                           float* stats, float* loss, int items, int N, int nres, const int* fft, const int* hop, const int* win,
+                           float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, void* stream);
+int dasp_mrstft_sd_backward(const float* pred, const float* target, const void* tw, const void* const* mel_tables, const float* stats,
+                            const float* gloss, float* grad, int items, int N, int nres, const int* fft, const int* hop, const int* win,
+                            float eps, float w_sc, float w_log_mag, float w_lin_mag, int n_bins, int wrt_target, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Time-domain losses.  Replaces auraloss.time.ESRLoss, DCLoss, LogCoshLoss, SNRLoss, SISDRLoss and SDSDRLoss (auraloss 0.4.0; not

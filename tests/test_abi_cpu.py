@@ -92,7 +92,7 @@ def test_argument_errors_without_gpu():
     assert L.dasp_lfilter_work_doubles(4, 100, 5, 7) == 2 * 15 * 4 * 7 + 4 * 7 * 7               # the caller's chunk length: 15 chunks of 7 samples
     # a scratch buffer smaller than the plan needs is refused before anything is launched (the pointers are never dereferenced on the host)
     assert L.dasp_lfilter_forward(8, 8, 8, 1, 8, None, 8, 10, 4, 262144, 5, 0, 0, None) == -1
-    assert L.dasp_mrstft_backward_target(None, None, None, None, None, None, 1, 4096, 0, None, None, None, 1e-8, None) == -1
+    assert L.dasp_mrstft_backward(None, None, None, None, None, None, None, 1, 4096, 0, None, None, None, 1e-8, 1.0, 1.0, 0.0, 0, 1, None) == -1
 
 
 def test_product_has_no_cpu_path():

@@ -129,7 +129,7 @@ def _torch_mrstft(p, t, resolutions, eps=1e-8):
 
 @pytest.mark.parametrize("res", [((1024, 120, 600), (2048, 240, 1200), (512, 50, 240)), ((256, 64, 256),)])
 def test_gradient_for_both_arguments(D, res):
-    """auraloss differentiates input and target; so does this loss (dasp_mrstft_backward_target: the backward kernels with the two signals
+    """auraloss differentiates input and target; so does this loss (dasp_mrstft_backward with wrt_target = 1: the backward kernels with the two signals
     swapped plus the norm term of the spectral convergence). Both gradients against torch.stft + autograd in float64 on a draw whose
     log-magnitude differences keep their sign (prediction = 1.5 x target + a little noise), and the plain case target.requires_grad =
     False still returns None for it."""

@@ -126,7 +126,7 @@ def test_each_term_alone(D, term, fs):
                                    (30001, ((8192, 1000, 8191), (4096, 999, 4000), (2048, 333, 2048)))])
 def test_8192_point_frames(D, N, res):
     """n_fft = 8192 (one frame per 1024-thread workgroup): windows shorter than the frame, hops that do not divide N, N just above
-    4096 (the reflect-padding limit), beside other resolutions; default weights (they take the weighted entry points). Generic inputs
+    4096 (the reflect-padding limit), beside other resolutions; default weights. Generic inputs
     at 1e-2, the 1.5x construction at 3e-4 (test_gpu_losses.py's bound for thousands of bins per frame)."""
     a, b = generic((2, 1, N), N)
     check(f"8192 generic N={N}", gpu_loss(D, a, b, res), ref_loss(D, a, b, res), 1e-2)
@@ -227,8 +227,9 @@ def test_auto_eq_training_step(D):
     check("auto_eq slice (2,1,131072)", gpu_loss(D, ys, tsl, ar.EXAMPLE_RESOLUTIONS, **opts), ref_loss(D, ys, tsl, ar.EXAMPLE_RESOLUTIONS, **opts), 1e-2)
 
 
-def test_weighted_entry_points_at_unit_weights_are_the_default_loss(D):
-    """dasp_mrstft_weighted_forward with weights (1, 1, 0) runs the default loss's kernels: the same loss bit for bit."""
+def test_opts_none_is_unit_weights(D):
+    """opts=None (what the modules carry for auraloss's defaults) and the explicit weights (1, 1, 0) with no sample rate are the same
+    call of dasp_mrstft_forward: the same loss bit for bit."""
     from dasp_pytorch_amd import losses
     a, b = generic((2, 2, 20000), 4)
     res = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240), (256, 64, 256))

@@ -179,12 +179,12 @@ def test_empty_filters_are_refused_with_the_log_term():
 def test_size_queries_of_the_mel_exports():
     L = _lib.lib()
     arr = lambda *v: (ctypes.c_int * len(v))(*v)
-    q = L.dasp_mrstft_mel_partial_floats
+    q = L.dasp_mrstft_partial_floats                                                    # the last argument: n_bins, 0 for linear bins
     assert q(4, 20000, 3, arr(1024, 2048, 8192), arr(256, 512, 2048), arr(1024, 2048, 8192), 128) == \
-        L.dasp_mrstft_weighted_partial_floats(4, 20000, 3, arr(1024, 2048, 8192), arr(256, 512, 2048), arr(1024, 2048, 8192)) > 0
+        q(4, 20000, 3, arr(1024, 2048, 8192), arr(256, 512, 2048), arr(1024, 2048, 8192), 0) > 0
     assert q(1, 200, 1, arr(8), arr(4), arr(8), 5) > 0                                  # n_bins = n_fft / 2 + 1
     assert q(1, 200, 1, arr(8), arr(4), arr(8), 6) == -1                                # more filters than bins
-    assert q(1, 20000, 1, arr(1024), arr(256), arr(1024), 0) == -1
+    assert q(1, 20000, 1, arr(1024), arr(256), arr(1024), -1) == -1                     # 0 filters is the linear-bin query; fewer are refused
     assert q(1, 20000, 1, arr(1024), arr(256), arr(1024), 257) == -1
     assert q(1, 20000, 2, arr(1024, 64), arr(256, 16), arr(1024, 64), 40) == -1         # one resolution too short for 40 filters
     assert q(1, 20000, 1, arr(1000), arr(256), arr(1000), 40) == -1                     # not a power of two
@@ -196,5 +196,5 @@ def test_size_queries_of_the_mel_exports():
     assert L.dasp_mel_table_floats(8192, 256) == 3 * 4097 + 2 * 256
     for bad in ((1024, 0), (1024, 257), (8, 6), (1000, 40), (16384, 128), (4, 2)):
         assert L.dasp_mel_table_floats(*bad) == -1
-    assert L.dasp_mrstft_mel_forward(None, None, None, None, None, None, None, 1, 4096, 1, arr(1024), arr(256), arr(1024), 1e-8, 1.0, 1.0, 0.0, 64, None) == -1
+    assert L.dasp_mrstft_forward(None, None, None, None, None, None, None, 1, 4096, 1, arr(1024), arr(256), arr(1024), 1e-8, 1.0, 1.0, 0.0, 64, None) == -1
     assert L.dasp_mel_table_store(None, None, 44100.0, 1024, 64, None) == -1

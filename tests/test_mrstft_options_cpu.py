@@ -91,7 +91,7 @@ def test_unknown_keywords_and_extra_positionals_are_type_errors():
 
 
 def test_keywords_and_their_defaults():
-    """auraloss's defaults select the unweighted loss (dasp_mrstft_forward / _backward); `device` is accepted and ignored; the 4th positional
+    """auraloss's defaults are carried as None (weights (1, 1, 0), no sample rate); `device` is accepted and ignored; the 4th positional
     argument is still eps; the examples' configuration is carried as (w_sc, w_log_mag, w_lin_mag, sample_rate)."""
     fn = losses.MultiResolutionSTFTLoss(w_sc=1.0, w_log_mag=1.0, w_lin_mag=0.0, w_phs=0.0, sample_rate=None, scale=None, n_bins=None,
                                         perceptual_weighting=False, scale_invariance=False, window="hann_window", reduction="mean",

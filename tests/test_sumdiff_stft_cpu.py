@@ -97,11 +97,12 @@ def test_size_queries():
     fft, hop, win = (1024, 2048, 8192), (256, 512, 2048), (1024, 2048, 8192)
     groups = max(-(-(1 + N // 256) // 4), -(-(1 + N // 512) // 2), 1 + N // 2048)
     assert groups == 20
-    assert L.dasp_mrstft_sd_partial_floats(3, N, 3, _arr(fft), _arr(hop), _arr(win)) == 2 * 3 * 3 * groups * 4
-    assert L.dasp_mrstft_sd_mel_partial_floats(3, N, 3, _arr(fft), _arr(hop), _arr(win), 128) == 2 * 3 * 3 * groups * 4
-    assert L.dasp_mrstft_sd_partial_floats(1, 200, 1, _arr((8,)), _arr((4,)), _arr((8,))) == 2 * 1 * 1 * 1 * 4          # 51 frames: one group of 512
+    q = L.dasp_mrstft_sd_partial_floats                         # the last argument: n_bins, 0 for linear bins
+    assert q(3, N, 3, _arr(fft), _arr(hop), _arr(win), 0) == 2 * 3 * 3 * groups * 4
+    assert q(3, N, 3, _arr(fft), _arr(hop), _arr(win), 128) == 2 * 3 * 3 * groups * 4
+    assert q(1, 200, 1, _arr((8,)), _arr((4,)), _arr((8,)), 0) == 2 * 1 * 1 * 1 * 4          # 51 frames: one group of 512
     # twice the mono query for the 2 x items rows of the same signals
-    assert L.dasp_mrstft_sd_partial_floats(3, N, 3, _arr(fft), _arr(hop), _arr(win)) == L.dasp_mrstft_weighted_partial_floats(6, N, 3, _arr(fft), _arr(hop), _arr(win))
+    assert q(3, N, 3, _arr(fft), _arr(hop), _arr(win), 0) == L.dasp_mrstft_partial_floats(6, N, 3, _arr(fft), _arr(hop), _arr(win), 0)
     for bad in ((3, N, 1, (1000,), (256,), (1000,)),            # not a power of two
                 (3, N, 1, (16384,), (4096,), (16384,)),         # beyond 8192
                 (3, N, 1, (1024,), (256,), (2048,)),            # window longer than the frame
@@ -109,25 +110,37 @@ def test_size_queries():
                 (3, N, 1, (1024,), (0,), (1024,)),
                 (0, N, 1, (1024,), (256,), (1024,))):
         items, n, nres, f, h, w = bad
-        assert L.dasp_mrstft_sd_partial_floats(items, n, nres, _arr(f), _arr(h), _arr(w)) == -1, bad
-        assert L.dasp_mrstft_sd_mel_partial_floats(items, n, nres, _arr(f), _arr(h), _arr(w), 4) == -1, bad
-    assert L.dasp_mrstft_sd_partial_floats(3, N, 9, _arr(fft * 3), _arr(hop * 3), _arr(win * 3)) == -1                  # more than 8 resolutions
-    assert L.dasp_mrstft_sd_partial_floats(3, N, 1, None, None, None) == -1
-    assert L.dasp_mrstft_sd_mel_partial_floats(3, N, 3, _arr(fft), _arr(hop), _arr(win), 257) == -1
-    assert L.dasp_mrstft_sd_mel_partial_floats(3, N, 1, _arr((64,)), _arr((16,)), _arr((64,)), 34) == -1               # n_bins > n_fft / 2 + 1
-    assert L.dasp_mrstft_sd_mel_partial_floats(3, N, 1, _arr((64,)), _arr((16,)), _arr((64,)), 33) == 2 * 3 * (-(-(1 + N // 16) // 64)) * 4
+        assert q(items, n, nres, _arr(f), _arr(h), _arr(w), 0) == -1, bad
+        assert q(items, n, nres, _arr(f), _arr(h), _arr(w), 4) == -1, bad
+    assert q(3, N, 9, _arr(fft * 3), _arr(hop * 3), _arr(win * 3), 0) == -1                  # more than 8 resolutions
+    assert q(3, N, 1, None, None, None, 0) == -1
+    assert q(3, N, 3, _arr(fft), _arr(hop), _arr(win), 257) == -1
+    assert q(3, N, 1, _arr((64,)), _arr((16,)), _arr((64,)), 34) == -1               # n_bins > n_fft / 2 + 1
+    assert q(3, N, 1, _arr((64,)), _arr((16,)), _arr((64,)), 33) == 2 * 3 * (-(-(1 + N // 16) // 64)) * 4
 
 
 def test_null_pointers_are_refused_before_any_launch():
+    """Argument order: pred, target, tw, mel_tables, then partials, stats, loss (forward) or stats, gloss, grad (backward), items, N, nres,
+    fft, hop, win, eps, the three weights, n_bins, (backward: wrt_target,) stream."""
     L = _lib.lib()
     a = _arr((1024,)), _arr((256,)), _arr((1024,))
-    for name in ("dasp_mrstft_sd_forward", "dasp_mrstft_sd_backward", "dasp_mrstft_sd_backward_target"):
-        assert getattr(L, name)(None, None, None, None, None, None, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, None) == -1, name
-    for name in ("dasp_mrstft_sd_mel_forward", "dasp_mrstft_sd_mel_backward", "dasp_mrstft_sd_mel_backward_target"):
-        assert getattr(L, name)(None, None, None, None, None, None, None, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 8, None) == -1, name
+    tabs = (ctypes.c_void_p * 1)(8)
+    for n_bins in (0, 8):
+        assert L.dasp_mrstft_sd_forward(None, None, None, None, None, None, None, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, n_bins, None) == -1
+        for wrt_target in (0, 1):
+            assert L.dasp_mrstft_sd_backward(None, None, None, None, None, None, None, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, n_bins, wrt_target, None) == -1
     # non-null data pointers (never dereferenced on the host) but no table array / no items: still refused without a launch
-    assert L.dasp_mrstft_sd_mel_forward(8, 8, 8, None, 8, 8, 8, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 8, None) == -1
-    assert L.dasp_mrstft_sd_forward(8, 8, 8, 8, 8, 8, 0, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, None) == -1
+    assert L.dasp_mrstft_sd_forward(8, 8, 8, None, 8, 8, 8, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 8, None) == -1
+    assert L.dasp_mrstft_sd_forward(8, 8, 8, None, 8, 8, 8, 0, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 0, None) == -1
+    # for both layouts and directions: n_bins and mel_tables that disagree, and a wrt_target that is neither 0 nor 1
+    for prefix in ("dasp_mrstft_", "dasp_mrstft_sd_"):
+        fwd, bwd = getattr(L, prefix + "forward"), getattr(L, prefix + "backward")
+        assert fwd(8, 8, 8, None, 8, 8, 8, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 8, None) == -1, prefix
+        assert fwd(8, 8, 8, tabs, 8, 8, 8, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 0, None) == -1, prefix
+        assert bwd(8, 8, 8, None, 8, 8, 8, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 8, 0, None) == -1, prefix
+        assert bwd(8, 8, 8, tabs, 8, 8, 8, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 0, 0, None) == -1, prefix
+        assert bwd(8, 8, 8, None, 8, 8, 8, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 0, 2, None) == -1, prefix
+        assert bwd(8, 8, 8, tabs, 8, 8, 8, 1, 4096, 1, *a, 1e-8, 1.0, 1.0, 0.0, 8, 2, None) == -1, prefix
 
 
 def _draw(shape, seed):
@@ -188,7 +201,7 @@ def test_new_kernels_keep_their_registers_and_use_no_scratch(tmp_path):
         get = lambda key: re.search(rf"\.{key}:\s+(\S+)", block).group(1)
         recs[get("name")] = (int(get("vgpr_count")), int(get("private_segment_fixed_size")), int(get("vgpr_spill_count")))
     mine = {k: v for k, v in recs.items() if "mrstft_sd_" in k}
-    assert len(mine) == 14 and len(recs) == 44, (len(mine), len(recs))
+    assert len(mine) == 12 and len(recs) == 41, (len(mine), len(recs))
     for name, (vgprs, scratch, spills) in mine.items():
         assert scratch == 0 and spills == 0, (name, scratch, spills)
         if "ILi13E" in name:
