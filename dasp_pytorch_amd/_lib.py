@@ -103,6 +103,15 @@ SIGNATURES = {
     "dasp_tdloss_scratch_doubles": (_l, [_l, _l]),
     "dasp_tdloss_forward": (_i, [_p] * 6 + [_l, _l] + [_d] * 9 + [_i, _i, _p]),
     "dasp_tdloss_backward": (_i, [_p] * 6 + [_l, _l] + [_d] * 9 + [_i, _i, _p]),
+    "dasp_loudness_kweighting": (_i, [_d, ctypes.POINTER(ctypes.c_double)]),
+    "dasp_loudness_blocks": (_l, [_l, _d]),
+    "dasp_loudness_segments": (_l, [_l, _l]),
+    "dasp_loudness_scratch_doubles": (_l, [_l, _i, _l, _d]),
+    "dasp_loudness_forward": (_i, [_p] * 5 + [_l, _i, _l, _d, _p]),
+    "dasp_loudness_backward": (_i, [_p] * 5 + [_l, _i, _l, _d, _p]),
+    "dasp_peaknorm_scratch_doubles": (_l, [_l, _l]),
+    "dasp_peaknorm_forward": (_i, [_p] * 4 + [_l, _l, _d, _d, _p]),
+    "dasp_peaknorm_backward": (_i, [_p] * 5 + [_l, _l, _d, _d, _p]),
     "dasp_lfilter_work_doubles": (_l, [_i, _l, _i, _l]),
     "dasp_lfilter_forward": (_i, [_p, _p, _p, _i, _p, _p, _p, _l, _i, _l, _i, _i, _l, _p]),
     "dasp_lfilter_backward": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l, _i, _i, _l, _p]),

@@ -1,10 +1,12 @@
 """Drop-in for dasp_pytorch.functional on MI355X: same names, argument order and keyword names
 (dasp_pytorch/functional.py), every effect computed by hand-written HIP kernels (csrc/)."""
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import signal as _signal
 from . import _mt19937
 from . import ops as _ops
+from . import _lib
 from .ops import FILTER_TYPES, BusFunction, DistortionSampleFunction, PannerFunction, WidenerFunction
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
@@ -324,3 +326,145 @@ def _dynamics_from_matrix(mode, x, sample_rate, controls, eps=1e-8, lookahead_sa
     """compressor / expander on the (bs, 6) matrix of controls (columns in the functions' argument order)."""
     from .ops import DynamicsMatrixFunction
     return DynamicsMatrixFunction.apply(x, mode, float(sample_rate), float(eps), int(lookahead_samples), controls)
+
+
+# ---- level metering and normalisation (csrc/loudness.hip) ---------------------------------------------------------------------------------
+def _level_rows(x, what, sample_rate=None, max_chs=None):
+    """Shape, channel count, sample rate and length checks of the level ops, before any device check. -> H (samples per 100 ms) or None."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{what}: x must be a torch.Tensor")
+    if x.dim() != 3:
+        raise ValueError(f"{what}: x must be shaped (bs, chs, seq_len), got {tuple(x.shape)}")
+    bs, chs, seq_len = x.shape
+    if bs < 1 or chs < 1 or seq_len < 1:
+        raise ValueError(f"{what}: x must hold at least one item, channel and sample, got {tuple(x.shape)}")
+    H = None
+    if max_chs is not None:
+        if chs > max_chs:
+            raise ValueError(f"{what}: 1 to {max_chs} channels (L, R, C, Ls, Rs) are supported, got {chs}")
+        fs = float(sample_rate)
+        if not 8000.0 <= fs <= 384000.0:
+            raise ValueError(f"{what}: sample_rate must lie in [8000, 384000], got {sample_rate!r}")
+        H = int(round(0.1 * fs))
+        if seq_len < 4 * H:
+            raise ValueError(f"{what}: seq_len {seq_len} is shorter than one 400 ms block ({4 * H} samples at {sample_rate} Hz)")
+    require_fp32_ok(x, what)
+    _lib.require_device(x)
+    return H
+
+
+def _rows32(x):
+    return x.detach().to(torch.float32).contiguous()
+
+
+class _LoudnessFunction(torch.autograd.Function):
+    """x (bs, chs, N) -> L (bs) LUFS. Forward: filter pass (+ a state pre-pass for few rows) and the gate launch; backward: one filter
+    pass backwards in time over the K-weighted signal the forward call kept."""
+
+    @staticmethod
+    def forward(ctx, x, fs):
+        x32 = _rows32(x)
+        bs, chs, N = x32.shape
+        nd = _lib.lib().dasp_loudness_scratch_doubles(bs, chs, N, fs)
+        nb = _lib.lib().dasp_loudness_blocks(N, fs)
+        if nd < 0 or nb < 0:
+            raise _lib.DaspHipError(f"loudness: {tuple(x32.shape)} at {fs} Hz is not supported")
+        dev, grad = x.device, ctx.needs_input_grad[0]
+        with torch.cuda.device(dev):
+            scratch = torch.empty(nd, dtype=torch.float64, device=dev)
+            L = torch.empty(bs, dtype=torch.float32, device=dev)
+            ysave = torch.empty_like(x32) if grad else None
+            cov = torch.empty(bs * chs * (nb + 3), dtype=torch.float32, device=dev) if grad else None
+            _lib.call("dasp_loudness_forward", _lib.ptr(x32), _lib.ptr(scratch), _lib.ptr(L), _lib.ptr(ysave), _lib.ptr(cov), bs, chs, N, fs, _lib.stream())
+        if grad:
+            ctx.save_for_backward(ysave, cov)
+        ctx.cfg = (fs, nd, x.dtype)
+        return L.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gL):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        ysave, cov = ctx.saved_tensors
+        fs, nd, dtype = ctx.cfg
+        bs, chs, N = ysave.shape
+        with torch.cuda.device(ysave.device):
+            g32 = gL.detach().reshape(-1).to(torch.float32).contiguous()
+            scratch = torch.empty(nd, dtype=torch.float64, device=ysave.device)
+            gx = torch.empty_like(ysave)
+            _lib.call("dasp_loudness_backward", _lib.ptr(ysave), _lib.ptr(cov), _lib.ptr(g32), _lib.ptr(scratch), _lib.ptr(gx), bs, chs, N, fs, _lib.stream())
+        return gx.to(dtype), None
+
+
+class _PeakNormFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, peak_db, eps):
+        x32 = _rows32(x)
+        bs, chs, N = x32.shape
+        rows = bs * chs
+        nd = _lib.lib().dasp_peaknorm_scratch_doubles(rows, N)
+        if nd < 0:
+            raise _lib.DaspHipError(f"peak_normalize: {tuple(x32.shape)} is not supported")
+        dev = x.device
+        with torch.cuda.device(dev):
+            scratch = torch.empty(nd, dtype=torch.float64, device=dev)
+            peak = torch.empty(2 * rows, dtype=torch.float64, device=dev)
+            y = torch.empty_like(x32)
+            _lib.call("dasp_peaknorm_forward", _lib.ptr(x32), _lib.ptr(scratch), _lib.ptr(peak), _lib.ptr(y), rows, N, peak_db, eps, _lib.stream())
+        ctx.save_for_backward(x32, peak)
+        ctx.cfg = (peak_db, eps, nd, x.dtype)
+        return y.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        x32, peak = ctx.saved_tensors
+        peak_db, eps, nd, dtype = ctx.cfg
+        bs, chs, N = x32.shape
+        with torch.cuda.device(x32.device):
+            g32 = gy.detach().to(torch.float32).contiguous()
+            scratch = torch.empty(nd, dtype=torch.float64, device=x32.device)
+            gx = torch.empty_like(x32)
+            _lib.call("dasp_peaknorm_backward", _lib.ptr(x32), _lib.ptr(g32), _lib.ptr(peak), _lib.ptr(scratch), _lib.ptr(gx), bs * chs, N, peak_db, eps,
+                      _lib.stream())
+        return gx.to(dtype), None, None
+
+
+def loudness(x: torch.Tensor, sample_rate: float):
+    """Integrated loudness in LUFS (ITU-R BS.1770-4 / EBU R128) of each batch item of x (bs, chs, seq_len), 1 <= chs <= 5 in the order
+    L, R, C, Ls, Rs with the weights 1, 1, 1, 1.41, 1.41 -> (bs,). K-weighting (signal.k_weighting_sos), 400 ms blocks every 100 ms - a
+    tail that does not complete a block is ignored -, the absolute gate at -70 LUFS and the relative gate 10 LU below the gated mean.
+    An item with no block past the gates gives -inf and a zero gradient. Differentiable with respect to x with the gates held fixed
+    (what autograd of a masked mean gives). 8000 <= sample_rate <= 384000 and seq_len >= one block, else ValueError."""
+    _level_rows(x, "loudness", sample_rate, 5)
+    return _LoudnessFunction.apply(x, float(sample_rate))
+
+
+def loudness_normalize(x: torch.Tensor, sample_rate: float, target_lufs=-23.0):
+    """gain(x, sample_rate, target_lufs - loudness(x, sample_rate)): every item is brought to `target_lufs` (a float, or a tensor with bs
+    values). Gradients flow through the gain and through the meter. Items whose loudness is -inf are returned unchanged (0 dB)."""
+    _level_rows(x, "loudness_normalize", sample_rate, 5)
+    bs = x.shape[0]
+    L = _LoudnessFunction.apply(x, float(sample_rate))
+    if isinstance(target_lufs, torch.Tensor):
+        if target_lufs.numel() != bs:
+            raise RuntimeError(f"shape '[{bs}]' is invalid for input of size {target_lufs.numel()}")
+        target = target_lufs.to(device=x.device, dtype=L.dtype).reshape(bs)
+    else:
+        target = torch.full((bs,), float(target_lufs), dtype=L.dtype, device=x.device)
+    gain_db = torch.where(torch.isfinite(L), target - L, torch.zeros_like(L))
+    return gain(x, sample_rate, gain_db)
+
+
+def peak_normalize(x: torch.Tensor, sample_rate: float, peak_db: float = 0.0, eps: float = 1e-8):
+    """Per row - per (item, channel), as the reference's examples do by hand (examples/auto_eq.py:289-291) -:
+    y = x * 10^(peak_db / 20) / max(max_n |x[n]|, eps); eps = 0 is the examples' plain division. Differentiable: the maximum's
+    gradient goes to the lowest index attaining it."""
+    _level_rows(x, "peak_normalize")
+    peak_db, eps = float(peak_db), float(eps)
+    if not (peak_db == peak_db and abs(peak_db) != float("inf")) or not eps >= 0.0:
+        raise ValueError(f"peak_normalize: peak_db must be finite and eps >= 0, got {peak_db!r}, {eps!r}")
+    return _PeakNormFunction.apply(x, peak_db, eps)

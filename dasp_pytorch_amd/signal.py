@@ -264,3 +264,17 @@ def octave_band_filterbank(num_taps: int, sample_rate: float):
     """Octave-spaced linear-phase FIR bank, shape (12, 1, num_taps) float32 on the CPU, as the reference
     (dasp_pytorch/signal.py:42-92): lowpass 12 Hz, ten octave bandpasses 31.5 Hz .. 16 kHz, highpass 18 kHz."""
     return torch.from_numpy(_octave_band_taps(int(num_taps), float(sample_rate)).copy()).unsqueeze(1)   # a fresh tensor per call, as the reference
+
+
+def k_weighting_sos(sample_rate: float):
+    """The K-weighting filter of ITU-R BS.1770-4 designed for `sample_rate` (8000 .. 384000 Hz): a (2, 6) float64 tensor on the CPU, rows
+    [b0 b1 b2 a0 a1 a2] - the high-frequency shelf, then the high-pass. It is the table functional.loudness's kernels use (the library's
+    own host-side design, csrc/loudness.hip), so it can be fed to sosfilt_via_fsm or fft_sosfreqz. At 48 kHz it reproduces the
+    recommendation's coefficient table to 1e-15."""
+    import ctypes
+    fs = float(sample_rate)
+    if not 8000.0 <= fs <= 384000.0:
+        raise ValueError(f"k_weighting_sos: sample_rate must lie in [8000, 384000], got {sample_rate!r}")
+    out = (ctypes.c_double * 12)()
+    _lib.check(_lib.lib().dasp_loudness_kweighting(fs, out), "dasp_loudness_kweighting")
+    return torch.tensor(list(out), dtype=torch.float64).reshape(2, 6)

@@ -547,6 +547,36 @@ int dasp_fdfir_backward(const float* x, const void* H, const float* gy, const vo
                         long rows, long T, long n_fft, long h_rows, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Level metering and normalisation (csrc/loudness.hip).
+ * Integrated loudness of ITU-R BS.1770-4 / EBU R128: K-weighting designed from the sample rate, 400 ms blocks every 100 ms,
+ * the absolute gate at -70 LUFS and the relative gate 10 LU below the gated mean; its gradient with the gates held fixed.
+ *   x, gx, ysave: (items, chs, N) fp32, rows 4-byte aligned;  1 <= chs <= 5 in the order L R C Ls Rs (weights 1 1 1 1.41 1.41);
+ *   8000 <= sample_rate <= 384000;  N >= one block (4 H, H = round(0.1 sample_rate)) and N <= 2^30, else DASP_ERR_UNSUPPORTED.
+ *   dasp_loudness_kweighting: the two sections as rows [b0 b1 b2 a0 a1 a2] (12 doubles, host memory) - the table the kernels use.
+ *   dasp_loudness_blocks: complete blocks of N samples;  dasp_loudness_segments: workgroups a row of N samples is cut into when there
+ *   are `rows` = items * chs of them (1: one workgroup per row; more: a state pre-pass runs first);  -1: unsupported arguments.
+ *   scratch: dasp_loudness_scratch_doubles(...) doubles, uninitialised; the backward call takes the same size.
+ *   L: (items) LUFS, -inf for an empty gate.  ysave, cov: both NULL (value only), or the K-weighted signal (items, chs, N) and the
+ *   coverage weights (items, chs, blocks + 3) kept for dasp_loudness_backward;  gL: (items) upstream gradient.
+ *   No atomics, nothing to zero, no host synchronisation: bit-identical run to run, plain kernel nodes under capture.
+ * Peak normalisation per row: y = x 10^(peak_db / 20) / max(max |x|, eps);  peak: (rows, 2) doubles written by the forward call
+ * (the maximum and the lowest index attaining it) and read by the backward call;  scratch: dasp_peaknorm_scratch_doubles(...) doubles.
+ * ------------------------------------------------------------------------------------------- */
+int dasp_loudness_kweighting(double sample_rate, double* sos12);
+long dasp_loudness_blocks(long N, double sample_rate);
+long dasp_loudness_segments(long rows, long N);
+long dasp_loudness_scratch_doubles(long items, int chs, long N, double sample_rate);
+int dasp_loudness_forward(const float* x, double* scratch, float* L, float* ysave, float* cov, long items, int chs, long N,
+                          double sample_rate, void* stream);
+int dasp_loudness_backward(const float* ysave, const float* cov, const float* gL, double* scratch, float* gx, long items, int chs, long N,
+                           double sample_rate, void* stream);
+long dasp_peaknorm_scratch_doubles(long rows, long N);
+int dasp_peaknorm_forward(const float* x, double* scratch, double* peak, float* y, long rows, long N, double peak_db, double eps,
+                          void* stream);
+int dasp_peaknorm_backward(const float* x, const float* gy, const double* peak, double* scratch, float* gx, long rows, long N,
+                           double peak_db, double eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Double precision.  The reference follows the dtype of its input (`.type_as(x)`, dasp_pytorch/signal.py:113,119,
  * functional.py:211), so float64 tensors mean float64 arithmetic. These entry points are that path for the recurrences and the
  * elementwise effects - the same maps as above evaluated plainly, one thread per row / batch item, sequential in time: meant for
