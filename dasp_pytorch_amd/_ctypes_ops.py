@@ -764,6 +764,52 @@ class BusFunction(_StereoFunction):
         return BusFunction._grad(ctx, gy)
 
 
+class StereoMixFunction(torch.autograd.Function):
+    """(B, T, N) mono tracks -> (mix, send), both (B, 2, N): fader, pan and bus sum in one pass (dasp_stereo_mix_forward / _backward,
+    csrc/stereo.hip) - stereo_bus(stereo_panner(x, pan), gain_db) without the (B, 2, T, N) tensor in between; send (None without send_db)
+    is the same sum with 10^(send_db / 20) more per track. Saves x and the three control vectors only."""
+
+    @staticmethod
+    def forward(ctx, x, gain_db, pan, send_db):
+        _lib.require_device(x, "x")
+        B, T, N = x.shape
+        ctls = (gain_db, pan) if send_db is None else (gain_db, pan, send_db)
+        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls], B, T, N)
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            mix = torch.empty((B, 2, N), dtype=x.dtype, device=x.device)
+            return mix, (None if send_db is None else torch.empty_like(mix))
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            c32 = [c.detach().reshape(-1).to(device=x.device, dtype=torch.float32).contiguous() for c in ctls]
+            mix = torch.empty((B, 2, N), dtype=torch.float32, device=x.device)
+            send = None if send_db is None else torch.empty_like(mix)
+            call("dasp_stereo_mix_forward", ptr(x32), ptr(c32[0]), ptr(c32[1]), ptr(c32[2] if send is not None else None), ptr(mix), ptr(send),
+                 B, T, N, stream())
+            ctx.save_for_backward(x32, *c32)
+        return mix.to(x.dtype), (None if send is None else send.to(x.dtype))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gmix, gsend):
+        xd, cmeta, B, T, N = ctx.meta
+        dev = gmix.device
+        with_send = len(cmeta) == 3
+        if ctx.empty:
+            gc = [torch.zeros(s, dtype=d, device=dev) for d, s in cmeta]
+            return torch.empty((B, T, N), dtype=xd, device=dev), gc[0], gc[1], (gc[2] if with_send else None)
+        x32, *c32 = ctx.saved_tensors
+        with torch.cuda.device(dev):
+            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None           # not computed, not written when x needs no gradient
+            gc = [torch.empty_like(c) for c in c32]
+            partials = torch.empty(_lib.lib().dasp_stereo_mix_partial_floats(B, T, N, int(with_send)), dtype=torch.float32, device=dev)
+            call("dasp_stereo_mix_backward", ptr(x32), ptr(c32[0]), ptr(c32[1]), ptr(c32[2] if with_send else None), ptr(_f32c(gmix)),
+                 ptr(_f32c(gsend) if with_send else None), ptr(gx), ptr(gc[0]), ptr(gc[1]), ptr(gc[2] if with_send else None), ptr(partials),
+                 B, T, N, stream())
+        gc = [g.reshape(s).to(d) for g, (d, s) in zip(gc, cmeta)]
+        return (None if gx is None else gx.to(xd)), gc[0], gc[1], (gc[2] if with_send else None)
+
+
 _FSPEC_CACHE = {}
 
 

@@ -7,7 +7,7 @@ from . import signal as _signal
 from . import _mt19937
 from . import ops as _ops
 from . import _lib
-from .ops import FILTER_TYPES, BusFunction, DistortionSampleFunction, PannerFunction, WidenerFunction
+from .ops import FILTER_TYPES, BusFunction, DistortionSampleFunction, PannerFunction, StereoMixFunction, WidenerFunction
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
 
@@ -86,6 +86,22 @@ def stereo_panner(x: torch.Tensor, sample_rate: float, pan: torch.Tensor):
         raise RuntimeError(f"shape '[{bs}, 1, {num_tracks}, 1]' is invalid for input of size {pan.numel()}")
     require_fp32_ok(x, "stereo_panner")
     return PannerFunction.apply(x, pan)
+
+
+def stereo_mix(x: torch.Tensor, sample_rate: float, gain_db: torch.Tensor, pan: torch.Tensor, send_db: torch.Tensor = None):
+    """Mix mono tracks (bs, num_tracks, seq_len) onto a stereo bus (bs, 2, seq_len): a fader gain_db and a pan in [0, 1] per track, bs*num_tracks
+    values each, in one pass over x. The result is what the reference's functions compose to,
+    stereo_bus(stereo_panner(x, sample_rate, pan), sample_rate, gain_db), without the (bs, 2, num_tracks, seq_len) tensor between them.
+    With send_db (bs*num_tracks values) it returns the tuple (mix, send): send is an effects send taken post-fader and post-pan,
+    stereo_bus(stereo_panner(x, sample_rate, pan), sample_rate, gain_db + send_db). Differentiable in x and in every control.
+    At most 256 tracks (dasp_stereo_mix_max_tracks); more raise DaspHipError (unsupported configuration)."""
+    bs, num_tracks, seq_len = x.size()
+    for name, c in (("gain_db", gain_db), ("pan", pan), ("send_db", send_db)):
+        if c is not None and c.numel() != bs * num_tracks:
+            raise RuntimeError(f"{name}: shape '[{bs}, {num_tracks}]' is invalid for input of size {c.numel()}")
+    require_fp32_ok(x, "stereo_mix")
+    mix, send = StereoMixFunction.apply(x, gain_db, pan, send_db)
+    return mix if send_db is None else (mix, send)
 
 
 def parametric_eq(

@@ -398,6 +398,26 @@ int dasp_panner_backward(const float* x, const float* pan, const float* gy, floa
 int dasp_bus_forward(const float* x, const float* send_db, float* y, int B, int T, long N, void* stream);
 int dasp_bus_backward(const float* x, const float* send_db, const float* gy, float* gx, float* gsend, float* partials, int B, int T,
                       long N, void* stream);
+/* stereo_mix: fader, pan and bus sum of T mono tracks in one pass - what dasp_bus_forward(dasp_panner_forward(x, pan), gain_db) computes,
+ * without the (B, 2, T, N) tensor between them - and, optionally, a post-fader, post-pan effects send (a second bus).
+ *   x (B, T, N); gain_db, pan, send_db (B * T); mix, send (B, 2, N).   g = 10^(gain_db / 20), s = 10^(send_db / 20), l, r the panner's gains
+ *   mix[b, 0] = sum_t g l x[b, t],  mix[b, 1] = sum_t g r x[b, t],  send[b, c] = the same sums with s g in place of g
+ * send_db and send (forward), send_db, gsend and gsend_db (backward) are given together or are all NULL (no send bus): anything else, a
+ * null pointer elsewhere or a non-positive size is DASP_ERR_ARG. gx may be NULL (x needs no gradient: it is neither computed nor written).
+ * T <= dasp_stereo_mix_max_tracks() (256) and B * ceil(N / segment) < 2^31, else DASP_ERR_UNSUPPORTED; all of it is checked before any launch.
+ *   dasp_stereo_mix_segment(B, N): samples per workgroup - 4096, halved down to 1024 while B * ceil(N / segment) is below 512 workgroups
+ *     (two per compute unit). It fixes the layout of partials (B, segments, T, 2 or 4) and nothing else: what is computed for a sample of
+ *     mix, send or gx does not depend on it.
+ *   partials: dasp_stereo_mix_partial_floats(B, T, N, with_send) floats of scratch for the backward call (two launches, no atomics:
+ *     results are bit-identical run to run). */
+int dasp_stereo_mix_segment(long B, long N);
+int dasp_stereo_mix_max_tracks(void);
+long dasp_stereo_mix_partial_floats(long B, int T, long N, int with_send);
+int dasp_stereo_mix_forward(const float* x, const float* gain_db, const float* pan, const float* send_db, float* mix, float* send, int B,
+                            int T, long N, void* stream);
+int dasp_stereo_mix_backward(const float* x, const float* gain_db, const float* pan, const float* send_db, const float* gmix,
+                             const float* gsend, float* gx, float* ggain, float* gpan, float* gsend_db, float* partials, int B, int T,
+                             long N, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-resolution STFT loss, the op downstream of the effect chain in the reference's training loops
