@@ -443,12 +443,8 @@ def _dyn_forward(x, mode, sample_rate, eps, lookahead, ctl, need):
     # few items: every item is cut into segments that run as independent workgroups (dasp_hip.h, "Few batch items")
     tseg = 0 if not config.plan.dyn_segment else int(config.plan.dyn_segment_tiles or L.dasp_dyn_segment_tiles(B, N))
     segbuf = torch.empty(2 * B * L.dasp_dyn_segments(N, tseg), dtype=torch.float32, device=x.device) if tseg else None
-    if tseg:
-        call("dasp_dynamics_forward_seg", mode, ptr(x32), ptr(ctl), ptr(y), ptr(carries), ptr(lin), ptr(segbuf), B, C, N, float(sample_rate),
-             float(eps), int(lookahead), tseg, ptr(_dyn_counters(x.device) if B <= 128 else None), stream())
-    else:
-        call("dasp_dynamics_forward", mode, ptr(x32), ptr(ctl), ptr(y), ptr(carries), ptr(lin), B, C, N, float(sample_rate),
-             float(eps), int(lookahead), stream())
+    call("dasp_dynamics_forward", mode, ptr(x32), ptr(ctl), ptr(y), ptr(carries), ptr(lin), ptr(segbuf), B, C, N, float(sample_rate),
+         float(eps), int(lookahead), tseg, ptr(_dyn_counters(x.device) if tseg and B <= 128 else None), stream())
     saved = (x32, ctl, carries, lin if lin is not None else torch.empty(0, device=x.device))
     return y, saved, (mode, float(sample_rate), float(eps), int(lookahead), tseg)
 
@@ -463,14 +459,10 @@ def _dyn_backward(saved, cfg, gy):
     gctl = torch.empty(B, 5, dtype=torch.float32, device=x32.device)
     G = int(L.dasp_dyn_segments(N, tseg))
     partials = torch.empty(L.dasp_dyn_partial_floats(B * G), dtype=torch.float32, device=x32.device)
-    if tseg:
-        segbuf = torch.empty(2 * B * G, dtype=torch.float32, device=x32.device)
-        call("dasp_dynamics_backward_seg", mode, ptr(x32), ptr(ctl), ptr(_f32c(gy)), ptr(carries), ptr(lin if look > 0 else None),
-             ptr(gx), ptr(gctl), ptr(partials), ptr(segbuf), B, C, N, sr, eps, look, tseg, ptr(_dyn_counters(x32.device) if B <= 128 else None),
-             stream())
-    else:
-        call("dasp_dynamics_backward", mode, ptr(x32), ptr(ctl), ptr(_f32c(gy)), ptr(carries), ptr(lin if look > 0 else None),
-             ptr(gx), ptr(gctl), ptr(partials), B, C, N, sr, eps, look, stream())
+    segbuf = torch.empty(2 * B * G, dtype=torch.float32, device=x32.device) if tseg else None
+    call("dasp_dynamics_backward", mode, ptr(x32), ptr(ctl), ptr(_f32c(gy)), ptr(carries), ptr(lin if look > 0 else None),
+         ptr(gx), ptr(gctl), ptr(partials), ptr(segbuf), B, C, N, sr, eps, look, tseg, ptr(_dyn_counters(x32.device) if tseg and B <= 128 else None),
+         stream())
     return gx, gctl
 
 
@@ -660,7 +652,7 @@ def chain_eq_compressor_forward(x, eq_pn, types, lo, span, sample_rate, ctl, mod
         tab, segbuf = f32[:n_tab], (f32[n_tab:] if tseg else None)
         dtab, segtab = f64[:n_dt], (f64[n_dt:] if tseg else None)
         y = torch.empty_like(x32)
-        call("dasp_peq_prepare_norm_seg", ptr(pn32), Bp, S, (ctypes.c_int * S)(*types), float(sample_rate), (ctypes.c_double * (3 * S))(*lo),
+        call("dasp_peq_prepare_norm", ptr(pn32), Bp, S, (ctypes.c_int * S)(*types), float(sample_rate), (ctypes.c_double * (3 * S))(*lo),
              (ctypes.c_double * (3 * S))(*span), ptr(range_flag), ptr(tab), ptr(dtab), tseg, ptr(segtab), stream())      # design (+ segment matrices; range_flag: see parametric_eq_norm)
         call("dasp_chain_forward", ptr(tab), Bp, ptr(x32), ptr(c32), ptr(y), B, C, N, S, int(mode), float(sample_rate), float(eps), tseg,
              ptr(segtab), ptr(segbuf), stream())
@@ -841,7 +833,7 @@ def _seed_offset(t, dev):
 
 
 def reverb_noise(seed, B, nb, row_len, device, seed_offset=None):
-    """The white-noise stream the filter-bank kernels generate for `seed` (dasp_reverb_forward_rng), written out in the reference's layout
+    """The white-noise stream the filter-bank kernels generate for `seed` (dasp_reverb_forward without a noise tensor), written out in the reference's layout
     (2B, nb, row_len) (dasp_pytorch/functional.py:548). A test / inspection hook: the product never materialises it."""
     dev = torch.device(device)
     out = torch.empty(2 * B, nb, row_len, dtype=torch.float32, device=dev)
@@ -903,12 +895,9 @@ class ReverbFunction(torch.autograd.Function):
             W2 = None if need_grad else _cbuf(sizes[12], dev)
             W, H, Ah = _cbuf(sizes[12], dev), _cbuf(sizes[7], dev), _cbuf(sizes[13], dev)
             ir = torch.empty(sizes[8], dtype=torch.float32, device=dev)
-            if noise is None:
-                call("dasp_reverb_forward_rng", ptr(x32), useed, ptr(soff), ptr(Fspec), ptr(g32), ptr(d32), ptr(m32), ptr(y), ptr(A), ptr(H),
-                     ptr(W), ptr(W2), ptr(Ah), ptr(ir), B, C, N, L_ir, taps, nb, float(decay_bound), stream())
-            else:
-                call("dasp_reverb_forward", ptr(x32), ptr(n32), ptr(Fspec), ptr(g32), ptr(d32), ptr(m32), ptr(y), ptr(A), ptr(H),
-                     ptr(W), ptr(W2), ptr(Ah), ptr(ir), B, C, N, L_ir, taps, nb, float(decay_bound), stream())
+            # (noise given: n32, and seed 0 / no offset word, which the call ignores; seeded: a null noise pointer)
+            call("dasp_reverb_forward", ptr(x32), ptr(n32), useed if useed is not None else 0, ptr(soff), ptr(Fspec), ptr(g32), ptr(d32), ptr(m32), ptr(y), ptr(A), ptr(H),
+                 ptr(W), ptr(W2), ptr(Ah), ptr(ir), B, C, N, L_ir, taps, nb, float(decay_bound), stream())
             if need_grad:
                 # the seed-offset word is read again by the backward kernels when they run: it is saved WITH the tensors, so that an in-place
                 # bump between this forward and its backward (which would regenerate a different noise stream) trips autograd's
@@ -939,12 +928,9 @@ class ReverbFunction(torch.autograd.Function):
             gir = torch.empty(sizes[8], dtype=torch.float32, device=dev)
             part = torch.empty(sizes[11], dtype=torch.float32, device=dev)
             mix_part = torch.empty(sizes[10], dtype=torch.float32, device=dev)
-            tail = (ptr(Fspec), ptr(g32), ptr(d32), ptr(m32), ptr(A), ptr(H), ptr(gx), ptr(ggain), ptr(gdecay), ptr(gmix), ptr(Ag), ptr(W), ptr(P),
-                    ptr(gir), ptr(part), ptr(mix_part), B, C, N, L_ir, taps, nb, dbound, stream())
-            if useed is not None:
-                call("dasp_reverb_backward_rng", ptr(ir), ptr(_f32c(gy)), useed, ptr(soff), *tail)
-            else:
-                call("dasp_reverb_backward", ptr(ir), ptr(_f32c(gy)), ptr(n32), *tail)
+            call("dasp_reverb_backward", ptr(ir), ptr(_f32c(gy)), ptr(n32 if useed is None else None), useed if useed is not None else 0, ptr(soff), ptr(Fspec), ptr(g32),
+                 ptr(d32), ptr(m32), ptr(A), ptr(H), ptr(gx), ptr(ggain), ptr(gdecay), ptr(gmix), ptr(Ag), ptr(W), ptr(P), ptr(gir), ptr(part),
+                 ptr(mix_part), B, C, N, L_ir, taps, nb, dbound, stream())
         if C == 1:
             gx = gx.sum(1, keepdim=True)           # the adjoint of the mono -> stereo duplication
         return gx.to(xd), None, None, ggain.reshape(gs).to(gd), gdecay.reshape(ds).to(dd), gmix.reshape(ms).to(md), None, None, None, None

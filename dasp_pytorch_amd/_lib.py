@@ -30,18 +30,14 @@ SIGNATURES = {
     "dasp_peq_prepare": (_i, [_p, _i, _i, ctypes.POINTER(ctypes.c_int), _d, _p, _p, _p]),
     "dasp_peq_prepare_rows": (_i, [ctypes.POINTER(ctypes.c_void_p), _i, _i, ctypes.POINTER(ctypes.c_int), _d, _p, _p, _p]),
     "dasp_sosfilt_forward": (_i, [_p, _i, _p, _p, _p, _i, _i, _l, _i, _p]),
-    "dasp_sosfilt_backward": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _l, _i, _p]),
-    "dasp_sos_grad_finalize": (_i, [_p, _i, _p, _i, _i, _i, _i, _p, _p]),
-    "dasp_sosfilt_backward_grads": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _l, _i, _p]),
     "dasp_sosfilt_backward_ex": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _l, _i, _p]),
     "dasp_sos_grad_finalize_ex": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "dasp_sosfilt_backward_grads_ex": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _l, _i, _p]),
     "dasp_peq_forward": (_i, [ctypes.POINTER(ctypes.c_void_p), _i, _i, ctypes.POINTER(ctypes.c_int), _d, _p, _p, _p, _p, _p, _i, _i, _l, _l, _p, _p, _p]),
     "dasp_peq_forward_norm": (_i, [_p, _i, _i, ctypes.POINTER(ctypes.c_int), _d, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _p,
                                    _p, _p, _p, _p, _p, _i, _i, _l, _l, _p, _p, _p]),
-    "dasp_peq_prepare_norm": (_i, [_p, _i, _i, ctypes.POINTER(ctypes.c_int), _d, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _p, _p, _p, _p]),
-    "dasp_peq_prepare_norm_seg": (_i, [_p, _i, _i, ctypes.POINTER(ctypes.c_int), _d, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _p, _p, _p,
-                                       _l, _p, _p]),
+    "dasp_peq_prepare_norm": (_i, [_p, _i, _i, ctypes.POINTER(ctypes.c_int), _d, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _p, _p, _p,
+                                   _l, _p, _p]),
     "dasp_sos_segment_starts": (_i, [_p, _p, _i, _p, _p, _i, _i, _l, _i, _l, _p]),
     "dasp_chain_segment_tiles": (_l, [_l, _l]),
     "dasp_chain_seg_floats": (_l, [_l, _l, _l, _i, _l]),
@@ -57,8 +53,6 @@ SIGNATURES = {
     "dasp_sos_seg_floats": (_l, [_l, _l, _i, _l]),
     "dasp_sos_segment_prepare": (_i, [_p, _i, _i, _l, _p, _p]),
     "dasp_sosfilt_forward_seg": (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _l, _i, _l, _p]),
-    "dasp_sosfilt_backward_seg": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _l, _i, _l, _p]),
-    "dasp_sos_grad_finalize_seg": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "dasp_ew_partial_floats": (_l, [_l, _l]),
     "dasp_gain_forward": (_i, [_p, _p, _p, _i, _i, _l, _p]),
     "dasp_gain_backward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _l, _p]),
@@ -72,12 +66,10 @@ SIGNATURES = {
     "dasp_dyn_carry_floats": (_l, [_l, _l]),
     "dasp_dyn_partial_floats": (_l, [_l]),
     "dasp_dyn_counters_reset": (_i, [_p, _i, _p]),
-    "dasp_dynamics_forward": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _l, _d, ctypes.c_float, _i, _p]),
-    "dasp_dynamics_backward": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _l, _d, ctypes.c_float, _i, _p]),
     "dasp_dyn_segment_tiles": (_l, [_l, _l]),
     "dasp_dyn_segments": (_l, [_l, _l]),
-    "dasp_dynamics_forward_seg": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _l, _d, ctypes.c_float, _i, _l, _p, _p]),
-    "dasp_dynamics_backward_seg": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _l, _d, ctypes.c_float, _i, _l, _p, _p]),
+    "dasp_dynamics_forward": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _l, _d, ctypes.c_float, _i, _l, _p, _p]),
+    "dasp_dynamics_backward": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _l, _d, ctypes.c_float, _i, _l, _p, _p]),
     "dasp_dynamics_forward_rows": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _l, _d, ctypes.c_float, _i, _l, _p, _p]),
     "dasp_dynamics_backward_rows": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _l, _d, ctypes.c_float, _i, _l, _p, _p]),
     "dasp_stereo_partial_floats": (_l, [_i, _l, _i, _l]),
@@ -137,10 +129,8 @@ SIGNATURES = {
     "dasp_reverb_plan": (_i, [_l, ctypes.c_float, _i]),
     "dasp_reverb_sizes": (_i, [_i, _l, _i, _i, _i, ctypes.POINTER(ctypes.c_long)]),
     "dasp_reverb_filter_spectrum": (_i, [_p, _i, _i, _p, _p]),
-    "dasp_reverb_forward": (_i, [_p] * 13 + [_i, _i, _l, _i, _i, _i, ctypes.c_float, _p]),
-    "dasp_reverb_backward": (_i, [_p] * 19 + [_i, _i, _l, _i, _i, _i, ctypes.c_float, _p]),
-    "dasp_reverb_forward_rng": (_i, [_p, ctypes.c_ulonglong, _p] + [_p] * 11 + [_i, _i, _l, _i, _i, _i, ctypes.c_float, _p]),
-    "dasp_reverb_backward_rng": (_i, [_p, _p, ctypes.c_ulonglong, _p] + [_p] * 16 + [_i, _i, _l, _i, _i, _i, ctypes.c_float, _p]),
+    "dasp_reverb_forward": (_i, [_p, _p, ctypes.c_ulonglong, _p] + [_p] * 11 + [_i, _i, _l, _i, _i, _i, ctypes.c_float, _p]),
+    "dasp_reverb_backward": (_i, [_p, _p, _p, ctypes.c_ulonglong, _p] + [_p] * 16 + [_i, _i, _l, _i, _i, _i, ctypes.c_float, _p]),
     "dasp_reverb_noise": (_i, [ctypes.c_ulonglong, _p, _p, _i, _i, _l, _p]),
     "dasp_device_error": (_i, []),
     "dasp_device_error_clear": (None, []),

@@ -18,6 +18,7 @@
 #include "dyn_common.hpp"
 #include <atomic>
 #include <cstdint>
+#include <type_traits>
 
 // s_setprio of a wave from the top of its tile until its carry has been handed on (loads, gain computer, lane scans, mailbox):
 // see the same switch in sosfilt.hip
@@ -720,6 +721,21 @@ inline int dy_check() {
     return e == hipSuccess ? DASP_OK : (int)e;
 }
 inline bool dy_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The kernels' template arguments from run-time values: f receives them as std::integral_constant (generic lambdas, as dispatch_S and the
+// launch(flags) lambda of sosfilt.hip): mode 0 compressor / 1 expander, and for the backward kernel its DMA variant.
+template <typename F>
+void dispatch_mode(int mode, F&& f) {
+    if (mode == 0) f(std::integral_constant<int, 0>{});
+    else f(std::integral_constant<int, 1>{});
+}
+template <typename F>
+void dispatch_mode_dma(int mode, bool dma, F&& f) {
+    dispatch_mode(mode, [&](auto m) {
+        if (dma) f(m, std::true_type{});
+        else f(m, std::false_type{});
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -737,48 +753,11 @@ int dasp_dyn_counters_reset(int* counters, int B, void* stream) {
     return (int)zero_async(counters, sizeof(int) * 4 * (size_t)B, (hipStream_t)stream);
 }
 
-static int dynamics_forward_impl(int mode, const float* x, const DynCtl ctl, float* y, float* carries, float* lin_buf, int B, int C, long N,
-                          double sample_rate, float eps, int lookahead, void* stream) {
-    if (!x || !ctl.p[0] || !y || B <= 0 || C <= 0 || N <= 0 || lookahead < 0 || (mode != 0 && mode != 1)) return DASP_ERR_ARG;
-    if (lookahead > 0 && !lin_buf) return DASP_ERR_ARG;
-    if (N > 0x7fffffffL - DY_TS) return DASP_ERR_UNSUPPORTED;
-    const int nt = (int)dasp_dyn_num_tiles(N), vec = (N % 4 == 0) && dy_al16(x) && dy_al16(y) && (!lin_buf || dy_al16(lin_buf));
-    if (mode == 0)
-        hipLaunchKernelGGL((dyn_fwd_kernel<0, kDWF>), dim3(B), dim3(64 * kDWF), 0, (hipStream_t)stream, x, ctl, y, carries,
-                           lookahead > 0 ? lin_buf : nullptr, C, (int)N, nt, vec, lookahead, sample_rate, eps);
-    else
-        hipLaunchKernelGGL((dyn_fwd_kernel<1, kDWF>), dim3(B), dim3(64 * kDWF), 0, (hipStream_t)stream, x, ctl, y, carries,
-                           lookahead > 0 ? lin_buf : nullptr, C, (int)N, nt, vec, lookahead, sample_rate, eps);
-    return dy_check();
-}
-
-static int dynamics_backward_impl(int mode, const float* x, const DynCtl ctl, const float* gy, const float* carries, const float* lin_buf,
-                                  float* gx, const DynGrad gctl, float* partials, int B, int C, long N, double sample_rate, float eps, int lookahead,
-                                  void* stream) {
-    if (!x || !ctl.p[0] || !gy || !carries || !gx || !gctl.p[0] || !partials || B <= 0 || C <= 0 || N <= 0 || lookahead < 0 ||
-        (mode != 0 && mode != 1))
-        return DASP_ERR_ARG;
-    if (lookahead > 0 && !lin_buf) return DASP_ERR_ARG;
-    if (N > 0x7fffffffL - DY_TS) return DASP_ERR_UNSUPPORTED;
-    const int nt = (int)dasp_dyn_num_tiles(N), vec = (N % 4 == 0) && dy_al16(x) && dy_al16(gy) && dy_al16(gx);
-    const bool dma = vec && lookahead == 0 && C <= 2;
-#define DASP_DYN_BWD(MODE_, DMA_)                                                                                                              \
-    hipLaunchKernelGGL((dyn_bwd_kernel<MODE_, kDW, DMA_>), dim3(B), dim3(64 * kDW), 0, (hipStream_t)stream, x, ctl, gy, carries, lin_buf, gx, \
-                       partials, C, (int)N, nt, vec, lookahead, sample_rate, eps)
-    if (mode == 0) { if (dma) DASP_DYN_BWD(0, true); else DASP_DYN_BWD(0, false); }
-    else { if (dma) DASP_DYN_BWD(1, true); else DASP_DYN_BWD(1, false); }
-#undef DASP_DYN_BWD
-    int st = dy_check();
-    if (st != DASP_OK) return st;
-    hipLaunchKernelGGL(dyn_finalize_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, partials, ctl, B, kDW, sample_rate, gctl);
-    return dy_check();
-}
-
 // ---- segmented items (few batch items) -------------------------------------------------------------------------------------------
 // One workgroup per item leaves most of the chip idle below ~128 items; every item can be cut into segments of Tseg tiles that run as
 // independent workgroups: scan-only pre-pass (end state of every segment from a zero start), dyn_chain_kernel (the scalar smoothing
 // state chained through alpha^(samples per segment)), then the ordinary pass per segment. Same results (the chain runs in fp64).
-//   Tseg   = dasp_dyn_segment_tiles(B, N): proposed tiles per segment (a power of two), 0 = use the plain calls
+//   Tseg   = dasp_dyn_segment_tiles(B, N): proposed tiles per segment (a power of two), 0 = one workgroup per item
 //   segbuf = 2 * B * dasp_dyn_segments(N, Tseg) floats of scratch; carries as for the plain calls;
 //   partials of the backward pass: dasp_dyn_partial_floats(B * segments) floats.
 long dasp_dyn_segment_tiles(long B, long N) {
@@ -792,34 +771,29 @@ long dasp_dyn_segment_tiles(long B, long N) {
 }
 long dasp_dyn_segments(long N, long Tseg) { return Tseg > 0 ? (dasp_dyn_num_tiles(N) + Tseg - 1) / Tseg : 1; }
 
-static int dynamics_forward_seg_impl(int mode, const float* x, const DynCtl ctl, float* y, float* carries, float* lin_buf, float* segbuf, int B,
-                                     int C, long N, double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream) {
-    if (!x || !ctl.p[0] || !y || !segbuf || B <= 0 || C <= 0 || N <= 0 || lookahead < 0 || (mode != 0 && mode != 1) || Tseg <= 0) return DASP_ERR_ARG;
+// Tseg <= 0: one workgroup per item (segbuf / counters unused). Tseg > 0: the item's segments as workgroups of their own, in one launch
+// (look-back), two (counters: the pre-pass's last workgroup per item chains the segments) or three (dyn_chain_kernel between them).
+static int dynamics_forward_impl(int mode, const float* x, const DynCtl ctl, float* y, float* carries, float* lin_buf, float* segbuf, int B,
+                                 int C, long N, double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream) {
+    if (!x || !ctl.p[0] || !y || (Tseg > 0 && !segbuf) || B <= 0 || C <= 0 || N <= 0 || lookahead < 0 || (mode != 0 && mode != 1)) return DASP_ERR_ARG;
     if (lookahead > 0 && !lin_buf) return DASP_ERR_ARG;
     if (N > 0x7fffffffL - DY_TS) return DASP_ERR_UNSUPPORTED;
     const int nt = (int)dasp_dyn_num_tiles(N), G = (int)dasp_dyn_segments(N, Tseg);
     const int vec = (N % 4 == 0) && dy_al16(x) && dy_al16(y) && (!lin_buf || dy_al16(lin_buf));
-    float* z = segbuf;
-    float* start = segbuf + (size_t)B * G;
     hipStream_t st = (hipStream_t)stream;
     float* lb = lookahead > 0 ? lin_buf : nullptr;
+    const dim3 grid(B * G), block(64 * kDWF);
+    if (Tseg <= 0) {
+        dispatch_mode(mode, [&](auto m) {
+            hipLaunchKernelGGL((dyn_fwd_kernel<decltype(m)::value, kDWF>), grid, block, 0, st, x, ctl, y, carries, lb, C, (int)N, nt, vec, lookahead,
+                               sample_rate, eps);
+        });
+        return dy_check();
+    }
     // counters: 4 * B ints owned by the caller (dasp_hip.h), zero before their first use; every use returns its word to zero. (Rounds 3 - 4
     // zeroed them here with hipMemsetAsync on the stream; inside a captured graph that memset node was not ordered before the kernel node
     // behind it when the replay started on an idle device - the count was wiped half-way, no workgroup ever saw it complete, outputs
     // and control gradients of the replay were garbage: scripts/debug_dyn_graph.py.)
-#define DASP_DYN_FWD_SEG(MODE_)                                                                                                                  \
-    hipLaunchKernelGGL((dyn_fwd_kernel<MODE_, kDWF, 2>), dim3(B * G), dim3(64 * kDWF), 0, st, x, ctl, (float*)nullptr, (float*)nullptr,          \
-                       (float*)nullptr, C, (int)N, nt, vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)nullptr, z);               \
-    hipLaunchKernelGGL(dyn_chain_kernel, dim3((B + 63) / 64), dim3(64), 0, st, ctl, (const float*)z, start, B, G, (long)Tseg * DY_TS,            \
-                       sample_rate, 0);                                                                                                         \
-    hipLaunchKernelGGL((dyn_fwd_kernel<MODE_, kDWF, 1>), dim3(B * G), dim3(64 * kDWF), 0, st, x, ctl, y, carries, lb, C, (int)N, nt, vec,        \
-                       lookahead, sample_rate, eps, G, (int)Tseg, (const float*)start, (float*)nullptr)
-    /* counters: the pre-pass's last workgroup per item chains the segments - two launches instead of three */
-#define DASP_DYN_FWD_SEG2(MODE_)                                                                                                                 \
-    hipLaunchKernelGGL((dyn_fwd_kernel<MODE_, kDWF, 2>), dim3(B * G), dim3(64 * kDWF), 0, st, x, ctl, (float*)nullptr, (float*)nullptr,          \
-                       (float*)nullptr, C, (int)N, nt, vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)nullptr, z, counters, start); \
-    hipLaunchKernelGGL((dyn_fwd_kernel<MODE_, kDWF, 1>), dim3(B * G), dim3(64 * kDWF), 0, st, x, ctl, y, carries, lb, C, (int)N, nt, vec,        \
-                       lookahead, sample_rate, eps, G, (int)Tseg, (const float*)start, (float*)nullptr)
     /* one launch (dyn_fwd_lookback_kernel): Tseg = 1, 2 or 4 tiles per forward wave - what the planner proposes up to (32, c, 262144) */
     const long tpw = Tseg % kDWF == 0 ? Tseg / kDWF : 0;
     if (DASP_DYN_LOOKBACK && lookback_enabled() && counters && (tpw == 1 || tpw == 2 || tpw == 4) && !(reinterpret_cast<uintptr_t>(segbuf) & 7)) {
@@ -828,117 +802,118 @@ static int dynamics_forward_seg_impl(int mode, const float* x, const DynCtl ctl,
         static std::atomic<unsigned> calls{0x2545F491u};
         unsigned tag = calls.fetch_add(0x9E3779B1u) | 1u;                 // never 0 (= a returned word)
         unsigned long long* words = reinterpret_cast<unsigned long long*>(segbuf);
-#define DASP_DYN_FWD_LB(MODE_, TPW_)                                                                                                            \
-        hipLaunchKernelGGL((dyn_fwd_lookback_kernel<MODE_, kDWF, TPW_>), dim3(B * G), dim3(64 * kDWF), 0, st, x, ctl, y, carries, lb, C, (int)N,  \
-                           nt, vec, lookahead, sample_rate, eps, G, words, counters, tag, err)
-        if (mode == 0) { if (tpw == 1) { DASP_DYN_FWD_LB(0, 1); } else if (tpw == 2) { DASP_DYN_FWD_LB(0, 2); } else { DASP_DYN_FWD_LB(0, 4); } }
-        else { if (tpw == 1) { DASP_DYN_FWD_LB(1, 1); } else if (tpw == 2) { DASP_DYN_FWD_LB(1, 2); } else { DASP_DYN_FWD_LB(1, 4); } }
-#undef DASP_DYN_FWD_LB
+        auto launch = [&](auto m, auto t) {
+            hipLaunchKernelGGL((dyn_fwd_lookback_kernel<decltype(m)::value, kDWF, decltype(t)::value>), grid, block, 0, st, x, ctl, y, carries, lb, C, (int)N,
+                               nt, vec, lookahead, sample_rate, eps, G, words, counters, tag, err);
+        };
+        dispatch_mode(mode, [&](auto m) {
+            if (tpw == 1) launch(m, std::integral_constant<int, 1>{});
+            else if (tpw == 2) launch(m, std::integral_constant<int, 2>{});
+            else launch(m, std::integral_constant<int, 4>{});
+        });
+        return dy_check();
     }
-    else if (counters && G <= DY_GMAX) { if (mode == 0) { DASP_DYN_FWD_SEG2(0); } else { DASP_DYN_FWD_SEG2(1); } }
-    else if (mode == 0) { DASP_DYN_FWD_SEG(0); } else { DASP_DYN_FWD_SEG(1); }
-#undef DASP_DYN_FWD_SEG2
-#undef DASP_DYN_FWD_SEG
+    float* z = segbuf;
+    float* start = segbuf + (size_t)B * G;
+    const bool self_chain = counters && G <= DY_GMAX;      // the pre-pass's last workgroup per item chains the segments: no chain launch
+    dispatch_mode(mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        hipLaunchKernelGGL((dyn_fwd_kernel<M, kDWF, 2>), grid, block, 0, st, x, ctl, (float*)nullptr, (float*)nullptr, (float*)nullptr, C, (int)N, nt,
+                           vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)nullptr, z, self_chain ? counters : (int*)nullptr,
+                           self_chain ? start : (float*)nullptr);
+        if (!self_chain)
+            hipLaunchKernelGGL(dyn_chain_kernel, dim3((B + 63) / 64), dim3(64), 0, st, ctl, (const float*)z, start, B, G, (long)Tseg * DY_TS,
+                               sample_rate, 0);
+        hipLaunchKernelGGL((dyn_fwd_kernel<M, kDWF, 1>), grid, block, 0, st, x, ctl, y, carries, lb, C, (int)N, nt, vec, lookahead, sample_rate, eps,
+                           G, (int)Tseg, (const float*)start, (float*)nullptr);
+    });
     return dy_check();
 }
 
-static int dynamics_backward_seg_impl(int mode, const float* x, const DynCtl ctl, const float* gy, const float* carries, const float* lin_buf,
-                                      float* gx, const DynGrad gctl, float* partials, float* segbuf, int B, int C, long N, double sample_rate, float eps,
-                                      int lookahead, long Tseg, int* counters, void* stream) {
-    if (!x || !ctl.p[0] || !gy || !carries || !gx || !gctl.p[0] || !partials || !segbuf || B <= 0 || C <= 0 || N <= 0 || lookahead < 0 ||
-        (mode != 0 && mode != 1) || Tseg <= 0)
+// Tseg as above; with counters the adjoint pass's last workgroup per item forms the control gradients (two launches instead of four),
+// otherwise - and for Tseg <= 0 - dyn_finalize_kernel does.
+static int dynamics_backward_impl(int mode, const float* x, const DynCtl ctl, const float* gy, const float* carries, const float* lin_buf,
+                                  float* gx, const DynGrad gctl, float* partials, float* segbuf, int B, int C, long N, double sample_rate, float eps,
+                                  int lookahead, long Tseg, int* counters, void* stream) {
+    if (!x || !ctl.p[0] || !gy || !carries || !gx || !gctl.p[0] || !partials || (Tseg > 0 && !segbuf) || B <= 0 || C <= 0 || N <= 0 || lookahead < 0 ||
+        (mode != 0 && mode != 1))
         return DASP_ERR_ARG;
     if (lookahead > 0 && !lin_buf) return DASP_ERR_ARG;
     if (N > 0x7fffffffL - DY_TS) return DASP_ERR_UNSUPPORTED;
     const int nt = (int)dasp_dyn_num_tiles(N), G = (int)dasp_dyn_segments(N, Tseg);
     const int vec = (N % 4 == 0) && dy_al16(x) && dy_al16(gy) && dy_al16(gx);
     const bool dma = vec && lookahead == 0 && C <= 2;
-    float* z = segbuf;
-    float* start = segbuf + (size_t)B * G;
     hipStream_t st = (hipStream_t)stream;
-#define DASP_DYN_BWD_SEG(MODE_, DMA_)                                                                                                            \
-    hipLaunchKernelGGL((dyn_bwd_kernel<MODE_, kDW, DMA_, 2>), dim3(B * G), dim3(64 * kDW), 0, st, x, ctl, gy, carries, lin_buf, (float*)nullptr, \
-                       (float*)nullptr, C, (int)N, nt, vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)nullptr, z);               \
-    hipLaunchKernelGGL(dyn_chain_kernel, dim3((B + 63) / 64), dim3(64), 0, st, ctl, (const float*)z, start, B, G, (long)Tseg * DY_TS,            \
-                       sample_rate, 1);                                                                                                         \
-    hipLaunchKernelGGL((dyn_bwd_kernel<MODE_, kDW, DMA_, 1>), dim3(B * G), dim3(64 * kDW), 0, st, x, ctl, gy, carries, lin_buf, gx, partials,    \
-                       C, (int)N, nt, vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)start, (float*)nullptr)
-    /* counters: chain by the pre-pass's last workgroup per item, control gradients by the adjoint pass's - two launches instead of four */
-#define DASP_DYN_BWD_SEG2(MODE_, DMA_)                                                                                                           \
-    hipLaunchKernelGGL((dyn_bwd_kernel<MODE_, kDW, DMA_, 2>), dim3(B * G), dim3(64 * kDW), 0, st, x, ctl, gy, carries, lin_buf, (float*)nullptr, \
-                       (float*)nullptr, C, (int)N, nt, vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)nullptr, z, counters, start,\
-                       DynGrad{});                                                                                                              \
-    hipLaunchKernelGGL((dyn_bwd_kernel<MODE_, kDW, DMA_, 1>), dim3(B * G), dim3(64 * kDW), 0, st, x, ctl, gy, carries, lin_buf, gx, partials,    \
-                       C, (int)N, nt, vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)start, (float*)nullptr, counters,           \
-                       (float*)nullptr, gctl)
-    /* one launch (dyn_bwd_kernel<SEG = 3>): two tiles per backward wave, the LDS-ring variant; a workgroup needs the item's segments ABOVE
-       its own - workgroups with smaller indices or the up to seven right behind it (common.hpp lookback_bwd_segment) */
-    const void* lb_kernel = mode == 0 ? reinterpret_cast<const void*>(dyn_bwd_kernel<0, kDW, true, 3>) : reinterpret_cast<const void*>(dyn_bwd_kernel<1, kDW, true, 3>);
-    if (DASP_DYN_LOOKBACK && lookback_enabled() && counters && dma && Tseg == 2 * kDW && G <= DY_GMAX && !(reinterpret_cast<uintptr_t>(segbuf) & 7) &&
-        lookback_has_room(lb_kernel, 64 * kDW)) {
-        if (error_pending()) return DASP_ERR_DEVICE;
-        unsigned* err = error_words_device();
-        static std::atomic<unsigned> calls{0x6C8E9CF5u};
-        const unsigned tag = calls.fetch_add(0x9E3779B1u) | 1u;
-        if (mode == 0)
-            hipLaunchKernelGGL((dyn_bwd_kernel<0, kDW, true, 3>), dim3(B * G), dim3(64 * kDW), 0, st, x, ctl, gy, carries, lin_buf, gx, partials, C, (int)N, nt,
-                               vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)nullptr, segbuf, counters, (float*)nullptr, gctl, tag, err);
-        else
-            hipLaunchKernelGGL((dyn_bwd_kernel<1, kDW, true, 3>), dim3(B * G), dim3(64 * kDW), 0, st, x, ctl, gy, carries, lin_buf, gx, partials, C, (int)N, nt,
-                               vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)nullptr, segbuf, counters, (float*)nullptr, gctl, tag, err);
-        return dy_check();
+    const dim3 grid(B * G), block(64 * kDW);
+    if (Tseg <= 0) {
+        dispatch_mode_dma(mode, dma, [&](auto m, auto d) {
+            hipLaunchKernelGGL((dyn_bwd_kernel<decltype(m)::value, kDW, decltype(d)::value>), grid, block, 0, st, x, ctl, gy, carries, lin_buf, gx, partials,
+                               C, (int)N, nt, vec, lookahead, sample_rate, eps);
+        });
+    } else {
+        /* one launch (dyn_bwd_kernel<SEG = 3>): two tiles per backward wave, the LDS-ring variant; a workgroup needs the item's segments ABOVE
+           its own - workgroups with smaller indices or the up to seven right behind it (common.hpp lookback_bwd_segment) */
+        const void* lb_kernel = mode == 0 ? reinterpret_cast<const void*>(dyn_bwd_kernel<0, kDW, true, 3>) : reinterpret_cast<const void*>(dyn_bwd_kernel<1, kDW, true, 3>);
+        if (DASP_DYN_LOOKBACK && lookback_enabled() && counters && dma && Tseg == 2 * kDW && G <= DY_GMAX && !(reinterpret_cast<uintptr_t>(segbuf) & 7) &&
+            lookback_has_room(lb_kernel, 64 * kDW)) {
+            if (error_pending()) return DASP_ERR_DEVICE;
+            unsigned* err = error_words_device();
+            static std::atomic<unsigned> calls{0x6C8E9CF5u};
+            const unsigned tag = calls.fetch_add(0x9E3779B1u) | 1u;
+            dispatch_mode(mode, [&](auto m) {
+                hipLaunchKernelGGL((dyn_bwd_kernel<decltype(m)::value, kDW, true, 3>), grid, block, 0, st, x, ctl, gy, carries, lin_buf, gx, partials, C, (int)N, nt,
+                                   vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)nullptr, segbuf, counters, (float*)nullptr, gctl, tag, err);
+            });
+            return dy_check();
+        }
+        float* z = segbuf;
+        float* start = segbuf + (size_t)B * G;
+        const bool self_chain = counters && G <= DY_GMAX;  // chain by the pre-pass's last workgroup per item, control gradients by the adjoint pass's
+        int* cnt = self_chain ? counters : nullptr;
+        dispatch_mode_dma(mode, dma, [&](auto m, auto d) {
+            constexpr int M = decltype(m)::value;
+            constexpr bool D = decltype(d)::value;
+            hipLaunchKernelGGL((dyn_bwd_kernel<M, kDW, D, 2>), grid, block, 0, st, x, ctl, gy, carries, lin_buf, (float*)nullptr, (float*)nullptr, C, (int)N,
+                               nt, vec, lookahead, sample_rate, eps, G, (int)Tseg, (const float*)nullptr, z, cnt, self_chain ? start : (float*)nullptr,
+                               DynGrad{});
+            if (!self_chain)
+                hipLaunchKernelGGL(dyn_chain_kernel, dim3((B + 63) / 64), dim3(64), 0, st, ctl, (const float*)z, start, B, G, (long)Tseg * DY_TS,
+                                   sample_rate, 1);
+            hipLaunchKernelGGL((dyn_bwd_kernel<M, kDW, D, 1>), grid, block, 0, st, x, ctl, gy, carries, lin_buf, gx, partials, C, (int)N, nt, vec, lookahead,
+                               sample_rate, eps, G, (int)Tseg, (const float*)start, (float*)nullptr, cnt, (float*)nullptr, self_chain ? gctl : DynGrad{});
+        });
+        if (self_chain) return dy_check();
     }
-    if (counters && G <= DY_GMAX) {
-        if (mode == 0) { if (dma) { DASP_DYN_BWD_SEG2(0, true); } else { DASP_DYN_BWD_SEG2(0, false); } }
-        else { if (dma) { DASP_DYN_BWD_SEG2(1, true); } else { DASP_DYN_BWD_SEG2(1, false); } }
-        return dy_check();
-    }
-#undef DASP_DYN_BWD_SEG2
-    if (mode == 0) { if (dma) { DASP_DYN_BWD_SEG(0, true); } else { DASP_DYN_BWD_SEG(0, false); } }
-    else { if (dma) { DASP_DYN_BWD_SEG(1, true); } else { DASP_DYN_BWD_SEG(1, false); } }
-#undef DASP_DYN_BWD_SEG
-    int rc = dy_check();
+    const int rc = dy_check();
     if (rc != DASP_OK) return rc;
     hipLaunchKernelGGL(dyn_finalize_kernel, dim3((B + 3) / 4), dim3(256), 0, st, partials, ctl, B, kDW * G, sample_rate, gctl);
     return dy_check();
 }
 
-int dasp_dynamics_forward(int mode, const float* x, const float* ctl, float* y, float* carries, float* lin_buf, int B, int C, long N,
-                          double sample_rate, float eps, int lookahead, void* stream) {
+int dasp_dynamics_forward(int mode, const float* x, const float* ctl, float* y, float* carries, float* lin_buf, float* segbuf, int B,
+                          int C, long N, double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream) {
     if (!ctl) return DASP_ERR_ARG;
-    return dynamics_forward_impl(mode, x, dyn_ctl_rows(ctl), y, carries, lin_buf, B, C, N, sample_rate, eps, lookahead, stream);
+    return dynamics_forward_impl(mode, x, dyn_ctl_rows(ctl), y, carries, lin_buf, segbuf, B, C, N, sample_rate, eps, lookahead, Tseg, counters, stream);
 }
 int dasp_dynamics_backward(int mode, const float* x, const float* ctl, const float* gy, const float* carries, const float* lin_buf,
-                           float* gx, float* gctl, float* partials, int B, int C, long N, double sample_rate, float eps, int lookahead,
-                           void* stream) {
+                           float* gx, float* gctl, float* partials, float* segbuf, int B, int C, long N, double sample_rate, float eps,
+                           int lookahead, long Tseg, int* counters, void* stream) {
     if (!ctl || !gctl) return DASP_ERR_ARG;
-    return dynamics_backward_impl(mode, x, dyn_ctl_rows(ctl), gy, carries, lin_buf, gx, dyn_grad_rows(gctl), partials, B, C, N, sample_rate, eps, lookahead, stream);
-}
-int dasp_dynamics_forward_seg(int mode, const float* x, const float* ctl, float* y, float* carries, float* lin_buf, float* segbuf, int B,
-                              int C, long N, double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream) {
-    if (!ctl) return DASP_ERR_ARG;
-    return dynamics_forward_seg_impl(mode, x, dyn_ctl_rows(ctl), y, carries, lin_buf, segbuf, B, C, N, sample_rate, eps, lookahead, Tseg, counters, stream);
-}
-int dasp_dynamics_backward_seg(int mode, const float* x, const float* ctl, const float* gy, const float* carries, const float* lin_buf,
-                               float* gx, float* gctl, float* partials, float* segbuf, int B, int C, long N, double sample_rate, float eps,
-                               int lookahead, long Tseg, int* counters, void* stream) {
-    if (!ctl || !gctl) return DASP_ERR_ARG;
-    return dynamics_backward_seg_impl(mode, x, dyn_ctl_rows(ctl), gy, carries, lin_buf, gx, dyn_grad_rows(gctl), partials, segbuf, B, C, N, sample_rate, eps,
-                                      lookahead, Tseg, counters, stream);
+    return dynamics_backward_impl(mode, x, dyn_ctl_rows(ctl), gy, carries, lin_buf, gx, dyn_grad_rows(gctl), partials, segbuf, B, C, N, sample_rate, eps,
+                                  lookahead, Tseg, counters, stream);
 }
 
 /* functional.compressor / expander on the reference's own six control tensors (functional.py:275-286), no stacking launch in front of the
  * kernels and no transposition behind them: rows = 5 device vectors of B floats (threshold_db, ratio, attack_ms, knee_db, makeup_gain_db);
  * grows = 6 device vectors of B floats for the gradients in the reference's argument order (threshold_db, ratio, attack_ms, release_ms -
- * set to zero: it has no path to the output -, knee_db, makeup_gain_db). Tseg = 0: one workgroup per item (segbuf / counters unused),
- * else as dasp_dynamics_forward_seg / _backward_seg. */
+ * set to zero: it has no path to the output -, knee_db, makeup_gain_db). Tseg <= 0: one workgroup per item (segbuf / counters unused),
+ * else segmented, as dasp_dynamics_forward / _backward. */
 int dasp_dynamics_forward_rows(int mode, const float* x, const float* const* rows, float* y, float* carries, float* lin_buf, float* segbuf,
                                int B, int C, long N, double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream) {
     if (!rows) return DASP_ERR_ARG;
     for (int i = 0; i < 5; ++i) if (!rows[i]) return DASP_ERR_ARG;
     const DynCtl ctl = DynCtl{{rows[0], rows[1], rows[2], rows[3], rows[4]}, 1};
-    if (Tseg > 0) return dynamics_forward_seg_impl(mode, x, ctl, y, carries, lin_buf, segbuf, B, C, N, sample_rate, eps, lookahead, Tseg, counters, stream);
-    return dynamics_forward_impl(mode, x, ctl, y, carries, lin_buf, B, C, N, sample_rate, eps, lookahead, stream);
+    return dynamics_forward_impl(mode, x, ctl, y, carries, lin_buf, segbuf, B, C, N, sample_rate, eps, lookahead, Tseg, counters, stream);
 }
 int dasp_dynamics_backward_rows(int mode, const float* x, const float* const* rows, const float* gy, const float* carries, const float* lin_buf,
                                 float* gx, float* const* grows, float* partials, float* segbuf, int B, int C, long N, double sample_rate,
@@ -948,9 +923,7 @@ int dasp_dynamics_backward_rows(int mode, const float* x, const float* const* ro
     for (int i = 0; i < 6; ++i) if (!grows[i]) return DASP_ERR_ARG;
     const DynCtl ctl = DynCtl{{rows[0], rows[1], rows[2], rows[3], rows[4]}, 1};
     const DynGrad g = DynGrad{{grows[0], grows[1], grows[2], grows[4], grows[5]}, 1, grows[3]};
-    if (Tseg > 0)
-        return dynamics_backward_seg_impl(mode, x, ctl, gy, carries, lin_buf, gx, g, partials, segbuf, B, C, N, sample_rate, eps, lookahead, Tseg, counters, stream);
-    return dynamics_backward_impl(mode, x, ctl, gy, carries, lin_buf, gx, g, partials, B, C, N, sample_rate, eps, lookahead, stream);
+    return dynamics_backward_impl(mode, x, ctl, gy, carries, lin_buf, gx, g, partials, segbuf, B, C, N, sample_rate, eps, lookahead, Tseg, counters, stream);
 }
 
 }  // extern "C"

@@ -789,13 +789,19 @@ int dasp_reverb_filter_spectrum(const float* filters, int nb, int taps, void* Fs
  * exists: both output channels read the one row); noise (2B, nb, L+taps-1); Fspec (sizes[4] complex); gains, decays (B, nb); mix (B); y (B,2,N).
  * Saved for backward: H (sizes[7] complex), ir (sizes[8] floats: the impulse responses) and, when A is not NULL, A (sizes[6] complex: the column transforms of x; pass NULL when no
  * gradient is needed and they go to a chunk-sized scratch instead: W2, sizes[12] complex).
- * Scratch: W (sizes[12] complex), Ah (sizes[13] complex). */
-static int reverb_forward_impl(const float* x, const float* noise, unsigned long long seed, const unsigned long long* seed_dev, const void* Fspec, const float* gains,
-                               const float* decays, const float* mix, float* y, void* A, void* H, void* W, void* W2, void* Ah, float* ir, int B,
-                               int Cx, long N, int L, int taps, int nb, float decay_bound, void* stream) {
+ * Scratch: W (sizes[12] complex), Ah (sizes[13] complex).
+ * noise == NULL: the white noise is generated inside the filter-bank kernels from `seed` (the counter-based stream documented at the top of
+ * this file) instead of read from memory: nothing of size (2B, nb, L + taps - 1) exists. Forward and backward must be given the same seed.
+ * seed_dev (may be NULL): one 64-bit word in device memory that is ADDED to `seed` when the kernels run - a launch captured into a HIP graph
+ * has its by-value seed frozen, the word lets every replay draw new noise (the caller bumps it between replays). With noise both are ignored.
+ * dasp_reverb_noise writes the stream out in the reference's layout, out (2B, nb, L + taps - 1) - a test hook. */
+int dasp_reverb_forward(const float* x, const float* noise, unsigned long long seed, const unsigned long long* seed_dev, const void* Fspec, const float* gains,
+                        const float* decays, const float* mix, float* y, void* A, void* H, void* W, void* W2, void* Ah, float* ir, int B,
+                        int Cx, long N, int L, int taps, int nb, float decay_bound, void* stream) {
     if (!x || !Fspec || !gains || !decays || !mix || !y || (!A && !W2) || !H || !W || !Ah || !ir || B <= 0 || N <= 0 || L <= 0 || taps <= 0 ||
         nb <= 0 || nb > RV_BANDS_MAX)
         return DASP_ERR_ARG;
+    if (noise) { seed = 0ULL; seed_dev = nullptr; }
     RvDims d;
     if (Cx != 1 && Cx != 2) return DASP_ERR_ARG;
     if (!rv_dims(B, N, L, taps, &d)) return DASP_ERR_UNSUPPORTED;
@@ -842,13 +848,14 @@ static int reverb_forward_impl(const float* x, const float* noise, unsigned long
 /* Backward.  ir = the impulse responses the forward call left in its `ir` buffer (sizes[8] floats); gx (B,2,N) (mono input: the gradient
  * w.r.t. x is the sum of its two rows, left to the caller); ggain, gdecay (B, nb); gmix (B). x itself is not read (its column transforms A are).
  * Scratch: Ag, W (sizes[12] complex each), P (sizes[13] complex), gir (sizes[8] floats), part (sizes[11] floats), mix_part (sizes[10] floats). */
-static int reverb_backward_impl(const float* ir, const float* gy, const float* noise, unsigned long long seed, const unsigned long long* seed_dev, const void* Fspec, const float* gains,
-                                const float* decays, const float* mix, const void* A, const void* H, float* gx, float* ggain, float* gdecay,
-                                float* gmix, void* Ag, void* W, void* P, float* gir, float* part, float* mix_part, int B, int Cx, long N, int L,
-                                int taps, int nb, float decay_bound, void* stream) {
+int dasp_reverb_backward(const float* ir, const float* gy, const float* noise, unsigned long long seed, const unsigned long long* seed_dev, const void* Fspec, const float* gains,
+                         const float* decays, const float* mix, const void* A, const void* H, float* gx, float* ggain, float* gdecay,
+                         float* gmix, void* Ag, void* W, void* P, float* gir, float* part, float* mix_part, int B, int Cx, long N, int L,
+                         int taps, int nb, float decay_bound, void* stream) {
     if (!ir || !gy || !Fspec || !gains || !decays || !mix || !A || !H || !gx || !ggain || !gdecay || !gmix || !Ag || !W || !P ||
         !gir || !part || !mix_part || B <= 0 || N <= 0 || L <= 0 || taps <= 0 || nb <= 0 || nb > RV_BANDS_MAX)
         return DASP_ERR_ARG;
+    if (noise) { seed = 0ULL; seed_dev = nullptr; }
     RvDims d;
     if (Cx != 1 && Cx != 2) return DASP_ERR_ARG;
     if (!rv_dims(B, N, L, taps, &d)) return DASP_ERR_UNSUPPORTED;
@@ -886,37 +893,6 @@ static int reverb_backward_impl(const float* ir, const float* gy, const float* n
     return rv_check();
 }
 
-int dasp_reverb_forward(const float* x, const float* noise, const void* Fspec, const float* gains, const float* decays, const float* mix,
-                        float* y, void* A, void* H, void* W, void* W2, void* Ah, float* ir, int B, int Cx, long N, int L, int taps, int nb,
-                        float decay_bound, void* stream) {
-    if (!noise) return DASP_ERR_ARG;
-    return reverb_forward_impl(x, noise, 0ULL, nullptr, Fspec, gains, decays, mix, y, A, H, W, W2, Ah, ir, B, Cx, N, L, taps, nb, decay_bound, stream);
-}
-int dasp_reverb_backward(const float* ir, const float* gy, const float* noise, const void* Fspec, const float* gains, const float* decays,
-                         const float* mix, const void* A, const void* H, float* gx, float* ggain, float* gdecay, float* gmix,
-                         void* Ag, void* W, void* P, float* gir, float* part, float* mix_part, int B, int Cx, long N, int L, int taps, int nb,
-                         float decay_bound, void* stream) {
-    if (!noise) return DASP_ERR_ARG;
-    return reverb_backward_impl(ir, gy, noise, 0ULL, nullptr, Fspec, gains, decays, mix, A, H, gx, ggain, gdecay, gmix, Ag, W, P, gir, part, mix_part, B, Cx, N,
-                                L, taps, nb, decay_bound, stream);
-}
-/* The same two calls with the white noise generated inside the filter-bank kernels from `seed` (the counter-based stream documented at
- * the top of reverb.hip) instead of read from memory: nothing of size (2B, nb, L + taps - 1) exists. Forward and backward must be given
- * the same seed. seed_dev (may be NULL): one 64-bit word in device memory that is ADDED to `seed` when the kernels run - a launch captured
- * into a HIP graph has its by-value seed frozen, the word lets every replay draw new noise (the caller bumps it between replays).
- * dasp_reverb_noise writes the stream out in the reference's layout, out (2B, nb, L + taps - 1) - a test hook. */
-int dasp_reverb_forward_rng(const float* x, unsigned long long seed, const unsigned long long* seed_dev, const void* Fspec, const float* gains, const float* decays, const float* mix,
-                            float* y, void* A, void* H, void* W, void* W2, void* Ah, float* ir, int B, int Cx, long N, int L, int taps, int nb,
-                            float decay_bound, void* stream) {
-    return reverb_forward_impl(x, nullptr, seed, seed_dev, Fspec, gains, decays, mix, y, A, H, W, W2, Ah, ir, B, Cx, N, L, taps, nb, decay_bound, stream);
-}
-int dasp_reverb_backward_rng(const float* ir, const float* gy, unsigned long long seed, const unsigned long long* seed_dev, const void* Fspec, const float* gains, const float* decays,
-                             const float* mix, const void* A, const void* H, float* gx, float* ggain, float* gdecay, float* gmix,
-                             void* Ag, void* W, void* P, float* gir, float* part, float* mix_part, int B, int Cx, long N, int L, int taps, int nb,
-                             float decay_bound, void* stream) {
-    return reverb_backward_impl(ir, gy, nullptr, seed, seed_dev, Fspec, gains, decays, mix, A, H, gx, ggain, gdecay, gmix, Ag, W, P, gir, part, mix_part, B, Cx, N,
-                                L, taps, nb, decay_bound, stream);
-}
 int dasp_reverb_noise(unsigned long long seed, const unsigned long long* seed_dev, float* out, int B, int nb, long row_len, void* stream) {
     if (!out || B <= 0 || nb <= 0 || nb > RV_BANDS_MAX || row_len <= 0 || row_len >= (1L << 24) || (long)B * nb > 65535) return DASP_ERR_ARG;
     const unsigned gx = (unsigned)((row_len + 255) / 256 < 64 ? (row_len + 255) / 256 : 64);

@@ -5,7 +5,7 @@
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
-// g5 = dL/d(b0, b1, b2, a1, a2) of section k of the item (normalised coefficients) -> the requested gradients (mode as in dasp_sos_grad_finalize)
+// g5 = dL/d(b0, b1, b2, a1, a2) of section k of the item (normalised coefficients) -> the requested gradients (mode as in dasp_sos_grad_finalize_ex)
 struct EmitCoef { double a0, b[5], J[15]; };      // of one (item, section): a0 as given, the normalised coefficients, the design Jacobian (dtab)
 __device__ __forceinline__ EmitCoef load_emit_coef(const double* __restrict__ d) {
     EmitCoef e;

@@ -1606,15 +1606,10 @@ int dasp_sosfilt_backward_ex(const float* tab, int Bs, const float* x, const flo
     });
 }
 
-int dasp_sosfilt_backward(const float* tab, int Bs, const float* x, const float* gy, const float* carries, float* gx,
-                          float* partials, int B, int C, long N, int S, void* stream) {
-    if (!x || !carries || !gx || !partials) return DASP_ERR_ARG;
-    return dasp_sosfilt_backward_ex(tab, Bs, x, gy, carries, gx, partials, B, C, N, S, stream);
-}
-
 // mode 0: gout (B,S,6) = dL/dsos ; mode 1: gout (B,S,3) = dL/d(gain_db, cutoff_freq, q_factor); mode 2: the same as (3S, B) rows.
 // partials: one Gram matrix per (row, segment) - `segments` of them per row as written by the *_seg entry points, 1 for the plain ones.
-static int grad_finalize_impl(const double* dtab, int Bs, const float* partials, int B, int C, int S, int segments, int mode, float* gout, void* stream) {
+int dasp_sos_grad_finalize_ex(const double* dtab, int Bs, const float* partials, int B, int C, int S, int segments, int mode,
+                              float* gout, void* stream) {
     if (!dtab || !partials || !gout || B <= 0 || C <= 0 || (Bs != 1 && Bs != B) || mode < 0 || mode > 2 || segments <= 0)
         return DASP_ERR_ARG;
     return dispatch_S(S, [&](auto s) {
@@ -1625,17 +1620,7 @@ static int grad_finalize_impl(const double* dtab, int Bs, const float* partials,
     });
 }
 
-int dasp_sos_grad_finalize_ex(const double* dtab, int Bs, const float* partials, int B, int C, int S, int segments, int mode,
-                              float* gout, void* stream) {
-    return grad_finalize_impl(dtab, Bs, partials, B, C, S, segments, mode, gout, stream);
-}
-
-int dasp_sos_grad_finalize(const double* dtab, int Bs, const float* partials, int B, int C, int S, int mode,
-                           float* gout, void* stream) {
-    return grad_finalize_impl(dtab, Bs, partials, B, C, S, 1, mode, gout, stream);
-}
-
-// dasp_sosfilt_backward followed by dasp_sos_grad_finalize (same mode / gout) as one call (two launches: fusing the finalize step into the
+// dasp_sosfilt_backward_ex followed by dasp_sos_grad_finalize_ex (same mode / gout) as one call (two launches: fusing the finalize step into the
 // backward kernel of one-workgroup-per-row launches was measured at 2 - 3 us of 425 and is not built; segmented rows - dasp_peq_backward -
 // do finalize inside their launch).
 int dasp_sosfilt_backward_grads_ex(float* tab, const double* dtab, int Bs, const float* x, const float* gy, const float* carries,
@@ -1643,13 +1628,7 @@ int dasp_sosfilt_backward_grads_ex(float* tab, const double* dtab, int Bs, const
     if (mode < 0 || mode > 2 || (partials && (!dtab || !gout))) return DASP_ERR_ARG;
     const int rc = dasp_sosfilt_backward_ex(tab, Bs, x, gy, carries, gx, partials, B, C, N, S, stream);
     if (rc != DASP_OK || !partials) return rc;
-    return grad_finalize_impl(dtab, Bs, partials, B, C, S, 1, mode, gout, stream);
-}
-
-int dasp_sosfilt_backward_grads(float* tab, const double* dtab, int Bs, const float* x, const float* gy, const float* carries,
-                                float* gx, float* partials, int mode, float* gout, int B, int C, long N, int S, void* stream) {
-    if (!gx || !partials) return DASP_ERR_ARG;
-    return dasp_sosfilt_backward_grads_ex(tab, dtab, Bs, x, gy, carries, gx, partials, mode, gout, B, C, N, S, stream);
+    return dasp_sos_grad_finalize_ex(dtab, Bs, partials, B, C, S, 1, mode, gout, stream);
 }
 
 // ---- segmented rows -------------------------------------------------------------------------------------------------------------
@@ -1825,18 +1804,6 @@ int dasp_sosfilt_backward_seg_ex(const float* tab, const double* segtab, int Bs,
     return sosfilt_backward_seg_impl(tab, segtab, Bs, x, gy, carries, gx, partials, segbuf, B, C, N, S, Tseg, nullptr, 0, nullptr, stream);
 }
 
-int dasp_sosfilt_backward_seg(const float* tab, const double* segtab, int Bs, const float* x, const float* gy, const float* carries,
-                              float* gx, float* partials, float* segbuf, int B, int C, long N, int S, long Tseg, void* stream) {
-    if (!x || !carries || !gx || !partials) return DASP_ERR_ARG;
-    return dasp_sosfilt_backward_seg_ex(tab, segtab, Bs, x, gy, carries, gx, partials, segbuf, B, C, N, S, Tseg, stream);
-}
-
-// dasp_sos_grad_finalize for partial sums produced by dasp_sosfilt_backward_seg with `segments` segments per row
-int dasp_sos_grad_finalize_seg(const double* dtab, int Bs, const float* partials, int B, int C, int S, int segments, int mode,
-                               float* gout, void* stream) {
-    return grad_finalize_impl(dtab, Bs, partials, B, C, S, segments, mode, gout, stream);
-}
-
 // ---- one call per direction for functional.parametric_eq (functional.py:118-272) ------------------------------------------------------
 // Forward: RBJ design from the 3 S control vectors (dasp_peq_prepare_rows) + the cascade. Tseg > 0 takes the segmented-row path
 // (segtab / segbuf as for dasp_sosfilt_forward_seg; Tseg = dasp_sos_segment_tiles(B * C, N) or 0).
@@ -1876,13 +1843,9 @@ static int peq_prepare_norm_impl(const float* pn, int Bp, int S, const int* type
     });
 }
 /* Tseg > 0 (a power of two) with segtab: the design launch also leaves the segment transition matrices of dasp_sos_segment_prepare. */
-int dasp_peq_prepare_norm_seg(const float* pn, int Bp, int S, const int* types, double sample_rate, const double* lo, const double* span,
-                              unsigned* flag, float* tab, double* dtab, long Tseg, double* segtab, void* stream) {
-    return peq_prepare_norm_impl(pn, Bp, S, types, sample_rate, lo, span, flag, tab, dtab, Tseg, segtab, 0, stream);
-}
 int dasp_peq_prepare_norm(const float* pn, int Bp, int S, const int* types, double sample_rate, const double* lo, const double* span,
-                          unsigned* flag, float* tab, double* dtab, void* stream) {
-    return peq_prepare_norm_impl(pn, Bp, S, types, sample_rate, lo, span, flag, tab, dtab, 0, nullptr, 0, stream);
+                          unsigned* flag, float* tab, double* dtab, long Tseg, double* segtab, void* stream) {
+    return peq_prepare_norm_impl(pn, Bp, S, types, sample_rate, lo, span, flag, tab, dtab, Tseg, segtab, 0, stream);
 }
 int dasp_peq_forward_norm(const float* pn, int Bp, int S, const int* types, double sample_rate, const double* lo, const double* span,
                           unsigned* flag, float* tab, double* dtab, const float* x, float* y, float* carries, int B, int C, long N, long Tseg,
@@ -1893,7 +1856,7 @@ int dasp_peq_forward_norm(const float* pn, int Bp, int S, const int* types, doub
     return sosfilt_forward_lookback(tab, segtab, Bp, x, y, carries, segbuf, B, C, N, S, Tseg, stream);
 }
 
-// Backward of the same call: adjoint cascade + control gradients (mode as in dasp_sos_grad_finalize), the tables being the ones
+// Backward of the same call: adjoint cascade + control gradients (mode as in dasp_sos_grad_finalize_ex), the tables being the ones
 // dasp_peq_forward filled (designed cascade: the monic / identity kernel). gx == null: no input gradient; partials == null: none for
 // the controls. Tseg / segtab / segbuf as in the forward call (partials then hold dasp_sos_partial_floats(rows * segments, S) floats).
 int dasp_peq_backward(float* tab, const double* dtab, int Bp, const float* x, const float* gy, const float* carries, float* gx,
@@ -1905,7 +1868,7 @@ int dasp_peq_backward(float* tab, const double* dtab, int Bp, const float* x, co
     const int rc = sosfilt_backward_seg_impl(tab, segtab, Bp, x, gy, carries, gx, partials, segbuf, B, C, N, S, Tseg, fuse ? dtab : nullptr, mode,
                                              fuse ? gout : nullptr, stream);
     if (rc != DASP_OK || !partials || fuse) return rc;
-    return grad_finalize_impl(dtab, Bp, partials, B, C, S, (int)dasp_sos_segments(N, Tseg), mode, gout, stream);
+    return dasp_sos_grad_finalize_ex(dtab, Bp, partials, B, C, S, (int)dasp_sos_segments(N, Tseg), mode, gout, stream);
 }
 
 // ---- signal.biquad (dasp_pytorch/signal.py:242-306) ------------------------------------------------------------------------------

@@ -240,7 +240,7 @@ Tensor peq_norm_autograd(const Tensor& x, const Tensor& pn, double sample_rate, 
     return PeqNormFn::apply(x, pn, sample_rate, types.vec(), lo.vec(), span.vec(), range_flag);
 }
 
-// ---- compressor / expander on (bs, 5) control rows (ops.DynamicsCtlFunction; dasp_dynamics_forward(_seg) / _backward(_seg)) -------------
+// ---- compressor / expander on (bs, 5) control rows (ops.DynamicsCtlFunction; dasp_dynamics_forward / _backward) ---------------------------
 int64_t dyn_segment_tiles(int64_t B, int64_t N) {
     return g_dyn_tiles_override >= 0 ? g_dyn_tiles_override : dasp_dyn_segment_tiles(B, N);
 }
@@ -255,57 +255,69 @@ void dyn_check(const Tensor& x, const Tensor& ctl, int64_t mode, int64_t lookahe
     TORCH_CHECK(mode == 0 || mode == 1, "dasp::dynamics_ctl: mode 0 (compressor) or 1 (expander)");
     TORCH_CHECK(lookahead >= 0, "dasp::dynamics_ctl: lookahead_samples must be >= 0");
 }
+// One body for both forms of the controls: the (bs, 5) matrix `ctl` through dasp_dynamics_forward / _backward, or - `ctl` undefined - the
+// five vectors `five` through the _rows entry points. tseg = 0: one workgroup per item, no segment scratch and no counters.
 // -> y, carries, lin (the linear gain curve, kept only with a look-ahead delay)
-std::tuple<Tensor, Tensor, Tensor> dyn_forward(const Tensor& x, const Tensor& ctl, int64_t mode, double sample_rate, double eps, int64_t lookahead,
-                                               int64_t tseg, bool save) {
-    dyn_check(x, ctl, mode, lookahead);
+std::tuple<Tensor, Tensor, Tensor> dyn_forward_any(const Tensor& x, const Tensor& ctl, at::TensorList five, int64_t mode, double sample_rate, double eps,
+                                                   int64_t lookahead, int64_t tseg, bool save) {
     c10::DeviceGuard guard(x.device());
     const int64_t B = x.size(0), C = x.size(1), N = x.size(2);
-    const Tensor x32 = x.contiguous(), c32 = f32c(ctl);
+    const Tensor x32 = x.contiguous(), c32 = ctl.defined() ? f32c(ctl) : Tensor();
     Tensor y = at::empty_like(x32);
     Tensor carries = empty_f32(save && x32.numel() ? dasp_dyn_carry_floats(B, N) : 0, x32);
     Tensor lin = lookahead > 0 ? at::empty({B, N}, x32.options()) : at::empty({0}, x32.options());
     if (x32.numel() == 0) return {y, carries, lin};
-    if (tseg) {
-        Tensor segbuf = empty_f32(2 * B * dasp_dyn_segments(N, tseg), x32);
-        Tensor counters = dyn_counters(x32, B);
-        check_rc(dasp_dynamics_forward_seg((int)mode, x32.data_ptr<float>(), c32.data_ptr<float>(), y.data_ptr<float>(), fp(carries), fp(lin), fp(segbuf),
-                                           (int)B, (int)C, N, sample_rate, (float)eps, (int)lookahead, tseg, counters.data_ptr<int>(), stream_of(x32)),
-                 "dasp_dynamics_forward_seg");
-    } else {
-        check_rc(dasp_dynamics_forward((int)mode, x32.data_ptr<float>(), c32.data_ptr<float>(), y.data_ptr<float>(), fp(carries), fp(lin), (int)B, (int)C, N,
-                                       sample_rate, (float)eps, (int)lookahead, stream_of(x32)),
-                 "dasp_dynamics_forward");
-    }
+    const float* rows[5] = {};
+    if (!ctl.defined()) for (int i = 0; i < 5; ++i) rows[i] = five[i].data_ptr<float>();
+    Tensor segbuf = tseg ? empty_f32(2 * B * dasp_dyn_segments(N, tseg), x32) : Tensor();
+    Tensor counters = tseg ? dyn_counters(x32, B) : Tensor();
+    auto run = [&](auto entry, auto controls) {
+        return entry((int)mode, x32.data_ptr<float>(), controls, y.data_ptr<float>(), fp(carries), fp(lin), fp(segbuf), (int)B, (int)C, N, sample_rate, (float)eps,
+                     (int)lookahead, tseg, tseg ? counters.data_ptr<int>() : nullptr, stream_of(x32));
+    };
+    if (ctl.defined()) check_rc(run(dasp_dynamics_forward, c32.data_ptr<float>()), "dasp_dynamics_forward");
+    else check_rc(run(dasp_dynamics_forward_rows, rows), "dasp_dynamics_forward_rows");
     return {y, carries, lin};
+}
+// -> gx and the control gradients: (bs, 5) for the matrix, the rows of one (6, bs) tensor for the vectors. `op` names the op in the messages.
+std::tuple<Tensor, Tensor> dyn_backward_any(const char* op, const Tensor& x, const Tensor& ctl, at::TensorList five, const Tensor& gy, const Tensor& carries,
+                                            const Tensor& lin, int64_t mode, double sample_rate, double eps, int64_t lookahead, int64_t tseg) {
+    same_device(x, gy, "grad_output");
+    TORCH_CHECK(gy.sizes() == x.sizes(), "dasp::", op, ": grad_output ", gy.sizes(), " does not match x ", x.sizes());
+    c10::DeviceGuard guard(x.device());
+    const int64_t B = x.size(0), C = x.size(1), N = x.size(2);
+    const Tensor x32 = x.contiguous(), c32 = ctl.defined() ? f32c(ctl) : Tensor(), g32 = f32c(gy);
+    Tensor gx = at::empty_like(x32), gctl = ctl.defined() ? at::empty({B, 5}, x32.options()) : at::empty({6, B}, x32.options());
+    if (x32.numel() == 0) return {gx, gctl.zero_()};
+    TORCH_CHECK(carries.numel() >= dasp_dyn_carry_floats(B, N), "dasp::", op, ": `carries` does not belong to a forward call of this shape");
+    const long G = dasp_dyn_segments(N, tseg);
+    Tensor partials = empty_f32(dasp_dyn_partial_floats(B * G), x32);
+    const float* rows[5] = {};
+    float* grows[6] = {};
+    if (!ctl.defined()) {
+        for (int i = 0; i < 5; ++i) rows[i] = five[i].data_ptr<float>();
+        for (int i = 0; i < 6; ++i) grows[i] = gctl.data_ptr<float>() + i * B;
+    }
+    Tensor segbuf = tseg ? empty_f32(2 * B * G, x32) : Tensor();
+    Tensor counters = tseg ? dyn_counters(x32, B) : Tensor();
+    auto run = [&](auto entry, auto controls, auto grads) {
+        return entry((int)mode, x32.data_ptr<float>(), controls, g32.data_ptr<float>(), fp(carries), lookahead > 0 ? fp(lin) : nullptr, gx.data_ptr<float>(), grads,
+                     fp(partials), fp(segbuf), (int)B, (int)C, N, sample_rate, (float)eps, (int)lookahead, tseg, tseg ? counters.data_ptr<int>() : nullptr,
+                     stream_of(x32));
+    };
+    if (ctl.defined()) check_rc(run(dasp_dynamics_backward, c32.data_ptr<float>(), gctl.data_ptr<float>()), "dasp_dynamics_backward");
+    else check_rc(run(dasp_dynamics_backward_rows, rows, grows), "dasp_dynamics_backward_rows");
+    return {gx, gctl};
+}
+std::tuple<Tensor, Tensor, Tensor> dyn_forward(const Tensor& x, const Tensor& ctl, int64_t mode, double sample_rate, double eps, int64_t lookahead,
+                                               int64_t tseg, bool save) {
+    dyn_check(x, ctl, mode, lookahead);
+    return dyn_forward_any(x, ctl, {}, mode, sample_rate, eps, lookahead, tseg, save);
 }
 std::tuple<Tensor, Tensor> dyn_backward(const Tensor& x, const Tensor& ctl, const Tensor& gy, const Tensor& carries, const Tensor& lin, int64_t mode,
                                         double sample_rate, double eps, int64_t lookahead, int64_t tseg) {
     dyn_check(x, ctl, mode, lookahead);
-    same_device(x, gy, "grad_output");
-    TORCH_CHECK(gy.sizes() == x.sizes(), "dasp::_dynamics_backward: grad_output ", gy.sizes(), " does not match x ", x.sizes());
-    c10::DeviceGuard guard(x.device());
-    const int64_t B = x.size(0), C = x.size(1), N = x.size(2);
-    const Tensor x32 = x.contiguous(), c32 = f32c(ctl), g32 = f32c(gy);
-    Tensor gx = at::empty_like(x32), gctl = at::empty({B, 5}, x32.options());
-    if (x32.numel() == 0) return {gx, gctl.zero_()};
-    TORCH_CHECK(carries.numel() >= dasp_dyn_carry_floats(B, N), "dasp::_dynamics_backward: `carries` does not belong to a forward call of this shape");
-    const long G = dasp_dyn_segments(N, tseg);
-    Tensor partials = empty_f32(dasp_dyn_partial_floats(B * G), x32);
-    if (tseg) {
-        Tensor segbuf = empty_f32(2 * B * G, x32);
-        Tensor counters = dyn_counters(x32, B);
-        check_rc(dasp_dynamics_backward_seg((int)mode, x32.data_ptr<float>(), c32.data_ptr<float>(), g32.data_ptr<float>(), fp(carries), lookahead > 0 ? fp(lin) : nullptr,
-                                            gx.data_ptr<float>(), gctl.data_ptr<float>(), fp(partials), fp(segbuf), (int)B, (int)C, N, sample_rate, (float)eps,
-                                            (int)lookahead, tseg, counters.data_ptr<int>(), stream_of(x32)),
-                 "dasp_dynamics_backward_seg");
-    } else {
-        check_rc(dasp_dynamics_backward((int)mode, x32.data_ptr<float>(), c32.data_ptr<float>(), g32.data_ptr<float>(), fp(carries), lookahead > 0 ? fp(lin) : nullptr,
-                                        gx.data_ptr<float>(), gctl.data_ptr<float>(), fp(partials), (int)B, (int)C, N, sample_rate, (float)eps, (int)lookahead,
-                                        stream_of(x32)),
-                 "dasp_dynamics_backward");
-    }
-    return {gx, gctl};
+    return dyn_backward_any("_dynamics_backward", x, ctl, {}, gy, carries, lin, mode, sample_rate, eps, lookahead, tseg);
 }
 // The same on the reference's own six control tensors (functional.py:275-286), straight from where they lie: five device vectors in,
 // the six gradients as the rows of one (6, bs) tensor out (release_ms: zeros, written by the kernel) - no stacking launch in front of the
@@ -325,46 +337,12 @@ void dyn6_check(const Tensor& x, at::TensorList five, int64_t mode, int64_t look
 std::tuple<Tensor, Tensor, Tensor> dyn6_forward(const Tensor& x, at::TensorList five, int64_t mode, double sample_rate, double eps, int64_t lookahead,
                                                 int64_t tseg, bool save) {
     dyn6_check(x, five, mode, lookahead);
-    c10::DeviceGuard guard(x.device());
-    const int64_t B = x.size(0), C = x.size(1), N = x.size(2);
-    const Tensor x32 = x.contiguous();
-    Tensor y = at::empty_like(x32);
-    Tensor carries = empty_f32(save && x32.numel() ? dasp_dyn_carry_floats(B, N) : 0, x32);
-    Tensor lin = lookahead > 0 ? at::empty({B, N}, x32.options()) : at::empty({0}, x32.options());
-    if (x32.numel() == 0) return {y, carries, lin};
-    const float* rows[5];
-    for (int i = 0; i < 5; ++i) rows[i] = five[i].data_ptr<float>();
-    Tensor segbuf = tseg ? empty_f32(2 * B * dasp_dyn_segments(N, tseg), x32) : Tensor();
-    Tensor counters = tseg ? dyn_counters(x32, B) : Tensor();
-    check_rc(dasp_dynamics_forward_rows((int)mode, x32.data_ptr<float>(), rows, y.data_ptr<float>(), fp(carries), fp(lin), tseg ? fp(segbuf) : nullptr, (int)B, (int)C, N,
-                                        sample_rate, (float)eps, (int)lookahead, tseg, tseg ? counters.data_ptr<int>() : nullptr, stream_of(x32)),
-             "dasp_dynamics_forward_rows");
-    return {y, carries, lin};
+    return dyn_forward_any(x, Tensor(), five, mode, sample_rate, eps, lookahead, tseg, save);
 }
 std::tuple<Tensor, Tensor> dyn6_backward(const Tensor& x, at::TensorList five, const Tensor& gy, const Tensor& carries, const Tensor& lin, int64_t mode,
                                          double sample_rate, double eps, int64_t lookahead, int64_t tseg) {
     dyn6_check(x, five, mode, lookahead);
-    same_device(x, gy, "grad_output");
-    TORCH_CHECK(gy.sizes() == x.sizes(), "dasp::_dynamics6_backward: grad_output ", gy.sizes(), " does not match x ", x.sizes());
-    c10::DeviceGuard guard(x.device());
-    const int64_t B = x.size(0), C = x.size(1), N = x.size(2);
-    const Tensor x32 = x.contiguous(), g32 = f32c(gy);
-    Tensor gx = at::empty_like(x32), g6 = at::empty({6, B}, x32.options());
-    if (x32.numel() == 0) return {gx, g6.zero_()};
-    TORCH_CHECK(carries.numel() >= dasp_dyn_carry_floats(B, N), "dasp::_dynamics6_backward: `carries` does not belong to a forward call of this shape");
-    const long G = dasp_dyn_segments(N, tseg);
-    Tensor partials = empty_f32(dasp_dyn_partial_floats(B * G), x32);
-    const float* rows[5];
-    for (int i = 0; i < 5; ++i) rows[i] = five[i].data_ptr<float>();
-    float* grows[6];
-    for (int i = 0; i < 6; ++i) grows[i] = g6.data_ptr<float>() + i * B;
-    Tensor segbuf = tseg ? empty_f32(2 * B * G, x32) : Tensor();
-    Tensor counters = tseg ? dyn_counters(x32, B) : Tensor();
-    check_rc(dasp_dynamics_backward_rows((int)mode, x32.data_ptr<float>(), rows, g32.data_ptr<float>(), fp(carries), lookahead > 0 ? fp(lin) : nullptr, gx.data_ptr<float>(),
-                                         grows, fp(partials), tseg ? fp(segbuf) : nullptr, (int)B, (int)C, N, sample_rate, (float)eps, (int)lookahead, tseg,
-                                         tseg ? counters.data_ptr<int>() : nullptr, stream_of(x32)),
-             "dasp_dynamics_backward_rows");
-    return {gx, g6};
+    return dyn_backward_any("_dynamics6_backward", x, Tensor(), five, gy, carries, lin, mode, sample_rate, eps, lookahead, tseg);
 }
 Tensor dyn_device(const Tensor& x, const Tensor& ctl, int64_t mode, double sample_rate, double eps, int64_t lookahead) {
     dyn_check(x, ctl, mode, lookahead);
@@ -425,7 +403,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> eq_dyn_norm_forward(const Ten
     std::vector<int> ty(types.begin(), types.end());
     float* w = work32.data_ptr<float>();
     check_rc(dasp_peq_prepare_norm(pn32.data_ptr<float>(), (int)d.Bp, (int)d.S, ty.data(), sample_rate, lo.data(), span.data(), flag_ptr(range_flag, x32), w,
-                                   work64.data_ptr<double>(), stream_of(x32)),
+                                   work64.data_ptr<double>(), 0, nullptr, stream_of(x32)),
              "dasp_peq_prepare_norm");
     check_rc(dasp_chain_forward_saving(w, (int)d.Bp, x32.data_ptr<float>(), c32.data_ptr<float>(), y.data_ptr<float>(), yeq.data_ptr<float>(), w + n_tab,
                                        dcar.data_ptr<float>(), (int)d.B, (int)d.C, d.N, (int)d.S, (int)mode, sample_rate, (float)eps, stream_of(x32)),
@@ -557,7 +535,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> chain_controls_autograd(const Tensor&
     return {r[0], r[1], r[2], r[3]};
 }
 
-// ---- noise-shaped reverb on control matrices (ops.ReverbFunction; dasp_reverb_forward(_rng) / _backward(_rng)) ---------------------------
+// ---- noise-shaped reverb on control matrices (ops.ReverbFunction; dasp_reverb_forward / _backward) -------------------------------------------
 // noise: (2 bs, nb, L + taps - 1) or undefined = generated inside the filter-bank kernels from `seed` (+ the device word seed_offset);
 // fspec: dasp_reverb_filter_spectrum of the (nb, taps) bank (cached by the Python side); gains / decays (bs, nb), mix (bs).
 struct RvDims { int64_t B, C, N; long sizes[14]; };
@@ -600,18 +578,11 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> reverb_forward(const Tensor& x, const
     const Tensor g32 = f32c(gains), d32 = f32c(decays), m32 = f32c(mix.reshape({d.B}));
     Tensor A = cbuf(save ? d.sizes[6] : 0, x32), W2 = cbuf(save ? 0 : d.sizes[12], x32);
     Tensor W = cbuf(d.sizes[12], x32), H = cbuf(d.sizes[7], x32), Ah = cbuf(d.sizes[13], x32), ir = empty_f32(d.sizes[8], x32);
-    if (noise.has_value() && noise->defined()) {
-        const Tensor n32 = f32c(*noise);
-        check_rc(dasp_reverb_forward(x32.data_ptr<float>(), n32.data_ptr<float>(), fspec.data_ptr<float>(), g32.data_ptr<float>(), d32.data_ptr<float>(),
-                                     m32.data_ptr<float>(), y.data_ptr<float>(), fp(A), fp(H), fp(W), fp(W2), fp(Ah), fp(ir), (int)d.B, (int)d.C, d.N, (int)L, (int)taps,
-                                     (int)nb, (float)decay_bound, stream_of(x32)),
-                 "dasp_reverb_forward");
-    } else {
-        check_rc(dasp_reverb_forward_rng(x32.data_ptr<float>(), (unsigned long long)seed, seed_ptr(seed_offset), fspec.data_ptr<float>(), g32.data_ptr<float>(),
-                                         d32.data_ptr<float>(), m32.data_ptr<float>(), y.data_ptr<float>(), fp(A), fp(H), fp(W), fp(W2), fp(Ah), fp(ir), (int)d.B, (int)d.C,
-                                         d.N, (int)L, (int)taps, (int)nb, (float)decay_bound, stream_of(x32)),
-                 "dasp_reverb_forward_rng");
-    }
+    const Tensor n32 = noise.has_value() && noise->defined() ? f32c(*noise) : Tensor();       // undefined: a null pointer = generated from the seed
+    check_rc(dasp_reverb_forward(x32.data_ptr<float>(), fp(n32), (unsigned long long)seed, seed_ptr(seed_offset), fspec.data_ptr<float>(), g32.data_ptr<float>(),
+                                 d32.data_ptr<float>(), m32.data_ptr<float>(), y.data_ptr<float>(), fp(A), fp(H), fp(W), fp(W2), fp(Ah), fp(ir), (int)d.B, (int)d.C,
+                                 d.N, (int)L, (int)taps, (int)nb, (float)decay_bound, stream_of(x32)),
+             "dasp_reverb_forward");
     return {y, A, H, ir};
 }
 // -> gx (bs, Cx, N), ggain (bs, nb), gdecay (bs, nb), gmix (bs)
@@ -632,20 +603,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> reverb_backward(const Tensor& gy, con
     Tensor gx = at::empty({B, 2, N}, o);
     Tensor Ag = cbuf(sizes[12], g32), W = cbuf(sizes[12], g32), P = cbuf(sizes[13], g32);
     Tensor gir = empty_f32(sizes[8], g32), part = empty_f32(sizes[11], g32), mix_part = empty_f32(sizes[10], g32);
-    if (noise.has_value() && noise->defined()) {
-        const Tensor n32 = f32c(*noise);
-        check_rc(dasp_reverb_backward(ir.data_ptr<float>(), g32.data_ptr<float>(), n32.data_ptr<float>(), fspec.data_ptr<float>(), ga.data_ptr<float>(), de.data_ptr<float>(),
-                                      mi.data_ptr<float>(), A.data_ptr<float>(), H.data_ptr<float>(), gx.data_ptr<float>(), ggain.data_ptr<float>(), gdecay.data_ptr<float>(),
-                                      gmix.data_ptr<float>(), fp(Ag), fp(W), fp(P), fp(gir), fp(part), fp(mix_part), (int)B, (int)Cx, N, (int)L, (int)taps, (int)nb,
-                                      (float)decay_bound, stream_of(g32)),
-                 "dasp_reverb_backward");
-    } else {
-        check_rc(dasp_reverb_backward_rng(ir.data_ptr<float>(), g32.data_ptr<float>(), (unsigned long long)seed, seed_ptr(seed_offset), fspec.data_ptr<float>(),
-                                          ga.data_ptr<float>(), de.data_ptr<float>(), mi.data_ptr<float>(), A.data_ptr<float>(), H.data_ptr<float>(), gx.data_ptr<float>(),
-                                          ggain.data_ptr<float>(), gdecay.data_ptr<float>(), gmix.data_ptr<float>(), fp(Ag), fp(W), fp(P), fp(gir), fp(part), fp(mix_part),
-                                          (int)B, (int)Cx, N, (int)L, (int)taps, (int)nb, (float)decay_bound, stream_of(g32)),
-                 "dasp_reverb_backward_rng");
-    }
+    const Tensor n32 = noise.has_value() && noise->defined() ? f32c(*noise) : Tensor();
+    check_rc(dasp_reverb_backward(ir.data_ptr<float>(), g32.data_ptr<float>(), fp(n32), (unsigned long long)seed, seed_ptr(seed_offset), fspec.data_ptr<float>(),
+                                  ga.data_ptr<float>(), de.data_ptr<float>(), mi.data_ptr<float>(), A.data_ptr<float>(), H.data_ptr<float>(), gx.data_ptr<float>(),
+                                  ggain.data_ptr<float>(), gdecay.data_ptr<float>(), gmix.data_ptr<float>(), fp(Ag), fp(W), fp(P), fp(gir), fp(part), fp(mix_part),
+                                  (int)B, (int)Cx, N, (int)L, (int)taps, (int)nb, (float)decay_bound, stream_of(g32)),
+             "dasp_reverb_backward");
     if (Cx == 1) gx = gx.sum(1, /*keepdim=*/true);             // the adjoint of the mono -> stereo duplication (functional.py:493-495)
     return {gx, ggain, gdecay, gmix};
 }

@@ -89,33 +89,21 @@ int dasp_peq_prepare_rows(const float* const* rows, int Bs, int S, const int* ty
 int dasp_sosfilt_forward(const float* tab, int Bs, const float* x, float* y, float* carries,
                          int B, int C, long N, int S, void* stream);
 
-/* gx = adjoint cascade(gy); partials receives what dasp_sos_grad_finalize turns into the coefficient gradients (per row: the matrix
- * sum over chunks of [gy chunk; adjoint state] [x chunk; forward state]^T, accumulated on the matrix cores: csrc/sosfilt.hip sos_bwd_gram_kernel). */
-int dasp_sosfilt_backward(const float* tab, int Bs, const float* x, const float* gy,
-                          const float* carries, float* gx, float* partials,
-                          int B, int C, long N, int S, void* stream);
-
-/* mode 0: gout (B, S, 6) = dL/dsos;  mode 1: gout (B, S, 3) = dL/d[gain_db, cutoff_freq, q_factor].
- * With Bs == 1 the caller sums gout over the batch. */
-int dasp_sos_grad_finalize(const double* dtab, int Bs, const float* partials, int B, int C, int S,
-                           int mode, float* gout, void* stream);
-
-/* dasp_sosfilt_backward followed by dasp_sos_grad_finalize (same mode / gout) as one call - the autograd of
- * signal.sosfilt_via_fsm (dasp_pytorch/signal.py:136-166) / functional.parametric_eq (functional.py:118-272) in one step.
- * Two launches at one workgroup per row (the segmented forms - dasp_peq_backward - finalize inside their launch and count an item's
- * workgroups in the item's table: hence the non-const tab; the count is left at zero). */
-int dasp_sosfilt_backward_grads(float* tab, const double* dtab, int Bs, const float* x, const float* gy,
-                                const float* carries, float* gx, float* partials, int mode, float* gout,
-                                int B, int C, long N, int S, void* stream);
+/* gx = adjoint cascade(gy) (dasp_sosfilt_backward_ex); partials receives what dasp_sos_grad_finalize_ex turns into the coefficient gradients
+ * (per row: the matrix sum over chunks of [gy chunk; adjoint state] [x chunk; forward state]^T, accumulated on the matrix cores:
+ * csrc/sosfilt.hip sos_bwd_gram_kernel). dasp_sos_grad_finalize_ex: mode 0: gout (B, S, 6) = dL/dsos;  mode 1: gout (B, S, 3) =
+ * dL/d[gain_db, cutoff_freq, q_factor]. With Bs == 1 the caller sums gout over the batch.
+ * dasp_sosfilt_backward_grads_ex: the two (same mode / gout) as one call - the autograd of signal.sosfilt_via_fsm
+ * (dasp_pytorch/signal.py:136-166) / functional.parametric_eq (functional.py:118-272) in one step. Two launches at one workgroup per row
+ * (the segmented forms - dasp_peq_backward - finalize inside their launch and count an item's workgroups in the item's table: hence the
+ * non-const tab; the count is left at zero). The _ex suffix of the three is historical: they are the only forms. */
 
 /* The backward pass as asked for (torch.autograd's needs_input_grad) and for the cascade it is:
  *   gx == NULL        no input gradient: the adjoint output is neither transposed back nor stored (parametric_eq is the first effect of
  *                     the reference's chain, examples/style_transfer.py:150 - its input never needs one);
  *   partials == NULL  no coefficient gradients (a fixed filter): x and carries are not read, only the adjoint cascade runs.
- * (Rounds 3 - 5 carried an `int designed` in these signatures that had been ignored since the Gram-matrix backward; round 6 dropped it -
- * the ABI hash changed with it.)
- * dasp_sos_grad_finalize_ex: segments = rows of partial sums per (row, wave) (1 after dasp_sosfilt_backward*, dasp_sos_segments(N, Tseg)
- * after the *_seg calls); mode 2 = mode 1 written as 3*S rows of B values ([3 k + c][item]: one contiguous vector per control tensor). */
+ * dasp_sos_grad_finalize_ex: segments = rows of partial sums per (row, wave) (1 after dasp_sosfilt_backward_ex, dasp_sos_segments(N, Tseg)
+ * after dasp_sosfilt_backward_seg_ex); mode 2 = mode 1 written as 3*S rows of B values ([3 k + c][item]: one contiguous vector per control tensor). */
 int dasp_sosfilt_backward_ex(const float* tab, int Bs, const float* x, const float* gy, const float* carries, float* gx,
                              float* partials, int B, int C, long N, int S, void* stream);
 int dasp_sos_grad_finalize_ex(const double* dtab, int Bs, const float* partials, int B, int C, int S, int segments, int mode,
@@ -140,12 +128,10 @@ int dasp_peq_forward_norm(const float* pn, int Bp, int S, const int* types, doub
 int dasp_peq_backward(float* tab, const double* dtab, int Bp, const float* x, const float* gy, const float* carries, float* gx,
                       float* partials, int mode, float* gout, int B, int C, long N, int S, long Tseg, const double* segtab,
                       float* segbuf, void* stream);
-/* The design step of dasp_peq_forward_norm on its own: tables from the normalised (Bp, 3 S) tensor, no cascade. */
+/* The design step of dasp_peq_forward_norm on its own: tables from the normalised (Bp, 3 S) tensor, no cascade. Tseg <= 0 and segtab == NULL:
+ * tables only; Tseg > 0 (a power of two) with segtab: also the segment transition matrices of dasp_sos_segment_prepare, from the same launch. */
 int dasp_peq_prepare_norm(const float* pn, int Bp, int S, const int* types, double sample_rate, const double* lo, const double* span,
-                          unsigned* flag, float* tab, double* dtab, void* stream);
-/* ... and, with Tseg > 0 (a power of two) and segtab, also the segment transition matrices of dasp_sos_segment_prepare, from the same launch. */
-int dasp_peq_prepare_norm_seg(const float* pn, int Bp, int S, const int* types, double sample_rate, const double* lo, const double* span,
-                              unsigned* flag, float* tab, double* dtab, long Tseg, double* segtab, void* stream);
+                          unsigned* flag, float* tab, double* dtab, long Tseg, double* segtab, void* stream);
 /* The first two launches of dasp_sosfilt_forward_seg on their own (scan-only pre-pass + chain): afterwards the second half of segbuf
  * (dasp_sos_seg_floats floats) holds the state every (row, segment) starts from, [row][segment][2 S]. */
 int dasp_sos_segment_starts(const float* tab, const double* segtab, int Bs, const float* x, float* segbuf, int B, int C, long N, int S,
@@ -167,7 +153,7 @@ long dasp_chain_seg_floats(long B, long C, long N, int S, long Tseg);
 int dasp_chain_forward(const float* tab, int Bs, const float* x, const float* ctl, float* y, int B, int C, long N, int S, int mode,
                        double sample_rate, float eps, long Tseg, const double* segtab, float* segbuf, void* stream);
 /* The same pass for the step that carries gradients: also writes the EQ's output yeq (B, C, N) - the input of dasp_dynamics_backward -, the
- * EQ's chunk start states eq_carries (dasp_sos_carry_floats(B * C, N, S) floats, for dasp_peq_backward / dasp_sosfilt_backward*) and the
+ * EQ's chunk start states eq_carries (dasp_sos_carry_floats(B * C, N, S) floats, for dasp_peq_backward / dasp_sosfilt_backward_ex) and the
  * smoothing state entering every compressor tile dyn_carries (dasp_dyn_carry_floats(B, N) floats): 15 B per channel-sample instead of 19
  * for the two forward calls. One workgroup per item (no segments); pays from ~200 items on (profiles/r06/chain_fwd_saving_ab.log). */
 int dasp_chain_forward_saving(const float* tab, int Bs, const float* x, const float* ctl, float* y, float* yeq, float* eq_carries,
@@ -184,7 +170,7 @@ int dasp_biquad_backward(const double* jac, const double* gba, int n, double* gp
 /* Few rows (B*C <= 128; from there up to 256 rows the plain calls launch twice the waves per row instead): a row is one workgroup, so the calls above
  * would leave most of the chip idle. The *_seg entry points cut every row into segments of Tseg tiles that run as independent workgroups;
  * same results (oracle/chunkscan_model.py forward_row_segmented / backward_row_segmented).
- *   dasp_sosfilt_forward_seg / dasp_sosfilt_backward_seg[_ex] (tables that may serve many calls): per direction a scan-only pre-pass gives
+ *   dasp_sosfilt_forward_seg / dasp_sosfilt_backward_seg_ex (tables that may serve many calls): per direction a scan-only pre-pass gives
  *     every segment's end state, the last of an item's workgroups to finish chains them through Phi^(samples per segment)
  *     (dasp_sos_segment_prepare, from dtab; the completion counters are words of the item's table, zeroed by the prepare call and reset
  *     after use - the one place where a call writes into `tab`), then the ordinary pass runs per segment from its start state.
@@ -197,7 +183,7 @@ int dasp_biquad_backward(const double* jac, const double* gba, int n, double* gp
  *   segtab = dasp_sos_segtab_doubles(S) doubles per item (Bs items): the two segment transition matrices + the basis responses of the Gram
  *            finalize step (filled by the design launch of dasp_peq_forward*);  segbuf = dasp_sos_seg_floats(rows, N, S, Tseg) floats of scratch
  *   partials of the backward pass: dasp_sos_partial_floats(rows * dasp_sos_segments(N, Tseg), S) floats, finalized by
- *   dasp_sos_grad_finalize_seg(..., segments = dasp_sos_segments(N, Tseg), ...) after dasp_sosfilt_backward_seg*. */
+ *   dasp_sos_grad_finalize_ex(..., segments = dasp_sos_segments(N, Tseg), ...) after dasp_sosfilt_backward_seg_ex. */
 long dasp_sos_segment_tiles(long rows, long N);
 long dasp_sos_segments(long N, long Tseg);
 long dasp_sos_segtab_doubles(int S);
@@ -205,14 +191,9 @@ long dasp_sos_seg_floats(long rows, long N, int S, long Tseg);
 int dasp_sos_segment_prepare(const double* dtab, int Bs, int S, long Tseg, double* segtab, void* stream);
 int dasp_sosfilt_forward_seg(const float* tab, const double* segtab, int Bs, const float* x, float* y, float* carries,
                              float* segbuf, int B, int C, long N, int S, long Tseg, void* stream);
-int dasp_sosfilt_backward_seg(const float* tab, const double* segtab, int Bs, const float* x, const float* gy,
-                              const float* carries, float* gx, float* partials, float* segbuf,
-                              int B, int C, long N, int S, long Tseg, void* stream);
 int dasp_sosfilt_backward_seg_ex(const float* tab, const double* segtab, int Bs, const float* x, const float* gy,
                                  const float* carries, float* gx, float* partials, float* segbuf,
                                  int B, int C, long N, int S, long Tseg, void* stream);
-int dasp_sos_grad_finalize_seg(const double* dtab, int Bs, const float* partials, int B, int C, int S, int segments,
-                               int mode, float* gout, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * gain / distortion.  Replace dasp_pytorch.functional.gain (dasp_pytorch/functional.py:10-29):
@@ -266,30 +247,25 @@ long dasp_dyn_num_tiles(long N);
 long dasp_dyn_carry_floats(long B, long N);
 long dasp_dyn_partial_floats(long B);
 int dasp_dyn_counters_reset(int* counters, int B, void* stream);
-int dasp_dynamics_forward(int mode, const float* x, const float* ctl, float* y, float* carries, float* lin_buf,
-                          int B, int C, long N, double sample_rate, float eps, int lookahead, void* stream);
-int dasp_dynamics_backward(int mode, const float* x, const float* ctl, const float* gy, const float* carries,
-                           const float* lin_buf, float* gx, float* gctl, float* partials, int B, int C, long N,
-                           double sample_rate, float eps, int lookahead, void* stream);
-
 /* Few batch items (B < 128; the reference trains with 8 to 32: examples/style_transfer.py:403, auto_eq.py:231): one workgroup per item
- * would leave most of the chip idle, so every item is cut into segments of Tseg tiles that run as independent workgroups - scan-only
+ * would leave most of the chip idle, so every item can be cut into segments of Tseg tiles that run as independent workgroups - scan-only
  * pre-pass, a scalar chain through alpha^(samples per segment) in fp64, then the ordinary pass per segment; same results.
- *   Tseg = dasp_dyn_segment_tiles(B, N) (a power of two; 0 = use the plain calls); segbuf = 2 * B * dasp_dyn_segments(N, Tseg) floats of
- *   scratch; carries as above; partials of the backward pass: dasp_dyn_partial_floats(B * dasp_dyn_segments(N, Tseg)) floats. */
+ *   Tseg = dasp_dyn_segment_tiles(B, N) (a power of two); Tseg <= 0 = one workgroup per item: segbuf and counters are then unused and may
+ *   be NULL, partials as above. Tseg > 0: segbuf = 2 * B * dasp_dyn_segments(N, Tseg) floats of scratch; carries as above; partials of the
+ *   backward pass: dasp_dyn_partial_floats(B * dasp_dyn_segments(N, Tseg)) floats; counters: below. */
 long dasp_dyn_segment_tiles(long B, long N);
 long dasp_dyn_segments(long N, long Tseg);
-int dasp_dynamics_forward_seg(int mode, const float* x, const float* ctl, float* y, float* carries, float* lin_buf, float* segbuf,
-                              int B, int C, long N, double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream);
-int dasp_dynamics_backward_seg(int mode, const float* x, const float* ctl, const float* gy, const float* carries,
-                               const float* lin_buf, float* gx, float* gctl, float* partials, float* segbuf, int B, int C, long N,
-                               double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream);
+int dasp_dynamics_forward(int mode, const float* x, const float* ctl, float* y, float* carries, float* lin_buf, float* segbuf,
+                          int B, int C, long N, double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream);
+int dasp_dynamics_backward(int mode, const float* x, const float* ctl, const float* gy, const float* carries,
+                           const float* lin_buf, float* gx, float* gctl, float* partials, float* segbuf, int B, int C, long N,
+                           double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream);
 /* functional.compressor / expander on the reference's own six control tensors (dasp_pytorch/functional.py:275-286), without a stacking
  * launch in front of the kernels or a transposition behind them: rows = 5 device vectors of B floats (threshold_db, ratio, attack_ms,
  * knee_db, makeup_gain_db; the array of pointers itself is host memory), grows = 6 device vectors of B floats that receive the gradients
  * in the reference's argument order (threshold_db, ratio, attack_ms, release_ms - set to zero: it has no path to the output,
- * functional.py:340,343-344 -, knee_db, makeup_gain_db). Tseg = 0: one workgroup per item (segbuf / counters unused), otherwise as the
- * *_seg calls above. Everything else as dasp_dynamics_forward / _backward. */
+ * functional.py:340,343-344 -, knee_db, makeup_gain_db). Everything else, Tseg, segbuf and counters included, as dasp_dynamics_forward /
+ * _backward. */
 int dasp_dynamics_forward_rows(int mode, const float* x, const float* const* rows, float* y, float* carries, float* lin_buf, float* segbuf,
                                int B, int C, long N, double sample_rate, float eps, int lookahead, long Tseg, int* counters, void* stream);
 int dasp_dynamics_backward_rows(int mode, const float* x, const float* const* rows, const float* gy, const float* carries,
@@ -350,34 +326,27 @@ int dasp_reverb_filter_spectrum(const float* filters, int nb, int taps, void* Fs
  * Ag, W, P, gir, part, mix_part are scratch. Neither the wet signal nor x is needed for d loss / d mix = sum_n gy (wet - x):
  * sum_n gy wet = sum_r ir[r] c[r] and sum_n gy x = c[0] with c[r] = sum_n gy[n] x[n - r], r < L - the correlation the pass forms for
  * d loss / d ir anyway. */
-int dasp_reverb_forward(const float* x, const float* noise, const void* Fspec, const float* gains, const float* decays,
-                        const float* mix, float* y, void* A, void* H, void* W, void* W2, void* Ah, float* ir, int B, int Cx,
-                        long N, int L, int taps, int nb, float decay_bound, void* stream);
-int dasp_reverb_backward(const float* ir, const float* gy, const float* noise, const void* Fspec, const float* gains,
-                         const float* decays, const float* mix, const void* A, const void* H, float* gx,
-                         float* ggain, float* gdecay, float* gmix, void* Ag, void* W, void* P, float* gir, float* part,
+int dasp_reverb_forward(const float* x, const float* noise, unsigned long long seed, const unsigned long long* seed_dev, const void* Fspec,
+                        const float* gains, const float* decays, const float* mix, float* y, void* A, void* H, void* W, void* W2, void* Ah,
+                        float* ir, int B, int Cx, long N, int L, int taps, int nb, float decay_bound, void* stream);
+int dasp_reverb_backward(const float* ir, const float* gy, const float* noise, unsigned long long seed, const unsigned long long* seed_dev,
+                         const void* Fspec, const float* gains, const float* decays, const float* mix, const void* A, const void* H,
+                         float* gx, float* ggain, float* gdecay, float* gmix, void* Ag, void* W, void* P, float* gir, float* part,
                          float* mix_part, int B, int Cx, long N, int L, int taps, int nb, float decay_bound, void* stream);
 /* Cx: channels of x, 2, or 1 for a mono input (the reference duplicates it to stereo, functional.py:493-495: here both output channels read
  * the one row - no copy; gx stays (B, 2, N), the gradient w.r.t. the mono input is the sum of its two rows).
  * decay_bound: > 0 = the caller vouches that no band decay exceeds this value (Processor.process_normalized: the validated upper end of the
  * parameter range); when even that decay stays on the envelope-inside-the-transform route of the filter bank, the other route's (empty) launch
  * is skipped. 0 = unknown.
- * The same two calls with the white noise of functional.py:548 generated inside the filter-bank kernels from a 64-bit seed instead of read
- * from memory (the `device_noise=True` mode of the Python layer): a counter-based stream, a pure function of (seed, batch item, band,
+ * noise != NULL: the white noise of functional.py:548 is read from memory; seed and seed_dev are ignored. noise == NULL: it is generated
+ * inside the filter-bank kernels from the 64-bit seed (the `device_noise=True` mode of the Python layer): a counter-based stream, a pure function of (seed, batch item, band,
  * sample index) - one 32-bit hash per (item, band, index), its halves a Box-Muller pair = the item's two noise rows - so the forward and
  * the backward pass recompute identical values and nothing of size (2B, nb, L + taps - 1) exists (0.82 GB at B = 128 and the default
  * sizes, which torch.randn wrote once and the two filter-bank kernels read once each). Both calls of a step take the same seed.
  * seed_dev (may be NULL): one 64-bit device word added to `seed` when the kernels run - a launch captured into a HIP graph has its by-value
  * seed frozen; bumping the word between replays gives every replay new noise.
  * dasp_reverb_noise writes the stream out in the reference's layout, out (2B, nb, row_len), row_len = L + taps - 1 < 2^24: a test hook
- * (the explicit-noise calls above, given that tensor, must reproduce the seeded calls). Specification: oracle/noise_stream.py. */
-int dasp_reverb_forward_rng(const float* x, unsigned long long seed, const unsigned long long* seed_dev, const void* Fspec, const float* gains, const float* decays,
-                            const float* mix, float* y, void* A, void* H, void* W, void* W2, void* Ah, float* ir, int B, int Cx,
-                            long N, int L, int taps, int nb, float decay_bound, void* stream);
-int dasp_reverb_backward_rng(const float* ir, const float* gy, unsigned long long seed, const unsigned long long* seed_dev, const void* Fspec, const float* gains,
-                             const float* decays, const float* mix, const void* A, const void* H, float* gx,
-                             float* ggain, float* gdecay, float* gmix, void* Ag, void* W, void* P, float* gir, float* part,
-                             float* mix_part, int B, int Cx, long N, int L, int taps, int nb, float decay_bound, void* stream);
+ * (the calls above, given that tensor as noise, must reproduce the seeded calls). Specification: oracle/noise_stream.py. */
 int dasp_reverb_noise(unsigned long long seed, const unsigned long long* seed_dev, float* out, int B, int nb, long row_len, void* stream);
 
 /* ---------------------------------------------------------------------------------------------

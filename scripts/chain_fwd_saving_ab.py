@@ -42,7 +42,7 @@ yeq, y, yeq2, y2 = (torch.empty_like(x) for _ in range(4))
 
 def separate():
     _lib.call("dasp_peq_forward", rows, B, S, tys, SR, ptr(tab), ptr(dtab), ptr(x), ptr(yeq), ptr(car), B, C, N, 0, ptr(None), ptr(None), stream())
-    _lib.call("dasp_dynamics_forward", 0, ptr(yeq), ptr(ctl), ptr(y), ptr(dcar), ptr(None), B, C, N, SR, ctypes.c_float(1e-8), 0, stream())
+    _lib.call("dasp_dynamics_forward", 0, ptr(yeq), ptr(ctl), ptr(y), ptr(dcar), ptr(None), ptr(None), B, C, N, SR, ctypes.c_float(1e-8), 0, 0, ptr(None), stream())
 
 
 def fused():

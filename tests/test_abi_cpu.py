@@ -95,6 +95,39 @@ def test_argument_errors_without_gpu():
     assert L.dasp_mrstft_backward(None, None, None, None, None, None, None, 1, 4096, 0, None, None, None, 1e-8, 1.0, 1.0, 0.0, 0, 1, None) == -1
 
 
+REMOVED_EXPORTS = ("dasp_sosfilt_backward", "dasp_sos_grad_finalize", "dasp_sosfilt_backward_grads", "dasp_sosfilt_backward_seg",
+                   "dasp_sos_grad_finalize_seg", "dasp_peq_prepare_norm_seg", "dasp_dynamics_forward_seg", "dasp_dynamics_backward_seg",
+                   "dasp_reverb_forward_rng", "dasp_reverb_backward_rng")
+
+
+def test_alias_and_twin_exports_are_gone():
+    """The aliases of the *_ex biquad calls and the _seg / _rng twins of the dynamics, reverb and design calls were folded into the entry
+    points that stay: none of them is exported or bound any more."""
+    import ctypes
+    raw = ctypes.CDLL(_lib.lib()._name)            # a fresh handle: no attribute that an earlier lookup may have cached
+    for name in REMOVED_EXPORTS:
+        assert not hasattr(raw, name), name
+        assert name not in _lib.SIGNATURES and name not in _header_symbols(), name
+
+
+def test_folded_entry_points_check_their_arguments_without_gpu():
+    """The folded calls refuse inconsistent arguments before any launch (DASP_ERR_ARG = -1): segments asked for without their scratch,
+    a missing gradient buffer, a null input, a segment length that is no power of two. The non-null pointers are fakes, never read."""
+    import ctypes
+    L = _lib.lib()
+    f = 256                                        # a fake, 16-byte aligned, non-null device pointer
+    # dasp_dynamics_forward(mode, x, ctl, y, carries, lin_buf, segbuf, B, C, N, sample_rate, eps, lookahead, Tseg, counters, stream)
+    assert L.dasp_dynamics_forward(0, f, f, f, None, None, None, 2, 2, 65536, 44100.0, 1e-8, 0, 16, None, None) == -1       # Tseg = 16, segbuf = NULL
+    # dasp_dynamics_backward(mode, x, ctl, gy, carries, lin_buf, gx, gctl, partials, segbuf, B, C, N, sample_rate, eps, lookahead, Tseg, counters, stream)
+    assert L.dasp_dynamics_backward(0, f, f, f, f, None, f, None, f, None, 2, 2, 65536, 44100.0, 1e-8, 0, 0, None, None) == -1   # gctl = NULL
+    # dasp_reverb_forward(x = NULL, noise, seed, seed_dev, Fspec, gains, decays, mix, y, A, H, W, W2, Ah, ir, B, Cx, N, L, taps, nb, decay_bound, stream)
+    assert L.dasp_reverb_forward(None, None, 1, None, f, f, f, f, f, f, f, f, f, f, f, 2, 2, 9000, 1000, 63, 12, 0.0, None) == -1
+    # dasp_peq_prepare_norm(pn, Bp, S, types, sample_rate, lo, span, flag, tab, dtab, Tseg, segtab, stream)
+    types, lo, span = (ctypes.c_int * 6)(1, 0, 0, 0, 0, 2), (ctypes.c_double * 18)(), (ctypes.c_double * 18)()
+    assert L.dasp_peq_prepare_norm(f, 2, 6, types, 44100.0, lo, span, None, f, f, 8, None, None) == -1                      # Tseg = 8, segtab = NULL
+    assert L.dasp_peq_prepare_norm(f, 2, 6, types, 44100.0, lo, span, None, f, f, 6, f, None) == -1                         # Tseg = 6: no power of two
+
+
 def test_product_has_no_cpu_path():
     import dasp_pytorch_amd as D
     x = torch.zeros(1, 1, 64)

@@ -405,9 +405,9 @@ def test_needs_input_grad_selects_the_kernel_variant(D):
 
 @pytest.mark.parametrize("Bs_shared", [False, True])
 def test_backward_grads_entry_equals_two_calls(D, Bs_shared):
-    """dasp_sosfilt_backward_grads == dasp_sosfilt_backward followed by dasp_sos_grad_finalize, bit for bit (gx and all three
-    gradient layouts), with one table per item and with a table shared by the batch; the item counters it may use are left at zero
-    so the same table serves repeated backward passes."""
+    """dasp_sosfilt_backward_grads_ex == dasp_sosfilt_backward_ex followed by dasp_sos_grad_finalize_ex (segments = 1), bit for bit (gx
+    and all three gradient layouts), with one table per item and with a table shared by the batch; the item counters it may use are left
+    at zero so the same table serves repeated backward passes."""
     import ctypes
     from dasp_pytorch_amd import _lib
     from dasp_pytorch_amd._lib import call, ptr, stream
@@ -429,12 +429,12 @@ def test_backward_grads_entry_equals_two_calls(D, Bs_shared):
         part = torch.empty(L.dasp_sos_partial_floats(B * C, S), dtype=torch.float32, device="cuda:0")
         gx1, gx2 = torch.empty_like(x), torch.empty_like(x)
         g1, g2 = torch.zeros(shape, device="cuda:0"), torch.zeros(shape, device="cuda:0")
-        call("dasp_sosfilt_backward", ptr(tab), Bs, ptr(x), ptr(gy), ptr(car), ptr(gx1), ptr(part), B, C, N, S, stream())
-        call("dasp_sos_grad_finalize", ptr(dtab), Bs, ptr(part), B, C, S, mode, ptr(g1), stream())
+        call("dasp_sosfilt_backward_ex", ptr(tab), Bs, ptr(x), ptr(gy), ptr(car), ptr(gx1), ptr(part), B, C, N, S, stream())
+        call("dasp_sos_grad_finalize_ex", ptr(dtab), Bs, ptr(part), B, C, S, 1, mode, ptr(g1), stream())
         for _ in range(2):   # twice: the table must come back ready for another pass
             part.fill_(float("nan"))
             g2.zero_()
-            call("dasp_sosfilt_backward_grads", ptr(tab), ptr(dtab), Bs, ptr(x), ptr(gy), ptr(car), ptr(gx2), ptr(part), mode, ptr(g2),
+            call("dasp_sosfilt_backward_grads_ex", ptr(tab), ptr(dtab), Bs, ptr(x), ptr(gy), ptr(car), ptr(gx2), ptr(part), mode, ptr(g2),
                  B, C, N, S, stream())
             assert torch.equal(gx1, gx2) and torch.equal(g1, g2) and torch.isfinite(g2).all()
 
