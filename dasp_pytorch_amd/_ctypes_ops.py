@@ -802,6 +802,45 @@ class StereoMixFunction(torch.autograd.Function):
         return (None if gx is None else gx.to(xd)), gc[0], gc[1], (gc[2] if with_send else None)
 
 
+class OversampledDistortionFunction(torch.autograd.Function):
+    """y = decimate(tanh(g * interpolate(x))) at `oversample` times the sample rate, g = 10^(drive_db / 20) with one drive per (b, c) row
+    (dasp_osdist_forward / _backward, csrc/oversample.hip). taps: the 2 * half_width * oversample + 1 float32 taps as a ctypes array
+    (signal.oversampling_taps, rounded once). Saves x and drive_db only: the backward kernel recomputes the oversampled signal in LDS."""
+
+    @staticmethod
+    def forward(ctx, x, drive_db, taps, oversample, half_width):
+        _lib.require_device(x, "x")
+        B, C, N = x.shape
+        ctx.meta = (x.dtype, drive_db.dtype, drive_db.shape)
+        ctx.cfg = (taps, int(oversample), int(half_width))
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            return torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            d32 = drive_db.detach().reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
+            y = torch.empty_like(x32)
+            call("dasp_osdist_forward", ptr(x32), ptr(d32), taps, ptr(y), B, C, N, int(oversample), int(half_width), stream())
+            ctx.save_for_backward(x32, d32)
+        return y.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xd, dd, dshape = ctx.meta
+        if ctx.empty:
+            return torch.empty_like(gy), torch.zeros(dshape, dtype=dd, device=gy.device), None, None, None
+        taps, L, H = ctx.cfg
+        x32, d32 = ctx.saved_tensors
+        B, C, N = x32.shape
+        with torch.cuda.device(x32.device):
+            gx = torch.empty_like(x32)
+            gd = torch.empty_like(d32)
+            partials = torch.empty(_lib.lib().dasp_osdist_partial_floats(B * C, N, L), dtype=torch.float32, device=x32.device)
+            call("dasp_osdist_backward", ptr(x32), ptr(d32), taps, ptr(_f32c(gy)), ptr(gx), ptr(gd), ptr(partials), B, C, N, L, H, stream())
+        return gx.to(xd), gd.reshape(dshape).to(dd), None, None, None
+
+
 _FSPEC_CACHE = {}
 
 

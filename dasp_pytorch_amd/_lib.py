@@ -84,6 +84,10 @@ SIGNATURES = {
     "dasp_stereo_mix_partial_floats": (_l, [_l, _i, _l, _i]),
     "dasp_stereo_mix_forward": (_i, [_p] * 6 + [_i, _i, _l, _p]),
     "dasp_stereo_mix_backward": (_i, [_p] * 11 + [_i, _i, _l, _p]),
+    "dasp_osdist_tile": (_i, [_i]),
+    "dasp_osdist_partial_floats": (_l, [_l, _l, _i]),
+    "dasp_osdist_forward": (_i, [_p, _p, ctypes.POINTER(ctypes.c_float), _p, _i, _i, _l, _i, _i, _p]),
+    "dasp_osdist_backward": (_i, [_p, _p, ctypes.POINTER(ctypes.c_float)] + [_p] * 4 + [_i, _i, _l, _i, _i, _p]),
     "dasp_mrstft_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i]),
     "dasp_mrstft_table": (_i, [_p, _p]),
     "dasp_mrstft_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),

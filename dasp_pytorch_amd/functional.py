@@ -1,5 +1,7 @@
 """Drop-in for dasp_pytorch.functional on MI355X: same names, argument order and keyword names
 (dasp_pytorch/functional.py), every effect computed by hand-written HIP kernels (csrc/)."""
+import ctypes
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -7,7 +9,8 @@ from . import signal as _signal
 from . import _mt19937
 from . import ops as _ops
 from . import _lib
-from .ops import FILTER_TYPES, BusFunction, DistortionSampleFunction, PannerFunction, StereoMixFunction, WidenerFunction
+from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, OversampledDistortionFunction, PannerFunction, StereoMixFunction,
+                  WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
 
@@ -43,6 +46,49 @@ def distortion(x: torch.Tensor, sample_rate: int, drive_db: torch.Tensor):
     if is_f64(x):
         return Elementwise64Function.apply(x, drive_db, 1)
     return _ops.distortion(x, drive_db)
+
+
+_OS_TAPS = {}
+
+
+def _oversampling_taps_f32(oversample, half_width, beta, cutoff):
+    """The float64 taps of signal.oversampling_taps rounded once to float32, as the ctypes array the C call takes; kept per design."""
+    key = (oversample, half_width, float(beta), float(cutoff))
+    hit = _OS_TAPS.get(key)
+    if hit is None:
+        h = _signal.oversampling_taps(oversample, half_width, beta, cutoff).to(torch.float32)
+        hit = (ctypes.c_float * h.numel())(*h.tolist())
+        if len(_OS_TAPS) >= 32:
+            _OS_TAPS.clear()
+        _OS_TAPS[key] = hit
+    return hit
+
+
+def oversampled_distortion(x: torch.Tensor, sample_rate: int, drive_db: torch.Tensor, oversample: int = 4, half_width: int = 12,
+                           beta: float = 8.0, cutoff: float = 0.9):
+    """Anti-aliased soft clipper: `distortion` evaluated at `oversample` times the sample rate. x (bs, chs, seq_len) is interpolated by
+    L = oversample with the Kaiser-windowed sinc of signal.oversampling_taps(oversample, half_width, beta, cutoff), goes through
+    tanh(. * 10^(drive_db/20)), is low-passed by the same taps and decimated by L - centred: no latency, same length as x, zeros assumed
+    outside the signal. In torch terms, with h the taps and H = half_width:
+        u = conv_transpose1d(x, h, stride=L)[..., H*L : H*L + L*seq_len];  y = conv1d(tanh(g * u), h / L, stride=L, padding=H*L)
+    as one kernel per direction that keeps the L-times-longer signal on chip (csrc/oversample.hip). The harmonics that tanh at the base
+    rate folds back below Nyquist are rejected by about 62 dB at the defaults and 78 dB with oversample=8.
+    drive_db holds one value per (batch item, channel) row, bs*chs values, as in `distortion`. oversample is 1, 2, 4 or 8 (1 is
+    `distortion` itself), half_width an integer from 1 to 16, 0 < cutoff <= 1 and beta >= 0: anything else raises ValueError.
+    float32 only. Differentiable in x and drive_db."""
+    _signal.check_oversampling(oversample, half_width, beta, cutoff)
+    if oversample == 1:
+        return distortion(x, sample_rate, drive_db)
+    bs, chs, seq_len = x.size()
+    n = drive_db.numel()
+    if n != bs * chs:
+        if bs * chs == 0 or n % (bs * chs) != 0:
+            raise RuntimeError(f"shape '[{bs}, {chs}, -1]' is invalid for input of size {n}")
+        raise RuntimeError(f"The size of tensor a ({seq_len}) must match the size of tensor b ({n // (bs * chs)}) at non-singleton dimension 2")
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "oversampled_distortion")
+    oversample, half_width = int(oversample), int(half_width)
+    return OversampledDistortionFunction.apply(x, drive_db, _oversampling_taps_f32(oversample, half_width, beta, cutoff), oversample, half_width)
 
 
 def stereo_bus(x: torch.Tensor, sample_rate: int, send_db: torch.Tensor):

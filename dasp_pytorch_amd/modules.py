@@ -321,6 +321,18 @@ class Distortion(Processor):
         self.param_ranges = {"drive_db": (min_gain_db, max_gain_db)}
 
 
+class OversampledDistortion(Processor):
+    """Distortion evaluated at `oversample` times the sample rate (functional.oversampled_distortion with its default low-pass): the same
+    one parameter `drive_db` and the same constructor order as Distortion, plus the oversampling factor."""
+
+    def __init__(self, min_gain_db: float = 0.0, max_gain_db: float = 24.0, sample_rate: int = None, oversample: int = 4):
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.oversample = oversample
+        self.process_fn = functools.partial(F.oversampled_distortion, oversample=oversample)
+        self.param_ranges = {"drive_db": (min_gain_db, max_gain_db)}
+
+
 def _eq_ranges(sample_rate, g, q):
     top = (sample_rate // 2) - 1000
     cut = {"low_shelf": (20, 2000), "band0": (80, 2000), "band1": (2000, 8000), "band2": (8000, 12000), "band3": (12000, top),

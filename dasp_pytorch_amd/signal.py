@@ -11,6 +11,7 @@ zero-padded FFTs, for float32 and float64 alike, with a hand-written adjoint. `f
 audio: irfft(rfft(x, n_fft) * H, n_fft) on the library's own transforms (csrc/fdfir.hip), float32, n_fft a power of two from 8 to 2^20.
 """
 import functools
+import numbers
 import operator
 
 import numpy as np
@@ -38,6 +39,33 @@ def biquad(gain_db: torch.Tensor, cutoff_freq: torch.Tensor, q_factor: torch.Ten
     ba = BiquadFunction.apply(gain_db.reshape(bs), cutoff_freq.reshape(bs), q_factor.reshape(bs), float(sample_rate), FILTER_TYPES[filter_type])
     ba = ba.to(gain_db.dtype)
     return ba[:, :3], ba[:, 3:]
+
+
+OVERSAMPLE_FACTORS = (1, 2, 4, 8)
+OVERSAMPLE_MAX_HALF_WIDTH = 16
+
+
+def check_oversampling(oversample, half_width, beta, cutoff):
+    """The argument ranges of oversampling_taps / functional.oversampled_distortion: ValueError naming the argument and what it may be."""
+    if isinstance(oversample, bool) or not isinstance(oversample, numbers.Integral) or oversample not in OVERSAMPLE_FACTORS:
+        raise ValueError(f"oversample must be one of {OVERSAMPLE_FACTORS}, got {oversample!r}")
+    if isinstance(half_width, bool) or not isinstance(half_width, numbers.Integral) or not 1 <= half_width <= OVERSAMPLE_MAX_HALF_WIDTH:
+        raise ValueError(f"half_width must be an integer from 1 to {OVERSAMPLE_MAX_HALF_WIDTH}, got {half_width!r}")
+    if not (isinstance(beta, numbers.Real) and not isinstance(beta, bool) and 0.0 <= beta < float("inf")):
+        raise ValueError(f"beta must be a finite number >= 0, got {beta!r}")
+    if not (isinstance(cutoff, numbers.Real) and not isinstance(cutoff, bool) and 0.0 < cutoff <= 1.0):
+        raise ValueError(f"cutoff must lie in (0, 1], got {cutoff!r}")
+
+
+def oversampling_taps(oversample: int, half_width: int = 12, beta: float = 8.0, cutoff: float = 0.9):
+    """The low-pass of functional.oversampled_distortion, used once to interpolate by L = `oversample` and once to decimate: a Kaiser-windowed
+    sinc over `half_width` base samples to either side, h[c] = cutoff sinc(cutoff c / L) I0(beta sqrt(1 - (c / (H L))^2)) / I0(beta) for
+    c = -H L .. H L, with its cutoff at `cutoff` times the base Nyquist frequency. Every phase h[p::L] sums to about 1 (unit gain at DC
+    after interpolation). Returns the 2 H L + 1 taps as a float64 CPU tensor."""
+    check_oversampling(oversample, half_width, beta, cutoff)
+    L, H = int(oversample), int(half_width)
+    c = np.arange(-H * L, H * L + 1, dtype=np.float64)
+    return torch.from_numpy(cutoff * np.sinc(cutoff * c / L) * np.kaiser(2 * H * L + 1, beta))
 
 
 def lfilter_via_fsm(x: torch.Tensor, b: torch.Tensor, a: torch.Tensor = None):

@@ -388,6 +388,21 @@ int dasp_stereo_mix_backward(const float* x, const float* gain_db, const float* 
                              const float* gsend, float* gx, float* ggain, float* gpan, float* gsend_db, float* partials, int B, int T,
                              long N, void* stream);
 
+/* oversampled_distortion: tanh(g x) at L times the sample rate, g = 10^(drive_db / 20) - interpolation by L with a windowed-sinc low-pass,
+ * the non-linearity, the same low-pass and decimation by L, in one kernel per direction (csrc/oversample.hip); the L-times-longer signal
+ * exists in LDS only.  x, y, gy, gx (B, C, N) fp32; drive_db, gdrive (B * C), one value per row; taps: 2 H L + 1 HOST floats h[c],
+ * c = -H L .. H L, symmetric (dasp_pytorch_amd.signal.oversampling_taps), handed to the kernels by value.  Zeros outside [0, N):
+ *   u[m] = sum_j h[m - L j] x[j],  v[m] = tanh(g u[m]) for 0 <= m < L N (zero outside),  y[n] = (1 / L) sum_m h[L n - m] v[m]
+ * Backward: gx = dL/dx and gdrive = dL/d(drive_db), u recomputed; partials is scratch of dasp_osdist_partial_floats(B * C, N, L) floats =
+ * rows * ceil(N / dasp_osdist_tile(L)), one per workgroup, summed in fp64 by a second launch: no atomics, bit-identical run to run.
+ * L one of 2, 4, 8 and 1 <= H <= 16; anything else, a null pointer or a non-positive size: DASP_ERR_ARG (-1 from the size queries);
+ * B * C * ceil(N / tile) >= 2^31: DASP_ERR_UNSUPPORTED. All of it is checked before taps is read and before any launch. */
+int dasp_osdist_tile(int L);
+long dasp_osdist_partial_floats(long rows, long N, int L);
+int dasp_osdist_forward(const float* x, const float* drive_db, const float* taps, float* y, int B, int C, long N, int L, int H, void* stream);
+int dasp_osdist_backward(const float* x, const float* drive_db, const float* taps, const float* gy, float* gx, float* gdrive, float* partials,
+                         int B, int C, long N, int L, int H, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Multi-resolution STFT loss, the op downstream of the effect chain in the reference's training loops
  * (auraloss.freq.MultiResolutionSTFTLoss(): examples/style_transfer.py:341,363, auto_eq.py:252, virtual_analog.py:288; auraloss is
