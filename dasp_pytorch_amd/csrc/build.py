@@ -9,6 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libdasp_hip.so")
 ARCH = "gfx950"
 # compile flags of every kernel source (scripts/isa_histogram.py compiles to assembly with the same ones)
+# No -ffast-math / -ffinite-math-only / -fno-honor-nans: the dynamics kernels hand a NaN or inf sample on to their smoothing state through
+# `mag < eps ? eps : mag` and `x_db - x_db` (dyn_common.hpp), which such flags fold away (tests/test_gpu_input_domain.py part B notices).
 HIPCC_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-Wno-pass-failed", "-Wno-inline-asm"]
 
 

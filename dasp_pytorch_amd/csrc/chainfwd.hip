@@ -198,7 +198,7 @@ chain_fwd_kernel(const float* __restrict__ tab, int tab_bcast, const float* __re
         for (int n = 0; n < L; ++n) {
             float d0, d1, d2, d3;
             const float s = Y[0][n] + Y[1][n];                                             // side chain: sum over channels (:328)
-            const float x_db = DB_PER_LOG2 * log2f(fmaxf(fabsf(s), it.eps));               // :347
+            const float x_db = DB_PER_LOG2 * log2f(clamp_min_eps(fabsf(s), it.eps));               // :347
             gc[n] = it.beta * gain_computer<MODE, false>(x_db, it, d0, d1, d2, d3);        // (1 - alpha) g_c[n]
             e = fmaf(it.alpha, e, gc[n]);                                                  // zero-state end of the chunk
         }

@@ -20,12 +20,15 @@ template <int MODE, bool D>
 __device__ __forceinline__ float gain_computer(float x_db, const DynItem& it, float& d_x, float& d_t, float& d_r, float& d_w) {
     const float half = 0.5f * it.knee, lo = it.thr - half, hi = it.thr + half;
     const bool in_knee = (x_db >= lo) && (x_db <= hi) && (it.knee > 0.f);
-    float g = 0.f;
+    // Outside the knee and the active branch x_sc = x_db and g_c = x_sc - x_db (functional.py:369): 0 for a finite level, NaN for a NaN
+    // level (every comparison is false for it) and for +inf (inf - inf), so that a non-finite sample reaches the smoothing state as in the
+    // reference. Needs IEEE NaN semantics from the compiler: build.py HIPCC_FLAGS.
+    float g = x_db - x_db;
     if (D) { d_x = d_t = d_r = d_w = 0.f; }
     if (MODE == 0) {   // compressor, functional.py:350-369
         const float sl = it.inv_ratio - 1.f;   // 1/R - 1
         if (x_db > hi) {
-            g = (x_db - it.thr) * sl;
+            g = fmaf(x_db - it.thr, sl, g);        // (+ g: the same bits for a finite level, NaN at +inf)
             if (D) { d_x = sl; d_t = -sl; d_r = -(x_db - it.thr) * it.inv_ratio * it.inv_ratio; }
         } else if (in_knee) {
             const float q = x_db - lo, iw = 1.f / it.knee, h = 0.5f * q * q * iw;
@@ -45,6 +48,11 @@ __device__ __forceinline__ float gain_computer(float x_db, const DynItem& it, fl
     }
     return g;
 }
+
+// max(|side chain|, eps) (functional.py:347, torch.clamp(min = eps)) that hands a NaN on, as torch.clamp does and fmaxf does not: the
+// reference's smoothing state - and with it the rest of the item - is NaN from a NaN sample on (tests/test_gpu_input_domain.py, part B)
+template <typename T>
+__device__ __forceinline__ T clamp_min_eps(T mag, T eps) { return mag < eps ? eps : mag; }
 
 // Where the five controls the kernels read live - threshold_db, ratio, attack_ms, knee_db, makeup_gain_db: control i of item b is
 // p[i][b * s]. (B, 5) rows (the C ABI's `ctl`): p[i] = ctl + i, s = 5; five separate vectors of B values (the reference's own

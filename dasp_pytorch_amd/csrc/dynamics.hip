@@ -193,7 +193,7 @@ dyn_fwd_kernel(const float* __restrict__ x, const DynCtl ctl, float* __restrict_
             float d0, d1, d2, d3;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float x_db = DB_PER_LOG2 * log2f(fmaxf(fabsf(s[j][i]), it.eps));   // :347
+                const float x_db = DB_PER_LOG2 * log2f(clamp_min_eps(fabsf(s[j][i]), it.eps));   // :347
                 s[j][i] = gain_computer<MODE, false>(x_db, it, d0, d1, d2, d3);           // s now holds g_c
             }
             const float e = it.beta * fmaf(it.alpha, fmaf(it.alpha, fmaf(it.alpha, s[j].x, s[j].y), s[j].z), s[j].w);
@@ -291,7 +291,7 @@ dyn_fwd_lookback_kernel(const float* __restrict__ x, const DynCtl ctl, float* __
             float d0, d1, d2, d3;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float x_db = DB_PER_LOG2 * log2f(fmaxf(fabsf(s[r][j][i]), it.eps));
+                const float x_db = DB_PER_LOG2 * log2f(clamp_min_eps(fabsf(s[r][j][i]), it.eps));
                 s[r][j][i] = gain_computer<MODE, false>(x_db, it, d0, d1, d2, d3);
             }
             const float e = it.beta * fmaf(it.alpha, fmaf(it.alpha, fmaf(it.alpha, s[r][j].x, s[r][j].y), s[r][j].z), s[r][j].w);
@@ -474,7 +474,7 @@ dyn_bwd_kernel(const float* __restrict__ x, const DynCtl ctl, const float* __res
         for (int j = 0; j < DY_SUB; ++j) {
             float d0, d1, d2, d3;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) T.gc[j][i] = gain_computer<MODE, false>(DB_PER_LOG2 * log2f(fmaxf(fabsf(T.s[j][i]), it.eps)), it, d0, d1, d2, d3);
+            for (int i = 0; i < 4; ++i) T.gc[j][i] = gain_computer<MODE, false>(DB_PER_LOG2 * log2f(clamp_min_eps(fabsf(T.s[j][i]), it.eps)), it, d0, d1, d2, d3);
             const float e = it.beta * fmaf(it.alpha, fmaf(it.alpha, fmaf(it.alpha, T.gc[j].x, T.gc[j].y), T.gc[j].z), T.gc[j].w);
             E[j] = lane_scan(e, it, pw16, pw32);
         }
@@ -526,7 +526,7 @@ dyn_bwd_kernel(const float* __restrict__ x, const DynCtl ctl, const float* __res
                 acc_a = fmaf(rn, glast - T.gc[j][i], acc_a);                         // dL/dalpha
                 const float p = it.beta * rn;                                      // dL/dg_c[n]
                 const float mag = fabsf(T.s[j][i]);
-                const float x_db = DB_PER_LOG2 * log2f(fmaxf(mag, it.eps));
+                const float x_db = DB_PER_LOG2 * log2f(clamp_min_eps(mag, it.eps));
                 float d_x, d_t, d_r, d_w;
                 gain_computer<MODE, true>(x_db, it, d_x, d_t, d_r, d_w);
                 acc_t = fmaf(p, d_t, acc_t); acc_r = fmaf(p, d_r, acc_r); acc_w = fmaf(p, d_w, acc_w);

@@ -113,12 +113,12 @@ template <int MODE, bool D>
 __device__ __forceinline__ double gain_computer64(double x_db, const Dyn64& it, double& d_x, double& d_t, double& d_r, double& d_w) {
     const double half = 0.5 * it.knee, lo = it.thr - half, hi = it.thr + half;
     const bool in_knee = (x_db >= lo) && (x_db <= hi) && (it.knee > 0.0);
-    double g = 0.0;
+    double g = x_db - x_db;                    // 0, and NaN for a NaN level: dyn_common.hpp gain_computer
     if (D) { d_x = d_t = d_r = d_w = 0.0; }
     if (MODE == 0) {
         const double ir = 1.0 / it.ratio, sl = ir - 1.0;
         if (x_db > hi) {
-            g = (x_db - it.thr) * sl;
+            g = fma(x_db - it.thr, sl, g);
             if (D) { d_x = sl; d_t = -sl; d_r = -(x_db - it.thr) * ir * ir; }
         } else if (in_knee) {
             const double q = x_db - lo, iw = 1.0 / it.knee, h = 0.5 * q * q * iw;
@@ -160,7 +160,7 @@ __global__ void dyn64_fwd_kernel(const double* __restrict__ x, const double* __r
     for (long n = 0; n < N; ++n) {
         double s = 0.0;
         for (int c = 0; c < C; ++c) s += xb[(size_t)c * N + n];                  // :328
-        const double x_db = K_DB * log(fmax(fabs(s), it.eps));                   // :347
+        const double as = fabs(s), x_db = K_DB * log(as < it.eps ? it.eps : as);       // :347 (a NaN goes through, as torch.clamp: dyn_common.hpp)
         const double gc = gain_computer64<MODE, false>(x_db, it, d0, d1, d2, d3);
         g = it.alpha * g + (1.0 - it.alpha) * gc;                                // :372-380 as a recursion
         if (gsave) gsave[(size_t)b * N + n] = g;
@@ -198,7 +198,7 @@ __global__ void dyn64_bwd_kernel(const double* __restrict__ x, const double* __r
         q *= K_LN10_20 * lin;
         acc_m += q;
         r = q + it.alpha * r;                                                    // r[n] = q[n] + alpha r[n + 1]
-        const double mag = fabs(s), x_db = K_DB * log(fmax(mag, it.eps));
+        const double mag = fabs(s), x_db = K_DB * log(mag < it.eps ? it.eps : mag);
         double d_x, d_t, d_r, d_w;
         const double gc = gain_computer64<MODE, true>(x_db, it, d_x, d_t, d_r, d_w);
         acc_a += r * ((n >= 1 ? gs[n - 1] : 0.0) - gc);                          // dL/dalpha
