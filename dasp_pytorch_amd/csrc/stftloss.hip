@@ -55,8 +55,10 @@ __device__ __forceinline__ Bin split_bin(float zr, float zi, float mr, float mi)
 }
 
 // one bin's contribution to the four sums of a resolution
+// torch.clamp(min = eps): a NaN power stays NaN (fmaxf would hand back eps and count the bins of a frame that holds a NaN or inf sample as silent)
+__device__ __forceinline__ float clamp_min_eps(float x, float eps) { return x < eps ? eps : x; }
 __device__ __forceinline__ void loss_terms(const Bin& b, float eps, float& s1, float& s2, float& s3, float& s4) {
-    const float p2 = fmaxf(b.pr * b.pr + b.pi * b.pi, eps), t2 = fmaxf(b.tr * b.tr + b.ti * b.ti, eps);
+    const float p2 = clamp_min_eps(b.pr * b.pr + b.pi * b.pi, eps), t2 = clamp_min_eps(b.tr * b.tr + b.ti * b.ti, eps);
     const float pm = __builtin_amdgcn_sqrtf(p2), tm = __builtin_amdgcn_sqrtf(t2);      // operands in [eps, ~1e6]: the plain instructions are exact enough (1 ulp)
     s1 = fmaf(tm - pm, tm - pm, s1);
     s2 += t2;
@@ -73,7 +75,7 @@ __device__ __forceinline__ GradK grad_consts(const StftSpec& spec, const float* 
     const float s1 = stats[res * 4], s2 = stats[res * 4 + 1], count = stats[res * 4 + 2];
     const float gl = gloss[0] / (float)spec.nres;
     GradK k;
-    k.sc = spec.w_sc != 0.f && s1 > 0.f ? spec.w_sc * gl / (s1 * s2) : 0.f;
+    k.sc = spec.w_sc != 0.f && s1 != 0.f ? spec.w_sc * gl / (s1 * s2) : 0.f;
     k.lm = spec.w_lm * gl / count;
     k.lin = spec.w_lin * gl / count;
     k.self = wrt_second && spec.w_sc != 0.f ? -(spec.w_sc * gl) * s1 / (s2 * s2 * s2) : 0.f;
@@ -85,8 +87,8 @@ template <bool LIN>
 __device__ __forceinline__ void grad_bin(const Bin& b, float eps, const GradK& k, float& hr, float& hi) {
     hr = 0.f; hi = 0.f;
     const float praw = b.pr * b.pr + b.pi * b.pi;
-    if (praw > eps) {                                            // the clamp has zero slope below eps
-        const float tm = sqrtf(fmaxf(b.tr * b.tr + b.ti * b.ti, eps)), pm = sqrtf(praw);
+    if (!(praw <= eps)) {                                        // the clamp has zero slope below eps; a NaN bin goes through, as in autograd
+        const float tm = sqrtf(clamp_min_eps(b.tr * b.tr + b.ti * b.ti, eps)), pm = sqrtf(praw);
         const float sgn = tm > pm ? 1.f : (tm < pm ? -1.f : 0.f);            // sign(log tm - log pm)
         float d = k.sc * (pm - tm) - k.lm * sgn / pm;
         if constexpr (LIN) d -= k.lin * sgn;
@@ -447,8 +449,8 @@ mrstft_bwd_split_kernel(const float* __restrict__ pred, const float* __restrict_
 
 // ---- perceptual weighting: the A-weighting FIR of auraloss (FIRFilter(filter_type="aw", ntaps=101)) -------------------------------------
 // y[n] = sum_{k=0}^{K-1} h[k] x[n + k - K/2], zeros outside [0, N) (conv1d(x, h, padding=K/2)); K odd, <= 101. The taps sit centred in
-// 101 LDS slots (zeros around a shorter filter), so every output is the same 101 fmas in the same order: the result does not depend on
-// the tile it falls in, and is bit-identical run to run. flip = 1 reverses the taps: the adjoint, gx[m] = sum_k h[k] gy[m - k + K/2],
+// 101 LDS slots (zeros around a shorter filter, which walks its own slots only), so every output is the same ntaps fmas in the same order:
+// the result does not depend on the tile it falls in, and is bit-identical run to run. flip = 1 reverses the taps: the adjoint, gx[m] = sum_k h[k] gy[m - k + K/2],
 // is the same sum over h[K-1-k] (no symmetry of the taps is assumed). A workgroup of 256 threads owns FIR_TILE consecutive outputs of one
 // row of one of the two signals (blockIdx.z): the tile plus a 50-sample halo on each side goes to LDS, each thread computes 8 consecutive
 // outputs from its 108-sample window, the taps are LDS broadcasts.
@@ -475,11 +477,22 @@ fir_same_kernel(const float* __restrict__ x0, const float* __restrict__ x1, floa
     float acc[FIR_Q];
 #pragma unroll
     for (int q = 0; q < FIR_Q; ++q) acc[q] = 0.f;
+    if (ntaps == FIR_MAXTAPS) {
 #pragma unroll
-    for (int k = 0; k < FIR_MAXTAPS; ++k) {
-        const float h = hs[k];
+        for (int k = 0; k < FIR_MAXTAPS; ++k) {
+            const float h = hs[k];
 #pragma unroll
-        for (int q = 0; q < FIR_Q; ++q) acc[q] = fmaf(h, xw[q + k], acc[q]);
+            for (int q = 0; q < FIR_Q; ++q) acc[q] = fmaf(h, xw[q + k], acc[q]);
+        }
+    } else {
+        // a shorter filter walks its own slots only, in the same order: the zero slots around it add exactly 0 to a finite sum, but 0 * NaN
+        // (or 0 * inf) would carry a bad sample 50 samples to either side, where conv1d confines it to ntaps outputs
+        const int lo = FIR_HALO - ntaps / 2;
+        for (int k = lo; k < lo + ntaps; ++k) {
+            const float h = hs[k];
+#pragma unroll
+            for (int q = 0; q < FIR_Q; ++q) acc[q] = fmaf(h, xw[q + k], acc[q]);
+        }
     }
 #pragma unroll
     for (int q = 0; q < FIR_Q; ++q) {
@@ -578,8 +591,8 @@ __device__ __forceinline__ void mel_magnitudes_to_lds(float* mag, const ColCfg& 
         const int k = g.j + g.T * q;
         if (k <= F / 2) {
             const Bin b = split_bin(r[q], i[q], mr[q], mi[q]);
-            mag[k * g.TC + g.c] = sqrtf(fmaxf(b.pr * b.pr + b.pi * b.pi, eps));
-            mag[(K + k) * g.TC + g.c] = sqrtf(fmaxf(b.tr * b.tr + b.ti * b.ti, eps));
+            mag[k * g.TC + g.c] = sqrtf(clamp_min_eps(b.pr * b.pr + b.pi * b.pi, eps));
+            mag[(K + k) * g.TC + g.c] = sqrtf(clamp_min_eps(b.tr * b.tr + b.ti * b.ti, eps));
         }
     }
     __syncthreads();
@@ -697,7 +710,7 @@ mrstft_mel_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ 
         if (live && k <= F / 2) {
             const Bin b = split_bin(r[q], i[q], mr[q], mi[q]);
             const float praw = b.pr * b.pr + b.pi * b.pi;
-            if (praw > spec.eps) {                               // the clamp has zero slope below eps
+            if (!(praw <= spec.eps)) {                           // the clamp has zero slope below eps; a NaN bin goes through
                 const f2 w = t.w[k];
                 const int ma = t.m0[k], mb = ma + 1 < nbins ? ma + 1 : ma;           // w.y = 0 where filter m0 + 1 does not exist
                 const float gm = (w.x * dm[ma * TC + g.c] + w.y * dm[mb * TC + g.c]) / sqrtf(praw);      // dL/d|P| / |P|
@@ -1139,7 +1152,7 @@ __device__ __forceinline__ void sd_mel_grad_spectrum(float* mag, const ColCfg& g
         const Bin b = k > F / 2 ? split_bin(mr[q], mi[q], r[q], i[q]) : split_bin(r[q], i[q], mr[q], mi[q]);
         float hr = 0.f, hi = 0.f;
         const float praw = b.pr * b.pr + b.pi * b.pi;
-        if (live && praw > spec.eps) {
+        if (live && !(praw <= spec.eps)) {
             const f2 w = t.w[kb];
             const int ma = t.m0[kb], mb = ma + 1 < t.B ? ma + 1 : ma;
             const float gm = (w.x * dm[ma * TC + g.c] + w.y * dm[mb * TC + g.c]) / sqrtf(praw);

@@ -91,8 +91,10 @@ __device__ double td_row(const double* __restrict__ M, double n, const TdParams&
         // sum (p' - alpha t')^2 = E + 2 beta C + beta^2 T with beta = 1 - alpha = (eps - C) / (T + eps)
         double E = Sdd, T = Stt, C = Sdt;
         if (q.zero_mean) {
-            E = fmax(Sdd - Sd * Sd / n, 0.0);
-            T = fmax(Stt - St * St / n, 0.0);
+            E = Sdd - Sd * Sd / n;                      // x < 0 ? 0 : x, not fmax: a NaN / inf - inf moment stays NaN (fmax would
+            T = Stt - St * St / n;                      // hand back 0, and SNRLoss of a diverged prediction would read as perfect)
+            E = E < 0.0 ? 0.0 : E;
+            T = T < 0.0 ? 0.0 : T;
             C = Sdt - Sd * St / n;
         }
         const double K = -4.342944819032518;            // -10 / ln 10

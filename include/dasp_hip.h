@@ -419,6 +419,12 @@ int dasp_osdist_backward(const float* x, const float* drive_db, const float* tap
  * bit-identical run to run (fixed summation order).  grad (rows, N) is overwritten with gloss * d loss / d pred, or with wrt_target = 1
  * gloss * d loss / d target (auraloss differentiates both arguments; the same kernels with the signals swapped), through float atomics:
  * summation order only is not deterministic.
+ * Non-finite samples: the clamp of the bin powers is torch.clamp(min = eps), not fmax - a NaN or +-inf sample makes every bin of the
+ * frames that hold it non-finite, so the loss (and stats) of that call are NaN / inf, as auraloss's are; it is never read as silence.
+ * Gradient: with w_sc != 0 every row is non-finite (all rows share the norms of the spectral convergence); with w_sc = 0 the rows of
+ * the other signals keep the values of a batch without the bad sample (up to the order of the atomics) and the row that holds the
+ * sample is non-finite over those frames. The buffers of a later call are not affected (grad is zeroed by every backward call). The
+ * sum / difference loss likewise, per item.
  * ------------------------------------------------------------------------------------------- */
 long dasp_mrstft_partial_floats(long rows, int N, int nres, const int* fft, const int* hop, const int* win, int n_bins);
 int dasp_mrstft_table(void* tw, void* stream);
@@ -488,6 +494,11 @@ int dasp_mrstft_sd_backward(const float* pred, const float* target, const void* 
  *   gpred, gtarget  (rows, N) fp32, overwritten with gloss * d loss / d pred and d loss / d target in one launch; either may be NULL
  * The backward call takes the options of the forward call that wrote `moments`. No atomics and nothing zeroed: loss and gradients are
  * bit-identical run to run, and both calls are plain kernel launches on `stream` (capturable into a graph).
+ * Non-finite samples: a NaN or +-inf sample makes the moments of ITS row non-finite and the row's loss what auraloss's formula gives
+ * on them - NaN or inf for every term (zero_mean included: the centred sums are clamped at 0 with `x < 0 ? 0 : x`, which hands a NaN
+ * on, so a diverged prediction never reads as a perfect SNR), the one finite case being snr of a +inf prediction with zero_mean = 0,
+ * -10 log10(eps) = 80 dB at eps = 1e-8. Every other row keeps its loss and its gradients bit for bit; reduction 1 / 2 are non-finite
+ * when a row is.
  * ------------------------------------------------------------------------------------------- */
 long dasp_tdloss_scratch_doubles(long rows, long N);
 int dasp_tdloss_forward(const float* pred, const float* target, double* scratch, double* moments, float* row_loss, float* loss, long rows,
@@ -543,6 +554,13 @@ int dasp_freqz_backward(const void* b, const void* a, const void* gH, int rows, 
  *   its size passed as work_floats (checked: DASP_ERR_ARG). The forward call needs the frames of x only:
  *   2 * h_rows * ((rows / h_rows + 1) / 2) * n_fft floats, one complex frame per two rows of an item.
  *   dasp_fdfir_backward: gx and / or gH may be NULL (skipped); x may be NULL when gH is.
+ *   Rows that share a transform: where chs >= 2 rows share a response, rows 2f and 2f + 1 of an item travel as ONE complex frame
+ *   x[2f] + i x[2f + 1] (an odd last row, and every row when h_rows = rows, travels alone). Guaranteed: (1) a non-finite sample in a row of
+ *   x makes y of that row AND of the row paired with it non-finite at every sample, and gH of the item non-finite (the same for gy and
+ *   gx); unpaired rows of the item, every other item, and the outputs the value does not enter (gx for x, y for gy) keep every bit.
+ *   (2) The error of a row is bounded relative to the larger peak of its PAIR, not to its own: 2e-5 of the item's largest output peak
+ *   (the bound of tests/test_gpu_freqdomain_fir.py); a channel 80 dB below its partner carries the partner's rounding error, 2e-7 .. 3e-7 of the
+ *   item's peak, i.e. 2e-3 .. 3e-3 of its own (measured). A caller who needs per-row accuracy passes a response per row (h_rows = rows).
  * ------------------------------------------------------------------------------------------- */
 long dasp_fdfir_work_floats(long rows, long T, long n_fft, long h_rows);
 int dasp_fdfir_forward(const float* x, const void* H, const void* tw, float* y, float* work, long work_floats, long rows, long T, long n_fft,
