@@ -599,7 +599,8 @@ class ChainControlsFunction(torch.autograd.Function):
             flat = buf.view(-1)
             ctl, gains, decays, mix = flat[:5 * B].view(B, 5), flat[5 * B:17 * B].view(B, 12), flat[17 * B:29 * B].view(B, 12), flat[29 * B:]
             if B:
-                call("dasp_chain_controls", ptr(_f32c(comp_pn)), ptr(_f32c(reverb_pn)), ptr(_f32c(gain_pn)), lo, span, ptr(ctl), ptr(gains),
+                c32, r32, g32 = _f32c(comp_pn), _f32c(reverb_pn), _f32c(gain_pn)      # named: copies must outlive one another (see StereoMixFunction)
+                call("dasp_chain_controls", ptr(c32), ptr(r32), ptr(g32), lo, span, ptr(ctl), ptr(gains),
                      ptr(decays), ptr(mix), ptr(range_flag), B, stream())
         return ctl, gains, decays, mix
 
@@ -795,8 +796,11 @@ class StereoMixFunction(torch.autograd.Function):
             gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None           # not computed, not written when x needs no gradient
             gc = [torch.empty_like(c) for c in c32]
             partials = torch.empty(_lib.lib().dasp_stereo_mix_partial_floats(B, T, N, int(with_send)), dtype=torch.float32, device=dev)
-            call("dasp_stereo_mix_backward", ptr(x32), ptr(c32[0]), ptr(c32[1]), ptr(c32[2] if with_send else None), ptr(_f32c(gmix)),
-                 ptr(_f32c(gsend) if with_send else None), ptr(gx), ptr(gc[0]), ptr(gc[1]), ptr(gc[2] if with_send else None), ptr(partials),
+            # both copies stay referenced until the call is queued: as temporaries, the copy of a non-contiguous gmix was freed before
+            # gsend was copied - into the same block - and the kernel read gsend twice
+            gm32, gs32 = _f32c(gmix), (_f32c(gsend) if with_send else None)
+            call("dasp_stereo_mix_backward", ptr(x32), ptr(c32[0]), ptr(c32[1]), ptr(c32[2] if with_send else None), ptr(gm32),
+                 ptr(gs32), ptr(gx), ptr(gc[0]), ptr(gc[1]), ptr(gc[2] if with_send else None), ptr(partials),
                  B, T, N, stream())
         gc = [g.reshape(s).to(d) for g, (d, s) in zip(gc, cmeta)]
         return (None if gx is None else gx.to(xd)), gc[0], gc[1], (gc[2] if with_send else None)
@@ -837,7 +841,8 @@ class OversampledDistortionFunction(torch.autograd.Function):
             gx = torch.empty_like(x32)
             gd = torch.empty_like(d32)
             partials = torch.empty(_lib.lib().dasp_osdist_partial_floats(B * C, N, L), dtype=torch.float32, device=x32.device)
-            call("dasp_osdist_backward", ptr(x32), ptr(d32), taps, ptr(_f32c(gy)), ptr(gx), ptr(gd), ptr(partials), B, C, N, L, H, stream())
+            g32 = _f32c(gy)
+            call("dasp_osdist_backward", ptr(x32), ptr(d32), taps, ptr(g32), ptr(gx), ptr(gd), ptr(partials), B, C, N, L, H, stream())
         return gx.to(xd), gd.reshape(dshape).to(dd), None, None, None
 
 

@@ -20,13 +20,16 @@
 //                  backward           <- the saved K-weighted signal times 2 x coverage weight of its sub-block x upstream gradient on
 //                                        load, filtered backwards in time, -> gx
 //                  state pre-pass     -> the end state of a segment from a zero start (few rows only, either direction)
-//                Sub-block sums: per lane fp32 over at most 32 squares, then fp64 in a fixed order (a wave tree per sub-block the wave
-//                touches, stored per wave; the gate launch adds a row's waves in sequence): bit-identical run to run, no atomics.
+//                Sub-block sums: per lane fp32 over at most 32 squares (summed again in fp64 where that sum is inf: a sample above
+//                1.8e19), then fp64 in a fixed order (a wave tree per sub-block the wave touches, stored per wave; the gate launch adds
+//                a row's waves in sequence): bit-identical run to run, no atomics.
 //   few rows     a row is cut into segments that run as workgroups of their own: the pre-pass leaves every segment's end state from a zero
 //                start, and the main pass begins by chaining the states of the segments before its own (at most 256 4-vectors, one
 //                thread) - two launches, and no workgroup ever waits for another one.
 //   gate         one workgroup per item: sub-block sums from the waves' partials in a fixed order, block powers from four consecutive sub-blocks,
-//                both gates in fp64, L in fp32, and the coverage weights of the backward pass (zeros for an empty gate).
+//                both gates in fp64, L in fp32, and the coverage weights of the backward pass (-0.f throughout for an empty gate: the
+//                backward pass then writes exact zeros and reads no sample). The gates are IEEE comparisons: a block whose power is NaN
+//                passes neither, so a NaN sample leaves L finite where clean blocks remain, and the row's gradient NaN (NaN x 0 coverage).
 //   peak         max |x| with the lowest index attaining it per (row, segment), then a scaling pass; backward: sum g x per (row,
 //                segment), then one elementwise pass that adds the correction at the index of the maximum.
 // Rows need 4-byte alignment only: samples are moved as 16-byte vectors through a type that claims no more (global dwordx4 needs no more).
@@ -49,6 +52,7 @@ constexpr long LD_FILL = 1024;              // workgroups that fill the chip (25
 constexpr int LD_MAX_SEG = 256;             // segments per row at most (the chain prologue stages their states in LDS)
 constexpr int LD_MAX_CH = 5;
 constexpr long LD_MAX_N = 1L << 30;         // in-row indices are 32-bit
+constexpr unsigned LD_EMPTY_GATE = 0x80000000u;      // -0.f in a row's coverage weights: no block of the item passed the gates
 enum { LD_STATE = 0, LD_SUMS = 1, LD_SUMS_STORE = 2, LD_STORE = 3 };
 
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));       // 16 bytes at a 4-byte aligned address
@@ -108,6 +112,11 @@ __global__ void __launch_bounds__(LD_NT) ld_filter_kernel(const LdArgs a, const 
     const float* __restrict__ in = a.in + row * N;
     float* __restrict__ out = a.out ? a.out + row * N : nullptr;
 
+    if (BWD && __float_as_uint(a.cov[row * a.nsub]) == LD_EMPTY_GATE) {      // no block past the gates (uniform over the workgroup, no barrier
+        if (EPI != LD_STATE)                                                 // before this): L is -inf and the gradient exactly 0, whatever
+            for (int i = tid; i < seglen; i += LD_NT) out[N - mseg - seglen + i] = 0.f;      // the samples and the upstream gradient hold
+        return;
+    }
     double c[4] = {0.0, 0.0, 0.0, 0.0};                     // state at the start of the tile
     if (tid == 0) {
 #pragma unroll
@@ -219,8 +228,8 @@ __global__ void __launch_bounds__(LD_NT) ld_filter_kernel(const LdArgs a, const 
             kb = (sa + 1) * H - nlo;
         }
         if (BWD) {
-            const float wa = sa < a.nsub ? scale2 * cov[sa] : 0.f;
-            const float wb = sa + 1 < a.nsub ? scale2 * cov[sa + 1] : 0.f;
+            const float wa = scale2 * (sa < a.nsub ? cov[sa] : 0.f);            // (the ignored tail too is multiplied: a NaN there, or a NaN
+            const float wb = scale2 * (sa + 1 < a.nsub ? cov[sa + 1] : 0.f);    // upstream gradient, reaches the whole row as in u = 2 y w gL)
 #pragma unroll
             for (int k = 0; k < LD_L; ++k) X[k] *= (k < kb ? wa : wb);
         }
@@ -318,12 +327,22 @@ __global__ void __launch_bounds__(LD_NT) ld_filter_kernel(const LdArgs a, const 
                 qa += (k < kb && k < nvalid) ? sq : 0.f;
                 qb += (k >= kb && k < nvalid) ? sq : 0.f;
             }
+            double da = (double)qa, db = (double)qb;
+            if (qa == INFINITY || qb == INFINITY) {          // a square (|y| > 1.8e19) or their sum left float32: these 32 again, in fp64
+                da = db = 0.0;
+#pragma unroll
+                for (int k = 0; k < LD_L; ++k) {
+                    const double sq = (double)X[k] * (double)X[k];
+                    da += (k < kb && k < nvalid) ? sq : 0.0;
+                    db += (k >= kb && k < nvalid) ? sq : 0.0;
+                }
+            }
             // the wave's sums of the (at most four) sub-blocks its samples fall in, bin 0 = the sub-block of its first sample; the gate
             // launch adds the waves of a row up in sequence
             const int sw = __builtin_amdgcn_readfirstlane(sa);
 #pragma unroll
             for (int k = 0; k < LD_BINS; ++k) {
-                double v = (sa - sw == k ? (double)qa : 0.0) + (sa + 1 - sw == k ? (double)qb : 0.0);
+                double v = (sa - sw == k ? da : 0.0) + (sa + 1 - sw == k ? db : 0.0);
                 v = wave_sum(v);
                 if (lane == 0 && wm0 < N) part[(long)(wm0 / (64 * LD_L)) * LD_BINS + k] = v;
             }
@@ -415,7 +434,7 @@ __global__ void __launch_bounds__(LG_NT) ld_gate_kernel(const LgArgs a) {
                     const double l = lg_lufs(lg_power(a, sub, j));
                     cnt += (l > -70.0 && l > gamma) ? 1 : 0;
                 }
-            a.cov[(item * a.chs + ch) * (long)a.nsub + s] = (float)(dz * a.w[ch] * cnt);
+            a.cov[(item * a.chs + ch) * (long)a.nsub + s] = dz != 0.0 ? (float)(dz * a.w[ch] * cnt) : -0.f;      // -0.f: LD_EMPTY_GATE
         }
     }
 }
@@ -441,8 +460,18 @@ __device__ __forceinline__ PkSpan pk_span(long N, long S, long G) {
 __device__ __forceinline__ void pk_take(float& m, int& k, float v, int i) {
     if (v > m || (v == m && i < k)) { m = v; k = i; }
 }
-// a NaN sample makes the peak NaN (as torch.max does); fmaxf would drop it
-__device__ __forceinline__ float pk_abs(float v) { return v != v ? INFINITY : fabsf(v); }
+// A NaN sample makes the peak NaN (as torch.max does; fmaxf would drop it). Through the reduction it travels as +inf at a NEGATIVE index
+// (the sample's index with PK_NAN set: in-row indices stay below 2^30), which wins every tie with a true inf; pk_peak turns it back.
+constexpr int PK_NAN = (int)0x80000000;
+__device__ __forceinline__ void pk_see(float& m, int& k, float v, int i) {
+    const bool nan = v != v;
+    pk_take(m, k, nan ? INFINITY : fabsf(v), nan ? (i | PK_NAN) : i);
+}
+__device__ __forceinline__ double pk_peak(float m, int& k) {
+    if (k >= 0) return (double)m;
+    k &= ~PK_NAN;
+    return (double)NAN;
+}
 
 // MODE 0: partials[(r G + g) 2 + {0, 1}] = (max |x|, its lowest index) as doubles;  MODE 1: partials[r G + g] = sum g x (fp64, fixed order)
 template <int MODE>
@@ -459,10 +488,10 @@ __global__ void __launch_bounds__(PK_NT) pk_reduce_kernel(const float* __restric
     for (int v = tid; v < s.nvec; v += PK_NT) {
         const f4u q = __builtin_nontemporal_load(xv + v);
         if (MODE == 0) {
-            pk_take(m, k, pk_abs(q.x), s.s0 + 4 * v);
-            pk_take(m, k, pk_abs(q.y), s.s0 + 4 * v + 1);
-            pk_take(m, k, pk_abs(q.z), s.s0 + 4 * v + 2);
-            pk_take(m, k, pk_abs(q.w), s.s0 + 4 * v + 3);
+            pk_see(m, k, q.x, s.s0 + 4 * v);
+            pk_see(m, k, q.y, s.s0 + 4 * v + 1);
+            pk_see(m, k, q.z, s.s0 + 4 * v + 2);
+            pk_see(m, k, q.w, s.s0 + 4 * v + 3);
         } else {
             const f4u h = __builtin_nontemporal_load(gv + v);
             acc += (double)fmaf(q.w, h.w, fmaf(q.z, h.z, fmaf(q.y, h.y, q.x * h.x)));
@@ -470,7 +499,7 @@ __global__ void __launch_bounds__(PK_NT) pk_reduce_kernel(const float* __restric
     }
     const int i = 4 * s.nvec + tid;
     if (tid < 4 && i < s.len) {
-        if (MODE == 0) pk_take(m, k, pk_abs(x[s.off + i]), s.s0 + i);
+        if (MODE == 0) pk_see(m, k, x[s.off + i], s.s0 + i);
         else acc += (double)(x[s.off + i] * gy[s.off + i]);
     }
     if (MODE == 0) {
@@ -495,8 +524,8 @@ __global__ void __launch_bounds__(PK_NT) pk_reduce_kernel(const float* __restric
     }
 }
 
-// MODE 0: y = x * scale / max(p, eps), peak[r] = (p, k) saved for the backward pass
-// MODE 1: gx = scale (g / p - [n == k] sign(x[k]) D / p^2) for p > eps, scale g / eps otherwise (src = g)
+// MODE 0: y = x * scale / max(p, eps), peak[r] = (p, k) saved for the backward pass; p is NaN for a row that holds a NaN (y is NaN throughout)
+// MODE 1: gx = scale (g / p - [n == k] sign(x[k]) D / p^2) for p > eps, scale g / eps for p <= eps, NaN throughout for a NaN p (src = g)
 template <int MODE>
 __global__ void __launch_bounds__(PK_NT) pk_apply_kernel(const float* __restrict__ src, const float* __restrict__ x, const double* __restrict__ partials,
                                                          double* __restrict__ peak, float* __restrict__ dst, long N, long S, long G, double scale,
@@ -511,15 +540,15 @@ __global__ void __launch_bounds__(PK_NT) pk_apply_kernel(const float* __restrict
             float m = -1.f;
             int k = 0x7fffffff;
             for (long g = 0; g < G; ++g) pk_take(m, k, (float)partials[(r * G + g) * 2], (int)partials[(r * G + g) * 2 + 1]);
-            if (s.s0 == 0) { peak[2 * r] = (double)m; peak[2 * r + 1] = (double)k; }
-            const double p = (double)m;
-            mul_s = (float)(scale / (p > eps ? p : eps));
+            const double p = pk_peak(m, k);                  // NaN for a row that holds one, k then the index of its first NaN
+            if (s.s0 == 0) { peak[2 * r] = p; peak[2 * r + 1] = (double)k; }
+            mul_s = (float)(scale / (p <= eps ? eps : p));   // (not p > eps ? p : eps, which reads a NaN peak as silence)
             k_s = -1;
             fix_s = 0.f;
         } else {
             const double p = peak[2 * r];
             const int k = (int)peak[2 * r + 1];
-            if (p > eps) {
+            if (!(p <= eps)) {                               // a NaN peak comes this way too: mul_s and fix_s are NaN, and so is the row
                 double D = 0.0;
                 for (long g = 0; g < G; ++g) D += partials[r * G + g];
                 const float xk = x[r * N + k];

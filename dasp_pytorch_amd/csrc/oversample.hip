@@ -28,7 +28,7 @@ constexpr int OS_HMAX = 16;                  // half width of the taps in base s
 constexpr int OS_LMAX = 8;
 constexpr int OS_SLOTS = 4096;               // oversampled samples per workgroup in LDS (16 KiB), halo included
 constexpr int OS_TAP_ROWS = 2 * OS_HMAX + 3;
-struct OsTaps { float h[OS_TAP_ROWS * OS_LMAX]; };          // h[(k + 1) L + p] = hp[k L + p]: a row of zeros in front, zeros past 2 H L
+struct OsTaps { float h[OS_TAP_ROWS * OS_LMAX]; };          // h[(k + 1) L + p] = hp[k L + p]: a row of zeros in front, zeros past 2 H L (padding that no loop multiplies)
 
 // sech^2 in the form of elementwise.hip, 4 e / (1 + e)^2 with e = exp(-2 |u|): keeps its relative accuracy where tanh saturates. On the
 // hardware exponential and reciprocal (1 ulp each; the argument's rounding costs e a relative 1e-6 only where e < 1e-10): this kernel is
@@ -76,7 +76,7 @@ osdist_kernel(const float* __restrict__ x, const float* __restrict__ drive_db, c
 #pragma unroll
         for (int p = 0; p < L; ++p) u[p] = w[p] = 0.f;
         if (q >= 0 && q < N) {
-            for (int d = 0; d < nk; ++d) {
+            for (int d = 0; d < nk - 1; ++d) {
                 const float xv = xs[qi + 2 * H - d];
                 const float gv = BWD ? gs[qi + 2 * H - d] : 0.f;
 #pragma unroll
@@ -86,6 +86,9 @@ osdist_kernel(const float* __restrict__ x, const float* __restrict__ drive_db, c
                     if (BWD) w[p] = __builtin_fmaf(hv, gv, w[p]);
                 }
             }
+            // d = 2 H: phase 0 alone has a tap there (hp[2 H L]); the padded zeros of the other phases are not multiplied, 0 x inf is NaN
+            u[0] = __builtin_fmaf(taps.h[nk * L], xs[qi], u[0]);
+            if (BWD) w[0] = __builtin_fmaf(taps.h[nk * L], gs[qi], w[0]);
             const bool own = qi >= H && qi < H + T;
 #pragma unroll
             for (int p = 0; p < L; ++p) {
@@ -112,13 +115,31 @@ osdist_kernel(const float* __restrict__ x, const float* __restrict__ drive_db, c
         float a0[L], a1[L];
 #pragma unroll
         for (int p = 0; p < L; ++p) a0[p] = a1[p] = 0.f;
-        for (int e = 0; e <= H; ++e) {
+        // the first and the last pair are peeled: tap -1 (e = 0, output ni + 1), tap 2 H + 1 (e = H, output ni) and, for the phases
+        // p > 0, tap 2 H are padded zeros, and a NaN or inf word under them belongs to a neighbouring output's footprint, not to these
+#pragma unroll
+        for (int p = 0; p < L; ++p) {
+            const f2 v = *reinterpret_cast<const f2*>(&vs[p * TQ + ni]);
+            const float h0 = taps.h[L + p], hp = taps.h[2 * L + p];
+            a0[p] = __builtin_fmaf(hp, v.y, __builtin_fmaf(h0, v.x, a0[p]));
+            a1[p] = __builtin_fmaf(h0, v.y, a1[p]);
+        }
+        for (int e = 1; e < H; ++e) {
 #pragma unroll
             for (int p = 0; p < L; ++p) {
                 const f2 v = *reinterpret_cast<const f2*>(&vs[p * TQ + ni + 2 * e]);
                 const float hm = taps.h[2 * e * L + p], h0 = taps.h[(2 * e + 1) * L + p], hp = taps.h[(2 * e + 2) * L + p];
                 a0[p] = __builtin_fmaf(hp, v.y, __builtin_fmaf(h0, v.x, a0[p]));
                 a1[p] = __builtin_fmaf(h0, v.y, __builtin_fmaf(hm, v.x, a1[p]));
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < L; ++p) {
+            const f2 v = *reinterpret_cast<const f2*>(&vs[p * TQ + ni + 2 * H]);
+            a1[p] = __builtin_fmaf(taps.h[2 * H * L + p], v.x, a1[p]);
+            if (p == 0) {
+                a0[0] = __builtin_fmaf(taps.h[(2 * H + 1) * L], v.x, a0[0]);
+                a1[0] = __builtin_fmaf(taps.h[(2 * H + 1) * L], v.y, a1[0]);
             }
         }
         float s0 = a0[0], s1 = a1[0];

@@ -293,8 +293,8 @@ __device__ __forceinline__ void mix_pan(float pan, double& l, double& r, double&
     l = sqrt(ul); r = sqrt(ur);
     if (DERIV) {
         const double dul = ip * (-c - (hp - th) * sn), dur = ip * (sn + th * c);       // d/dtheta
-        dl = ul > 0.0 ? 0.5 * dul / l * hp : 0.0;
-        dr = ur > 0.0 ? 0.5 * dur / r * hp : 0.0;
+        dl = ul > 0.0 ? 0.5 * dul / l * hp : (ul != ul ? ul : 0.0);        // (a NaN pan is no hard pan: its gradient is NaN)
+        dr = ur > 0.0 ? 0.5 * dur / r * hp : (ur != ur ? ur : 0.0);
     }
 }
 

@@ -500,7 +500,12 @@ def loudness(x: torch.Tensor, sample_rate: float):
     L, R, C, Ls, Rs with the weights 1, 1, 1, 1.41, 1.41 -> (bs,). K-weighting (signal.k_weighting_sos), 400 ms blocks every 100 ms - a
     tail that does not complete a block is ignored -, the absolute gate at -70 LUFS and the relative gate 10 LU below the gated mean.
     An item with no block past the gates gives -inf and a zero gradient. Differentiable with respect to x with the gates held fixed
-    (what autograd of a masked mean gives). 8000 <= sample_rate <= 384000 and seq_len >= one block, else ValueError."""
+    (what autograd of a masked mean gives). 8000 <= sample_rate <= 384000 and seq_len >= one block, else ValueError.
+    Non-finite samples: the gates are IEEE comparisons, so a block that holds a NaN (every block from a NaN or inf sample on: the
+    K-weighting is recursive) passes neither and is left out of the mean. A NaN in the middle of an item therefore gives a FINITE
+    loudness, measured on the blocks before it, and a gradient that is NaN over the whole row that holds it (the item's other rows stay
+    finite); a NaN in the first block gives -inf and a zero gradient. Other items are not affected. A sample as large as 1e30 is
+    metered (+567 LUFS); its gradient underflows float32 to 0."""
     _level_rows(x, "loudness", sample_rate, 5)
     return _LoudnessFunction.apply(x, float(sample_rate))
 
@@ -524,7 +529,9 @@ def loudness_normalize(x: torch.Tensor, sample_rate: float, target_lufs=-23.0):
 def peak_normalize(x: torch.Tensor, sample_rate: float, peak_db: float = 0.0, eps: float = 1e-8):
     """Per row - per (item, channel), as the reference's examples do by hand (examples/auto_eq.py:289-291) -:
     y = x * 10^(peak_db / 20) / max(max_n |x[n]|, eps); eps = 0 is the examples' plain division. Differentiable: the maximum's
-    gradient goes to the lowest index attaining it."""
+    gradient goes to the lowest index attaining it; a peak of exactly eps takes the constant branch (gy * scale / eps).
+    A row that holds a NaN has a NaN peak, as x.abs().amax(-1) has: the row and its gradient are NaN throughout. A row that holds an inf
+    comes out as 0 with a NaN at that sample. eps = 0 on a row of zeros gives NaN (0 / 0). Other rows are not affected."""
     _level_rows(x, "peak_normalize")
     peak_db, eps = float(peak_db), float(eps)
     if not (peak_db == peak_db and abs(peak_db) != float("inf")) or not eps >= 0.0:

@@ -378,7 +378,11 @@ int dasp_bus_backward(const float* x, const float* send_db, const float* gy, flo
  *     (two per compute unit). It fixes the layout of partials (B, segments, T, 2 or 4) and nothing else: what is computed for a sample of
  *     mix, send or gx does not depend on it.
  *   partials: dasp_stereo_mix_partial_floats(B, T, N, with_send) floats of scratch for the backward call (two launches, no atomics:
- *     results are bit-identical run to run). */
+ *     results are bit-identical run to run).
+ *   Non-finite input: a NaN or +-inf sample of a track reaches that sample of both channels of its item's mix and send - through a
+ *     muted (gain_db = -inf) or hard-panned track too: 0 x NaN - and nothing else there; gx does not depend on x; that track's three
+ *     control gradients are non-finite and no other's. A NaN control makes the item's buses, that track's gx and its control gradients
+ *     NaN (a NaN pan is not read as a hard pan, whose vanishing term is dropped). Other items keep every bit. */
 int dasp_stereo_mix_segment(long B, long N);
 int dasp_stereo_mix_max_tracks(void);
 long dasp_stereo_mix_partial_floats(long B, int T, long N, int with_send);
@@ -396,7 +400,11 @@ int dasp_stereo_mix_backward(const float* x, const float* gain_db, const float* 
  * Backward: gx = dL/dx and gdrive = dL/d(drive_db), u recomputed; partials is scratch of dasp_osdist_partial_floats(B * C, N, L) floats =
  * rows * ceil(N / dasp_osdist_tile(L)), one per workgroup, summed in fp64 by a second launch: no atomics, bit-identical run to run.
  * L one of 2, 4, 8 and 1 <= H <= 16; anything else, a null pointer or a non-positive size: DASP_ERR_ARG (-1 from the size queries);
- * B * C * ceil(N / tile) >= 2^31: DASP_ERR_UNSUPPORTED. All of it is checked before taps is read and before any launch. */
+ * B * C * ceil(N / tile) >= 2^31: DASP_ERR_UNSUPPORTED. All of it is checked before taps is read and before any launch.
+ * Non-finite input: a NaN sample x[j] (or gy[j]) makes y and gx (gx) NaN on [j - 2 H, j + 2 H] of its row and nowhere else, and gdrive
+ * of the row NaN. A +-inf or huge sample saturates tanh: y and gx stay finite everywhere (the zeros that pad the taps to whole rows of L
+ * are never multiplied - 0 x inf); gdrive of the row is NaN for +-inf (0 x inf in sum s u) and finite for a huge finite sample. A NaN
+ * drive_db makes its row NaN. Other rows keep every bit. */
 int dasp_osdist_tile(int L);
 long dasp_osdist_partial_floats(long rows, long N, int L);
 int dasp_osdist_forward(const float* x, const float* drive_db, const float* taps, float* y, int B, int C, long N, int L, int H, void* stream);
@@ -581,8 +589,20 @@ int dasp_fdfir_backward(const float* x, const void* H, const float* gy, const vo
  *   L: (items) LUFS, -inf for an empty gate.  ysave, cov: both NULL (value only), or the K-weighted signal (items, chs, N) and the
  *   coverage weights (items, chs, blocks + 3) kept for dasp_loudness_backward;  gL: (items) upstream gradient.
  *   No atomics, nothing to zero, no host synchronisation: bit-identical run to run, plain kernel nodes under capture.
+ *   Non-finite samples: the gates are IEEE comparisons on the block powers, so a block that holds a NaN (every block from a NaN or
+ *   +-inf sample on: the filter is recursive) passes neither gate and is left out - L is finite where clean blocks remain, -inf where
+ *   none does; it is never read as silence inside a block that counts. The gradient of the ROW that holds the sample is NaN throughout
+ *   whenever L is finite (NaN x a coverage weight of 0, filtered backwards over the row; a NaN in the ignored tail too), the item's other
+ *   rows stay finite; a NaN gL makes the item's gradient NaN. An item with an empty gate (L = -inf) has a gradient of exactly 0,
+ *   whatever its samples and gL hold: the forward call marks it with -0.f throughout its rows of cov, and the backward call then reads
+ *   neither ysave nor gL for it. A sample whose square leaves float32 (|K-weighted x| > 1.8e19) is summed in fp64: L is finite (1e30
+ *   reads +567 LUFS); the coverage weights are fp32 (about 1 / (block power x 4 H)): beyond some +340 LUFS they turn denormal and
+ *   then 0, and so does the gradient. Other items keep every bit.
  * Peak normalisation per row: y = x 10^(peak_db / 20) / max(max |x|, eps);  peak: (rows, 2) doubles written by the forward call
  * (the maximum and the lowest index attaining it) and read by the backward call;  scratch: dasp_peaknorm_scratch_doubles(...) doubles.
+ *   A row that holds a NaN has a NaN peak, as torch.max has (peak = (NaN, index of the first NaN)): y and gx of that row are NaN
+ *   throughout. A +-inf sample: y is 0 with a NaN at the sample, gx 0 with a NaN at the index of the maximum. eps = 0 on a row of zeros:
+ *   y is NaN (0 / 0) and gx +-inf. The constant branch of the gradient is taken for peak <= eps (a peak equal to eps included).
  * ------------------------------------------------------------------------------------------- */
 int dasp_loudness_kweighting(double sample_rate, double* sos12);
 long dasp_loudness_blocks(long N, double sample_rate);

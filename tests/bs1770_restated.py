@@ -116,7 +116,8 @@ def loudness_normalize(x, fs, target, gy=None):
 
 
 def peak_normalize(x, peak_db=0.0, eps=1e-8, gy=None):
-    """Per row: y = x s / max(max|x|, eps), s = 10^(peak_db / 20); gradient per the closed form, the maximum at its lowest index."""
+    """Per row: y = x s / max(max|x|, eps), s = 10^(peak_db / 20); gradient per the closed form, the maximum at its lowest index. A row
+    that holds a NaN has a NaN peak: y and the gradient are NaN throughout."""
     x = np.asarray(x, np.float64)
     s = 10.0 ** (peak_db / 20.0)
     p = np.abs(x).max(-1, keepdims=True)
@@ -129,7 +130,9 @@ def peak_normalize(x, peak_db=0.0, eps=1e-8, gy=None):
     gx = np.empty_like(x)
     for idx in np.ndindex(x.shape[:-1]):
         pp = p[idx][0]
-        if pp > eps:
+        if pp != pp:                                  # a NaN in the row: the peak is NaN and so is every derivative through it (torch's
+            g = np.full_like(gy[idx], np.nan)         # autograd of x * s / x.abs().amax(-1, keepdim=True).clamp(min=eps) says the same)
+        elif pp > eps:
             g = s * gy[idx] / pp
             g[k[idx]] -= s * np.sign(x[idx][k[idx]]) * np.dot(gy[idx], x[idx]) / pp ** 2
         else:
