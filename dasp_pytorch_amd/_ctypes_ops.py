@@ -846,6 +846,53 @@ class OversampledDistortionFunction(torch.autograd.Function):
         return gx.to(xd), gd.reshape(dshape).to(dd), None, None, None
 
 
+class ModulatedDelayFunction(torch.autograd.Function):
+    """y = (1 - mix) x + (mix / V) sum of V delay-line taps whose delays a sine LFO moves (dasp_moddelay_forward / _backward,
+    csrc/moddelay.hip). delay_ms, depth_ms, rate_hz, phase: bs * V values each; mix: bs values; sample_rate, max_delay_ms, stereo_spread:
+    floats; H = ceil(sample_rate / 1000 * max_delay_ms). Saves x, the controls packed as (bs, V, 4), and mix: the backward kernel
+    recomputes the taps from x in LDS."""
+
+    @staticmethod
+    def forward(ctx, x, delay_ms, depth_ms, rate_hz, phase, mix, sample_rate, max_delay_ms, stereo_spread, H):
+        _lib.require_device(x, "x")
+        B, C, N = x.shape
+        ctls = (delay_ms, depth_ms, rate_hz, phase, mix)
+        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
+        ctx.cfg = (float(sample_rate), float(max_delay_ms), float(stereo_spread), int(H))
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            return torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            ctl = torch.stack([c.detach().reshape(B, -1).to(device=x.device, dtype=torch.float32) for c in ctls[:4]], dim=-1).contiguous()
+            m32 = mix.detach().reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
+            y = torch.empty_like(x32)
+            call("dasp_moddelay_forward", ptr(x32), ptr(ctl), ptr(m32), ptr(y), B, C, N, ctl.shape[1], int(H), *ctx.cfg[:3], stream())
+            ctx.save_for_backward(x32, ctl, m32)
+        return y.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xd, cmeta = ctx.meta
+        if ctx.empty:
+            return (torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 4
+        sample_rate, max_delay_ms, stereo_spread, H = ctx.cfg
+        x32, ctl, m32 = ctx.saved_tensors
+        B, C, N = x32.shape
+        V = ctl.shape[1]
+        with torch.cuda.device(x32.device):
+            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # the scatter pass is skipped when x needs no gradient
+            gctl = torch.empty_like(ctl)
+            gmix = torch.empty_like(m32)
+            partials = torch.empty(_lib.lib().dasp_moddelay_partial_floats(B * C, N, V, H), dtype=torch.float32, device=x32.device)
+            g32 = _f32c(gy)
+            call("dasp_moddelay_backward", ptr(x32), ptr(ctl), ptr(m32), ptr(g32), ptr(gx), ptr(gctl), ptr(gmix), ptr(partials), B, C, N, V, H,
+                 sample_rate, max_delay_ms, stereo_spread, stream())
+        gc = [gctl[..., q].reshape(s).to(d) for q, (d, s) in enumerate(cmeta[:4])] + [gmix.reshape(cmeta[4][1]).to(cmeta[4][0])]
+        return (None if gx is None else gx.to(xd),) + tuple(gc) + (None,) * 4
+
+
 _FSPEC_CACHE = {}
 
 

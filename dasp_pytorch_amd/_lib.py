@@ -88,6 +88,12 @@ SIGNATURES = {
     "dasp_osdist_partial_floats": (_l, [_l, _l, _i]),
     "dasp_osdist_forward": (_i, [_p, _p, ctypes.POINTER(ctypes.c_float), _p, _i, _i, _l, _i, _i, _p]),
     "dasp_osdist_backward": (_i, [_p, _p, ctypes.POINTER(ctypes.c_float)] + [_p] * 4 + [_i, _i, _l, _i, _i, _p]),
+    "dasp_moddelay_max_voices": (_i, []),
+    "dasp_moddelay_max_delay_samples": (_i, []),
+    "dasp_moddelay_tile": (_i, [_i]),
+    "dasp_moddelay_partial_floats": (_l, [_l, _l, _i, _i]),
+    "dasp_moddelay_forward": (_i, [_p] * 4 + [_i, _i, _l, _i, _i, _d, _d, _d, _p]),
+    "dasp_moddelay_backward": (_i, [_p] * 8 + [_i, _i, _l, _i, _i, _d, _d, _d, _p]),
     "dasp_mrstft_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i]),
     "dasp_mrstft_table": (_i, [_p, _p]),
     "dasp_mrstft_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),

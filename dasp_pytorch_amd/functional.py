@@ -1,6 +1,7 @@
 """Drop-in for dasp_pytorch.functional on MI355X: same names, argument order and keyword names
 (dasp_pytorch/functional.py), every effect computed by hand-written HIP kernels (csrc/)."""
 import ctypes
+import math
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -9,8 +10,8 @@ from . import signal as _signal
 from . import _mt19937
 from . import ops as _ops
 from . import _lib
-from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, OversampledDistortionFunction, PannerFunction, StereoMixFunction,
-                  WidenerFunction)
+from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
+                  StereoMixFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
 
@@ -89,6 +90,39 @@ def oversampled_distortion(x: torch.Tensor, sample_rate: int, drive_db: torch.Te
     require_fp32_ok(x, "oversampled_distortion")
     oversample, half_width = int(oversample), int(half_width)
     return OversampledDistortionFunction.apply(x, drive_db, _oversampling_taps_f32(oversample, half_width, beta, cutoff), oversample, half_width)
+
+
+def modulated_delay(x: torch.Tensor, sample_rate: float, delay_ms: torch.Tensor, depth_ms: torch.Tensor, rate_hz: torch.Tensor,
+                    phase: torch.Tensor, mix: torch.Tensor, max_delay_ms: float = 40.0, stereo_spread: float = 0.25):
+    """Chorus / flanger / vibrato: V voices of a delay line whose length a sine LFO moves, mixed with the dry signal. x (bs, chs, seq_len);
+    delay_ms, depth_ms, rate_hz and phase hold bs*V values each, shaped (bs,) or (bs, V), V = numel / bs voices, 1 <= V <= 8; mix holds
+    bs values. phase and stereo_spread are in turns. For item b, voice v, channel c and sample n, with x zero outside the signal:
+        theta = 2 pi (rate_hz n / sample_rate + phase + c stereo_spread)
+        d = clamp(sample_rate/1000 (delay_ms + depth_ms sin theta), 0, sample_rate/1000 max_delay_ms);  p = n - d, i = floor(p), f = p - i
+        tap_v[n] = Catmull-Rom interpolation of x[i-1], x[i], x[i+1], x[i+2] at f;   y[n] = (1 - mix) x[n] + mix (1/V) sum_v tap_v[n]
+    A flanger is one voice of 1-5 ms with mix = 0.5; a chorus a few voices of 10-30 ms at different phases; a vibrato mix = 1. The read
+    position is float64 in the kernel, the interpolation float32 (csrc/moddelay.hip). The op works on whole tensors, not on a stream:
+    where d < 1 sample the four-point footprint reaches x[n+1]. There is no feedback path.
+    Differentiable in x and in all five controls; the delay gradients take no contribution from samples where d was clamped - size
+    max_delay_ms (a plain float, like stereo_spread; at most 8192 samples) so that delay_ms + depth_ms stays inside it.
+    float32 only. A wrong control count raises RuntimeError naming the control; more than 8 voices or a max_delay_ms beyond 8192
+    samples raise DaspHipError (unsupported configuration)."""
+    bs, chs, seq_len = x.size()
+    n = delay_ms.numel()
+    if bs and (n == 0 or n % bs != 0):
+        raise RuntimeError(f"delay_ms: shape '[{bs}, -1]' is invalid for input of size {n}")
+    for name, c in (("depth_ms", depth_ms), ("rate_hz", rate_hz), ("phase", phase)):
+        if c.numel() != n:
+            raise RuntimeError(f"{name}: shape '[{bs}, {n // bs if bs else 0}]' is invalid for input of size {c.numel()}")
+    if mix.numel() != bs:
+        raise RuntimeError(f"mix: shape '[{bs}]' is invalid for input of size {mix.numel()}")
+    max_delay_ms, stereo_spread = float(max_delay_ms), float(stereo_spread)
+    if not (max_delay_ms >= 0.0 and max_delay_ms != float("inf")) or stereo_spread - stereo_spread != 0.0 or not float(sample_rate) > 0.0:
+        raise ValueError(f"modulated_delay: sample_rate > 0, finite max_delay_ms >= 0 and finite stereo_spread, got {sample_rate}, {max_delay_ms}, {stereo_spread}")
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "modulated_delay")
+    H = max(1, math.ceil(float(sample_rate) / 1000.0 * max_delay_ms))
+    return ModulatedDelayFunction.apply(x, delay_ms, depth_ms, rate_hz, phase, mix, float(sample_rate), max_delay_ms, stereo_spread, H)
 
 
 def stereo_bus(x: torch.Tensor, sample_rate: int, send_db: torch.Tensor):

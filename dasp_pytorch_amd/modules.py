@@ -333,6 +333,41 @@ class OversampledDistortion(Processor):
         self.param_ranges = {"drive_db": (min_gain_db, max_gain_db)}
 
 
+_MODDELAY_ARGS = ("delay_ms", "depth_ms", "rate_hz", "phase")
+
+
+class ModulatedDelay(Processor):
+    """Chorus / flanger / vibrato (functional.modulated_delay) with `voices` delay voices. One voice: the parameters delay_ms, depth_ms,
+    rate_hz, phase, mix, the functional's own argument names. More: voice0_delay_ms, voice0_depth_ms, voice0_rate_hz, voice0_phase,
+    voice1_delay_ms, ... and mix last, 4 * voices + 1 columns. max_delay_ms is max_delay_ms + max_depth_ms of the ranges, so no value
+    inside them is ever clamped."""
+
+    def __init__(self, sample_rate: int, voices: int = 1, min_delay_ms: float = 0.0, max_delay_ms: float = 30.0, min_depth_ms: float = 0.0,
+                 max_depth_ms: float = 5.0, min_rate_hz: float = 0.05, max_rate_hz: float = 10.0, min_phase: float = 0.0, max_phase: float = 1.0,
+                 min_mix: float = 0.0, max_mix: float = 1.0, stereo_spread: float = 0.25):
+        super().__init__()
+        if int(voices) != voices or voices < 1:
+            raise ValueError(f"voices must be a positive integer, got {voices}")
+        self.sample_rate = sample_rate
+        self.voices = int(voices)
+        self.max_delay_ms = float(max_delay_ms) + float(max_depth_ms)
+        self.stereo_spread = stereo_spread
+        ranges = {"delay_ms": (min_delay_ms, max_delay_ms), "depth_ms": (min_depth_ms, max_depth_ms), "rate_hz": (min_rate_hz, max_rate_hz),
+                  "phase": (min_phase, max_phase)}
+        if self.voices == 1:
+            self.param_ranges = dict(ranges)
+            self.process_fn = functools.partial(F.modulated_delay, max_delay_ms=self.max_delay_ms, stereo_spread=stereo_spread)
+        else:
+            self.param_ranges = {f"voice{v}_{name}": ranges[name] for v in range(self.voices) for name in _MODDELAY_ARGS}
+            self.process_fn = self._process_voices
+        self.param_ranges["mix"] = (min_mix, max_mix)
+
+    def _process_voices(self, x, sample_rate, **kwargs):
+        """The voice{v}_... columns stacked into the functional's (bs, voices) controls."""
+        ctl = [torch.stack([kwargs[f"voice{v}_{name}"] for v in range(self.voices)], dim=-1) for name in _MODDELAY_ARGS]
+        return F.modulated_delay(x, sample_rate, *ctl, kwargs["mix"], max_delay_ms=self.max_delay_ms, stereo_spread=self.stereo_spread)
+
+
 def _eq_ranges(sample_rate, g, q):
     top = (sample_rate // 2) - 1000
     cut = {"low_shelf": (20, 2000), "band0": (80, 2000), "band1": (2000, 8000), "band2": (8000, 12000), "band3": (12000, top),

@@ -16,7 +16,8 @@ import torch
 
 from . import _lib, config
 from ._ctypes_ops import (FILTER_TYPES, BiquadFunction, BusFunction, ChainControlsFunction, DistortionFunction, DistortionSampleFunction,   # noqa: F401
-                          DynamicsCtlFunction, DynamicsFunction, DynamicsMatrixFunction, GainFunction, OversampledDistortionFunction, PannerFunction,
+                          DynamicsCtlFunction, DynamicsFunction, DynamicsMatrixFunction, GainFunction, ModulatedDelayFunction, OversampledDistortionFunction,
+                          PannerFunction,
                           ParametricEQFunction,
                           ParametricEQNormFunction, ReverbFunction, SosFiltFunction, StereoMixFunction, WidenerFunction, _dyn_counters, _filter_spectrum, _seed_offset,
                           _SosWork, chain_eq_compressor_forward, reverb_noise)

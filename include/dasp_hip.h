@@ -411,6 +411,38 @@ int dasp_osdist_forward(const float* x, const float* drive_db, const float* taps
 int dasp_osdist_backward(const float* x, const float* drive_db, const float* taps, const float* gy, float* gx, float* gdrive, float* partials,
                          int B, int C, long N, int L, int H, void* stream);
 
+/* modulated_delay: chorus / flanger / vibrato - V voices of a delay line whose length a sine LFO moves, read with Catmull-Rom
+ * interpolation and mixed with the dry signal, one kernel per direction (csrc/moddelay.hip).  x, y, gy, gx (B, C, N) fp32; ctl, gctl
+ * (B, V, 4) fp32, per voice (delay_ms, depth_ms, rate_hz, phase in turns); mix, gmix (B).  For item b, voice v, channel c, sample n, with x
+ * zero outside [0, N):
+ *   theta = 2 pi (rate_hz n / sample_rate + phase + c stereo_spread)
+ *   d = clamp(sample_rate/1000 (delay_ms + depth_ms sin theta), 0, sample_rate/1000 max_delay_ms),  p = n - d,  i = floor(p),  f = p - i
+ *   tap_v[n] = sum_{k = -1 .. 2} w_k(f) x[i + k]  (Catmull-Rom),   y[n] = (1 - mix) x[n] + (mix / V) sum_v tap_v[n]
+ * theta, d, p and i are float64 in the kernels; f is rounded to float32 and everything after it is float32. For d < 1 the footprint
+ * reaches x[n + 1].
+ * H: a whole number of samples with sample_rate/1000 max_delay_ms <= H <= dasp_moddelay_max_delay_samples(); it sets the staged window
+ * and the tile, dasp_moddelay_tile(H) samples per workgroup.  1 <= V <= dasp_moddelay_max_voices().
+ * Backward: gx (NULL: not computed), gctl and gmix, x's taps recomputed; partials is scratch of
+ * dasp_moddelay_partial_floats(B * C, N, V, H) = rows * ceil(N / tile) * (4 V + 1) floats, summed in fp64 in a fixed order by a second
+ * launch. No global atomics. y, gctl and gmix are bit-identical run to run; gx is accumulated with LDS float adds whose order varies:
+ * equal to rounding. The delay gradients take no contribution from samples where d was clamped.
+ * A null pointer (gx apart), a non-positive size, V < 1, H < 1, H below the largest delay, a sample rate that is not positive or a
+ * non-finite max_delay_ms / stereo_spread: DASP_ERR_ARG (-1 from the size queries); V or H above its maximum, or
+ * B * C * ceil(N / tile) >= 2^31: DASP_ERR_UNSUPPORTED (-2 from the size queries). All of it is checked before any launch.
+ * Non-finite input: all four products of a tap are always formed, and so is the dry term - a NaN or inf sample under a zero weight
+ * gives NaN. A control that makes p NaN reads at i = n (nothing out of range) with f = NaN: the item's y, gx, gmix and that voice's
+ * gradients are NaN.
+ * Other items keep every bit. */
+int dasp_moddelay_max_voices(void);
+int dasp_moddelay_max_delay_samples(void);
+int dasp_moddelay_tile(int H);
+long dasp_moddelay_partial_floats(long rows, long N, int V, int H);
+int dasp_moddelay_forward(const float* x, const float* ctl, const float* mix, float* y, int B, int C, long N, int V, int H, double sample_rate,
+                          double max_delay_ms, double stereo_spread, void* stream);
+int dasp_moddelay_backward(const float* x, const float* ctl, const float* mix, const float* gy, float* gx, float* gctl, float* gmix,
+                           float* partials, int B, int C, long N, int V, int H, double sample_rate, double max_delay_ms, double stereo_spread,
+                           void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Multi-resolution STFT loss, the op downstream of the effect chain in the reference's training loops
  * (auraloss.freq.MultiResolutionSTFTLoss(): examples/style_transfer.py:341,363, auto_eq.py:252, virtual_analog.py:288; auraloss is
