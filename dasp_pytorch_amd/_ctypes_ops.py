@@ -8,6 +8,13 @@ The product's autograd binding is the PyTorch extension (csrc/torch_ext -> torch
    and it owns the dtype / device / shape error messages of the calls the extension does not take.
 PyTorch is used for device memory, streams and autograd plumbing only; every number is produced by the HIP kernels in csrc/. Nothing here
 falls back to torch math on a missing library or a CPU tensor.
+
+What every Function here owes autograd (tests/test_gpu_autograd_contract.py): backward returns None for an input that needs no gradient
+and a tensor of the input's own dtype and shape otherwise; what it reads was written by its own forward and is left as it was, so a
+graph can be differentiated again (retain_graph) and two graphs in any order; a caller's tensor the backward reads again - a contiguous
+float32 x or control is kept as it is, not copied - goes through save_for_backward, so overwriting it between forward and backward raises
+autograd's "modified by an inplace operation" error; everything else (tables, carries, copies) is the forward's own. Contiguous copies of
+several upstream gradients are held in named variables until the call is queued: a temporary's block is handed to the next copy.
 """
 import ctypes
 
@@ -22,6 +29,11 @@ FILTER_TYPES = {"peaking": 0, "low_shelf": 1, "high_shelf": 2, "low_pass": 3, "h
 
 def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
+
+
+def _needed(ctx, grads):
+    """What a backward returns for an empty input: the gradients, None where the input needs none."""
+    return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad))
 
 
 def _pad_sections(S):
@@ -153,7 +165,7 @@ class SosFiltFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         if ctx.empty:
-            return torch.zeros(ctx.shapes[0], dtype=ctx.dtypes[0], device=gy.device), torch.empty(ctx.shapes[1], dtype=ctx.dtypes[1], device=gy.device)
+            return _needed(ctx, (torch.zeros(ctx.shapes[0], dtype=ctx.dtypes[0], device=gy.device), torch.empty(ctx.shapes[1], dtype=ctx.dtypes[1], device=gy.device)))
         (x32,) = ctx.saved_tensors
         with torch.cuda.device(x32.device):
             gx, gsos = ctx.work.backward(x32, _f32c(gy), 0, 0, ctx.needs_input_grad[1], ctx.needs_input_grad[0])
@@ -190,7 +202,7 @@ class BiquadFunction(torch.autograd.Function):
             with torch.cuda.device(jac.device):
                 call("dasp_biquad_backward", ptr(jac), ptr(gba.to(torch.float64).contiguous()), n, ptr(gp), stream())
         cols = gp.unbind(1)
-        return tuple(c.reshape(shape).to(dt) for c, (dt, shape) in zip(cols, ctx.meta)) + (None, None)
+        return tuple(c.reshape(shape).to(dt) if need else None for c, (dt, shape), need in zip(cols, ctx.meta, ctx.needs_input_grad)) + (None, None)
 
 
 class ParametricEQFunction(torch.autograd.Function):
@@ -243,7 +255,7 @@ class ParametricEQFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         if ctx.empty:
-            return (torch.empty_like(gy), None, None) + tuple(torch.zeros(shape, dtype=dt, device=gy.device) for dt, shape in ctx.ctl)
+            return _needed(ctx, ((torch.empty_like(gy), None, None) + tuple(torch.zeros(shape, dtype=dt, device=gy.device) for dt, shape in ctx.ctl)))
         (x32,) = ctx.saved_tensors
         need_gx, need_gc = ctx.needs_input_grad[0], any(ctx.needs_input_grad[3:])
         with torch.cuda.device(x32.device):
@@ -295,7 +307,7 @@ class ParametricEQNormFunction(torch.autograd.Function):
     def backward(ctx, gy):
         xd, pd, pshape = ctx.meta
         if ctx.empty:
-            return torch.empty_like(gy), torch.zeros(pshape, dtype=pd, device=gy.device), None, None, None, None, None
+            return _needed(ctx, (torch.empty_like(gy), torch.zeros(pshape, dtype=pd, device=gy.device), None, None, None, None, None))
         (x32,) = ctx.saved_tensors
         need_gx, need_gp = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         with torch.cuda.device(x32.device):
@@ -328,7 +340,7 @@ class _ElementwiseFunction(torch.autograd.Function):
     def _grad(cls, ctx, gy):
         xd, cd, cshape = ctx.meta
         if ctx.empty:
-            return torch.empty_like(gy), torch.zeros(cshape, dtype=cd, device=gy.device)
+            return _needed(ctx, (torch.empty_like(gy), torch.zeros(cshape, dtype=cd, device=gy.device)))
         L = _lib.lib()
         x32, c32 = ctx.saved_tensors
         B, C, N = x32.shape
@@ -337,7 +349,7 @@ class _ElementwiseFunction(torch.autograd.Function):
             gctl = torch.empty_like(c32)
             partials = torch.empty(L.dasp_ew_partial_floats(B * C, N), dtype=torch.float32, device=x32.device)
             call(cls.BWD, ptr(x32), ptr(c32), ptr(_f32c(gy)), ptr(gx), ptr(gctl), ptr(partials), B, C, N, stream())
-        return gx.to(xd), gctl.reshape(cshape).to(cd)
+        return (gx.to(xd) if ctx.needs_input_grad[0] else None), (gctl.reshape(cshape).to(cd) if ctx.needs_input_grad[1] else None)
 
 
 class GainFunction(_ElementwiseFunction):
@@ -393,13 +405,13 @@ class DistortionSampleFunction(torch.autograd.Function):
     def backward(ctx, gy):
         xd, dd, dshape = ctx.meta
         if ctx.empty:
-            return torch.empty_like(gy), torch.zeros(dshape, dtype=dd, device=gy.device)
+            return _needed(ctx, (torch.empty_like(gy), torch.zeros(dshape, dtype=dd, device=gy.device)))
         x32, d32 = ctx.saved_tensors
         with torch.cuda.device(x32.device):
             gx = torch.empty_like(x32)
             gd = torch.empty_like(x32)
             call("dasp_distortion_sample_backward", ptr(x32), ptr(d32), ptr(_f32c(gy)), ptr(gx), ptr(gd), x32.numel(), stream())
-        return gx.to(xd), gd.reshape(dshape).to(dd)
+        return (gx.to(xd) if ctx.needs_input_grad[0] else None), (gd.reshape(dshape).to(dd) if ctx.needs_input_grad[1] else None)
 
 
 def _require_rows(x, t, ncols, name):
@@ -493,7 +505,7 @@ class DynamicsFunction(torch.autograd.Function):
     def backward(ctx, gy):
         xd, cm = ctx.meta
         if ctx.empty:
-            return (torch.empty_like(gy), None, None, None, None) + tuple(torch.zeros(shape, dtype=dt, device=gy.device) for dt, shape in cm)
+            return _needed(ctx, ((torch.empty_like(gy), None, None, None, None) + tuple(torch.zeros(shape, dtype=dt, device=gy.device) for dt, shape in cm)))
         x32 = ctx.saved_tensors[0]
         with torch.cuda.device(x32.device):
             gx, gctl = _dyn_backward(ctx.saved_tensors, ctx.cfg, gy)
@@ -539,7 +551,7 @@ class DynamicsMatrixFunction(torch.autograd.Function):
     def backward(ctx, gy):
         xd, cd, cshape = ctx.meta
         if ctx.empty:
-            return torch.empty_like(gy), None, None, None, None, torch.zeros(cshape, dtype=cd, device=gy.device)
+            return _needed(ctx, (torch.empty_like(gy), None, None, None, None, torch.zeros(cshape, dtype=cd, device=gy.device)))
         x32 = ctx.saved_tensors[0]
         with torch.cuda.device(x32.device):
             gx, gctl = _dyn_backward(ctx.saved_tensors, ctx.cfg, gy)
@@ -558,7 +570,7 @@ class DynamicsCtlFunction(torch.autograd.Function):
         _lib.require_device(x, "x")
         _lib.require_same_device(x, ctl=ctl)
         _require_rows(x, ctl, 5, "ctl")
-        ctx.xdtype = x.dtype
+        ctx.xdtype, ctx.cdtype = x.dtype, ctl.dtype
         ctx.empty = x.numel() == 0
         if ctx.empty:
             return torch.empty_like(x)
@@ -574,10 +586,11 @@ class DynamicsCtlFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         if ctx.empty:
-            return torch.empty_like(gy), None, None, None, None, torch.zeros(gy.shape[0], 5, dtype=torch.float32, device=gy.device)
+            return _needed(ctx, (torch.empty_like(gy), None, None, None, None, torch.zeros(gy.shape[0], 5, dtype=ctx.cdtype, device=gy.device)))
         with torch.cuda.device(gy.device):
             gx, gctl = _dyn_backward(ctx.saved_tensors, ctx.cfg, gy)
-        return gx.to(ctx.xdtype) if ctx.needs_input_grad[0] else None, None, None, None, None, gctl
+        return (gx.to(ctx.xdtype) if ctx.needs_input_grad[0] else None, None, None, None, None,
+                gctl.to(ctx.cdtype) if ctx.needs_input_grad[5] else None)
 
 
 class ChainControlsFunction(torch.autograd.Function):
@@ -615,10 +628,12 @@ class ChainControlsFunction(torch.autograd.Function):
             gr = torch.empty(B, 25, dtype=torch.float32, device=dev)
             gg = torch.empty(B, 1, dtype=torch.float32, device=dev)
             if B:
-                call("dasp_chain_controls_backward", ptr(z(gctl, B, 5)), ptr(z(ggain, B, 12)), ptr(z(gdecay, B, 12)), ptr(z(gmix, B)), ctx.span,
-                     ptr(gc), ptr(gr), ptr(gg), B, stream())
-        cd, rd, gd = ctx.dtypes
-        return gc.to(cd), gr.to(rd), gg.to(gd), None, None, None
+                # the four copies stay referenced until the call is queued (see StereoMixFunction.backward): as temporaries, the copy of a
+                # non-contiguous gctl was freed before ggain was copied - into the same block - and the kernel read ggain's values for both
+                g0, g1, g2, g3 = z(gctl, B, 5), z(ggain, B, 12), z(gdecay, B, 12), z(gmix, B)
+                call("dasp_chain_controls_backward", ptr(g0), ptr(g1), ptr(g2), ptr(g3), ctx.span, ptr(gc), ptr(gr), ptr(gg), B, stream())
+        need = ctx.needs_input_grad
+        return tuple(g.to(d) if n else None for g, d, n in zip((gc, gr, gg), ctx.dtypes, need)) + (None, None, None)
 
 
 def chain_eq_compressor_forward(x, eq_pn, types, lo, span, sample_rate, ctl, mode=0, eps=1e-8, range_flag=None):
@@ -703,7 +718,7 @@ class _StereoFunction(torch.autograd.Function):
     def _grad(cls, ctx, gy):
         xd, cd, cshape, B, T, N = ctx.meta
         if ctx.empty:
-            return torch.empty(ctx.xshape, dtype=xd, device=gy.device), torch.zeros(cshape, dtype=cd, device=gy.device)
+            return _needed(ctx, (torch.empty(ctx.xshape, dtype=xd, device=gy.device), torch.zeros(cshape, dtype=cd, device=gy.device)))
         L = _lib.lib()
         x32, c32 = ctx.saved_tensors
         with torch.cuda.device(x32.device):
@@ -712,7 +727,7 @@ class _StereoFunction(torch.autograd.Function):
             partials = torch.empty(L.dasp_stereo_partial_floats(cls.OP, B, T, N), dtype=torch.float32, device=x32.device)
             dims = (B, N) if cls.OP == 0 else (B, T, N)
             call(cls.BWD, ptr(x32), ptr(c32), ptr(_f32c(gy)), ptr(gx), ptr(gctl), ptr(partials), *dims, stream())
-        return gx.to(xd), gctl.reshape(cshape).to(cd)
+        return (gx.to(xd) if ctx.needs_input_grad[0] else None), (gctl.reshape(cshape).to(cd) if ctx.needs_input_grad[1] else None)
 
 
 class WidenerFunction(_StereoFunction):
@@ -790,7 +805,7 @@ class StereoMixFunction(torch.autograd.Function):
         with_send = len(cmeta) == 3
         if ctx.empty:
             gc = [torch.zeros(s, dtype=d, device=dev) for d, s in cmeta]
-            return torch.empty((B, T, N), dtype=xd, device=dev), gc[0], gc[1], (gc[2] if with_send else None)
+            return _needed(ctx, (torch.empty((B, T, N), dtype=xd, device=dev), gc[0], gc[1], (gc[2] if with_send else None)))
         x32, *c32 = ctx.saved_tensors
         with torch.cuda.device(dev):
             gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None           # not computed, not written when x needs no gradient
@@ -802,8 +817,8 @@ class StereoMixFunction(torch.autograd.Function):
             call("dasp_stereo_mix_backward", ptr(x32), ptr(c32[0]), ptr(c32[1]), ptr(c32[2] if with_send else None), ptr(gm32),
                  ptr(gs32), ptr(gx), ptr(gc[0]), ptr(gc[1]), ptr(gc[2] if with_send else None), ptr(partials),
                  B, T, N, stream())
-        gc = [g.reshape(s).to(d) for g, (d, s) in zip(gc, cmeta)]
-        return (None if gx is None else gx.to(xd)), gc[0], gc[1], (gc[2] if with_send else None)
+        gc = [g.reshape(s).to(d) if need else None for g, (d, s), need in zip(gc, cmeta, ctx.needs_input_grad[1:])] + [None]
+        return (None if gx is None else gx.to(xd)), gc[0], gc[1], gc[2]
 
 
 class OversampledDistortionFunction(torch.autograd.Function):
@@ -833,7 +848,7 @@ class OversampledDistortionFunction(torch.autograd.Function):
     def backward(ctx, gy):
         xd, dd, dshape = ctx.meta
         if ctx.empty:
-            return torch.empty_like(gy), torch.zeros(dshape, dtype=dd, device=gy.device), None, None, None
+            return _needed(ctx, (torch.empty_like(gy), torch.zeros(dshape, dtype=dd, device=gy.device), None, None, None))
         taps, L, H = ctx.cfg
         x32, d32 = ctx.saved_tensors
         B, C, N = x32.shape
@@ -843,7 +858,7 @@ class OversampledDistortionFunction(torch.autograd.Function):
             partials = torch.empty(_lib.lib().dasp_osdist_partial_floats(B * C, N, L), dtype=torch.float32, device=x32.device)
             g32 = _f32c(gy)
             call("dasp_osdist_backward", ptr(x32), ptr(d32), taps, ptr(g32), ptr(gx), ptr(gd), ptr(partials), B, C, N, L, H, stream())
-        return gx.to(xd), gd.reshape(dshape).to(dd), None, None, None
+        return (gx.to(xd) if ctx.needs_input_grad[0] else None), (gd.reshape(dshape).to(dd) if ctx.needs_input_grad[1] else None), None, None, None
 
 
 class ModulatedDelayFunction(torch.autograd.Function):
@@ -876,7 +891,7 @@ class ModulatedDelayFunction(torch.autograd.Function):
     def backward(ctx, gy):
         xd, cmeta = ctx.meta
         if ctx.empty:
-            return (torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 4
+            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 4))
         sample_rate, max_delay_ms, stereo_spread, H = ctx.cfg
         x32, ctl, m32 = ctx.saved_tensors
         B, C, N = x32.shape
@@ -889,8 +904,9 @@ class ModulatedDelayFunction(torch.autograd.Function):
             g32 = _f32c(gy)
             call("dasp_moddelay_backward", ptr(x32), ptr(ctl), ptr(m32), ptr(g32), ptr(gx), ptr(gctl), ptr(gmix), ptr(partials), B, C, N, V, H,
                  sample_rate, max_delay_ms, stereo_spread, stream())
-        gc = [gctl[..., q].reshape(s).to(d) for q, (d, s) in enumerate(cmeta[:4])] + [gmix.reshape(cmeta[4][1]).to(cmeta[4][0])]
-        return (None if gx is None else gx.to(xd),) + tuple(gc) + (None,) * 4
+        cols = [gctl[..., q] for q in range(4)] + [gmix]
+        gc = tuple(g.reshape(s).to(d) if need else None for g, (d, s), need in zip(cols, cmeta, ctx.needs_input_grad[1:6]))
+        return (None if gx is None else gx.to(xd),) + gc + (None,) * 4
 
 
 _FSPEC_CACHE = {}
@@ -1004,7 +1020,7 @@ class ReverbFunction(torch.autograd.Function):
         xd, gd, gs, dd, ds, md, ms = ctx.meta
         if ctx.empty:
             z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=gy.device)
-            return torch.empty(gy.shape[0], ctx.xC, gy.shape[2], dtype=xd, device=gy.device), None, None, z(gs, gd), z(ds, dd), z(ms, md), None, None, None, None
+            return _needed(ctx, (torch.empty(gy.shape[0], ctx.xC, gy.shape[2], dtype=xd, device=gy.device), None, None, z(gs, gd), z(ds, dd), z(ms, md), None, None, None, None))
         ir, n32, Fspec, g32, d32, m32, A, H, soff = ctx.saved_tensors
         B, C, N, L_ir, taps, nb, sizes, useed, has_soff, dbound = ctx.cfg
         soff = soff if has_soff else None
@@ -1022,6 +1038,8 @@ class ReverbFunction(torch.autograd.Function):
             call("dasp_reverb_backward", ptr(ir), ptr(_f32c(gy)), ptr(n32 if useed is None else None), useed if useed is not None else 0, ptr(soff), ptr(Fspec), ptr(g32),
                  ptr(d32), ptr(m32), ptr(A), ptr(H), ptr(gx), ptr(ggain), ptr(gdecay), ptr(gmix), ptr(Ag), ptr(W), ptr(P), ptr(gir), ptr(part),
                  ptr(mix_part), B, C, N, L_ir, taps, nb, dbound, stream())
-        if C == 1:
+        need = ctx.needs_input_grad
+        if C == 1 and need[0]:
             gx = gx.sum(1, keepdim=True)           # the adjoint of the mono -> stereo duplication
-        return gx.to(xd), None, None, ggain.reshape(gs).to(gd), gdecay.reshape(ds).to(dd), gmix.reshape(ms).to(md), None, None, None, None
+        return (gx.to(xd) if need[0] else None, None, None, ggain.reshape(gs).to(gd) if need[3] else None, gdecay.reshape(ds).to(dd) if need[4] else None,
+                gmix.reshape(ms).to(md) if need[5] else None, None, None, None, None)

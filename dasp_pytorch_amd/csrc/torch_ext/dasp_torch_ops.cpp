@@ -526,7 +526,9 @@ struct ChainControlsFn : public torch::autograd::Function<ChainControlsFn> {
         static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("dasp::_chain_controls_backward", "")
                              .typed<std::tuple<Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&, at::ArrayRef<double>)>();
         auto [gc, gr, gg] = op.call(z(g[0], {B, 5}), z(g[1], {B, 12}), z(g[2], {B, 12}), z(g[3], {B}), span);
-        return {gc.to((at::ScalarType)dt[0]), gr.to((at::ScalarType)dt[1]), gg.to((at::ScalarType)dt[2]), Tensor(), Tensor(), Tensor()};
+        // (needs_input_grad counts the tensor arguments: comp_params, reverb_params, gain_params)
+        return {ctx->needs_input_grad(0) ? gc.to((at::ScalarType)dt[0]) : Tensor(), ctx->needs_input_grad(1) ? gr.to((at::ScalarType)dt[1]) : Tensor(),
+                ctx->needs_input_grad(2) ? gg.to((at::ScalarType)dt[2]) : Tensor(), Tensor(), Tensor(), Tensor()};
     }
 };
 std::tuple<Tensor, Tensor, Tensor, Tensor> chain_controls_autograd(const Tensor& comp_pn, const Tensor& reverb_pn, const Tensor& gain_pn, at::ArrayRef<double> lo,

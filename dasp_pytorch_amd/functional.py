@@ -455,7 +455,8 @@ def _rows32(x):
 
 class _LoudnessFunction(torch.autograd.Function):
     """x (bs, chs, N) -> L (bs) LUFS. Forward: filter pass (+ a state pre-pass for few rows) and the gate launch; backward: one filter
-    pass backwards in time over the K-weighted signal the forward call kept."""
+    pass backwards in time over the K-weighted signal the forward call kept (its own buffer: x may be overwritten after the forward,
+    and the backward repeated - scratch is allocated per call)."""
 
     @staticmethod
     def forward(ctx, x, fs):

@@ -11,7 +11,12 @@ mel tables, and in the backward which argument to differentiate.
 
 The time-domain half of auraloss (auraloss.time: ESRLoss, DCLoss, LogCoshLoss, SNRLoss, SISDRLoss, SDSDRLoss) and the MSE term of the
 reference's examples/virtual_analog.py:299,324-326 are one weighted sum, time_domain_loss, from one moment pass over both signals
-(csrc/tdloss.hip); FIRFilter is auraloss.perceptual.FIRFilter, the pre-emphasis / A-weighting filter those losses are used behind."""
+(csrc/tdloss.hip); FIRFilter is auraloss.perceptual.FIRFilter, the pre-emphasis / A-weighting filter those losses are used behind.
+
+Autograd (tests/test_gpu_autograd_contract.py): a contiguous float32 input or target is saved as it is, so overwriting it between the
+forward and a late backward raises autograd's in-place error (any other dtype or layout, and everything behind the A-weighting, is the
+forward's own copy); the saved signals, statistics and per-stream device constants are only read by a backward, which may run any number
+of times and in any order with other graphs'; a loss passed the same tensor twice returns the sum of both gradients."""
 import ctypes
 import functools
 import math

@@ -5,12 +5,18 @@ float64 arithmetic. The fp32 kernels have no double instantiation; these plain s
 recurrences (parametric_eq / sosfilt_via_fsm / lfilter_via_fsm, compressor / expander) and the elementwise effects (gain, distortion):
 right for validation and torch.autograd.gradcheck, not tuned for throughput. The FFT-based and stereo ops compute in fp32 only and
 refuse float64 input unless config.plan.fp64_as_fp32 asks for the old cast-compute-cast behaviour (`require_fp32_ok`).
+
+The autograd contract is that of _ctypes_ops.py (tests/test_gpu_autograd_contract.py): None for an input that needs no gradient, saved
+state that survives a backward, and a contiguous float64 tensor that a backward reads again (x of the elementwise ops and of the
+dynamics; sos, b, a) kept as it is through save_for_backward - overwriting it between forward and backward raises autograd's in-place
+error; the filters keep their own state signal instead of x.
 """
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib, config
+from ._ctypes_ops import _needed
 from ._lib import call, ptr, stream
 
 
@@ -60,7 +66,7 @@ class SosFilt64Function(torch.autograd.Function):
     def backward(ctx, gy):
         sdt, sshape, xshape = ctx.meta
         if ctx.empty:
-            return torch.zeros(sshape, dtype=sdt, device=gy.device), torch.empty(xshape, dtype=torch.float64, device=gy.device)
+            return _needed(ctx, (torch.zeros(sshape, dtype=sdt, device=gy.device), torch.empty(xshape, dtype=torch.float64, device=gy.device)))
         s64, c5, wsave = ctx.saved_tensors
         Bs, S, _ = sshape
         B, C, N = xshape
@@ -116,7 +122,7 @@ class LFilterFunction(torch.autograd.Function):
     def backward(ctx, gy):
         xdt, xshape, bdt, adt, bshape = ctx.meta
         if ctx.empty:
-            return torch.empty(xshape, dtype=xdt, device=gy.device), torch.zeros(bshape, dtype=bdt, device=gy.device), torch.zeros(bshape, dtype=adt, device=gy.device)
+            return _needed(ctx, (torch.empty(xshape, dtype=xdt, device=gy.device), torch.zeros(bshape, dtype=bdt, device=gy.device), torch.zeros(bshape, dtype=adt, device=gy.device)))
         b64, a64, wsave = ctx.saved_tensors
         B, C, N = xshape
         Bs, K = bshape
@@ -132,7 +138,7 @@ class LFilterFunction(torch.autograd.Function):
             call("dasp_lfilter_backward", ptr(g), ptr(b64), ptr(a64), Bs, ptr(wsave), ptr(gx), ptr(gb), ptr(ga), ptr(work), nwork, B * C, N, K, int(f64), ctx.chunk, stream())
             if Bs == 1 and B * C > 1:
                 gb, ga = gb.sum(0, keepdim=True), ga.sum(0, keepdim=True)
-        return (gx.to(xdt) if gx is not None else None), gb.to(bdt), ga.to(adt)
+        return (gx.to(xdt) if gx is not None else None), (gb.to(bdt) if ctx.needs_input_grad[1] else None), (ga.to(adt) if ctx.needs_input_grad[2] else None)
 
 
 class ParametricEQ64Function(torch.autograd.Function):
@@ -173,8 +179,8 @@ class ParametricEQ64Function(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         if ctx.empty:
-            return (torch.empty(ctx.xshape, dtype=torch.float64, device=gy.device), None, None) + tuple(
-                torch.zeros(shape, dtype=dt, device=gy.device) for dt, shape in ctx.ctl)
+            return _needed(ctx, ((torch.empty(ctx.xshape, dtype=torch.float64, device=gy.device), None, None) + tuple(
+                torch.zeros(shape, dtype=dt, device=gy.device) for dt, shape in ctx.ctl)))
         c5, jac, wsave = ctx.saved_tensors
         Bp, S, _ = c5.shape
         B, C, N = ctx.xshape
@@ -225,8 +231,8 @@ class Dynamics64Function(torch.autograd.Function):
     def backward(ctx, gy):
         dev = gy.device
         if ctx.empty:
-            return (torch.empty(ctx.xshape, dtype=torch.float64, device=dev), None, None, None, None) + tuple(
-                torch.zeros(shape, dtype=dt, device=dev) for dt, shape in ctx.meta)
+            return _needed(ctx, ((torch.empty(ctx.xshape, dtype=torch.float64, device=dev), None, None, None, None) + tuple(
+                torch.zeros(shape, dtype=dt, device=dev) for dt, shape in ctx.meta)))
         x64, ctl, gsave = ctx.saved_tensors
         mode, sr, eps, look = ctx.cfg
         B, C, N = ctx.xshape
@@ -272,11 +278,11 @@ class Elementwise64Function(torch.autograd.Function):
         cdt, cshape, xshape, op = ctx.meta
         dev = gy.device
         if ctx.empty:
-            return torch.empty(xshape, dtype=torch.float64, device=dev), torch.zeros(cshape, dtype=cdt, device=dev), None
+            return _needed(ctx, (torch.empty(xshape, dtype=torch.float64, device=dev), torch.zeros(cshape, dtype=cdt, device=dev), None))
         x64, c64 = ctx.saved_tensors
         B, C, N = xshape
         with torch.cuda.device(dev):
             gx = torch.empty_like(x64)
             gctl = torch.empty_like(c64)
             call("dasp_ew64_backward", op, ptr(x64), ptr(c64), ptr(_d(gy, dev)), ptr(gx), ptr(gctl), B, C, N, stream())
-        return gx, gctl.reshape(cshape).to(cdt), None
+        return (gx if ctx.needs_input_grad[0] else None), (gctl.reshape(cshape).to(cdt) if ctx.needs_input_grad[1] else None), None
