@@ -129,23 +129,76 @@ def _expand(g):
     return row
 
 
-def build_table(path=TABLE_PATH, force=False):
-    """(N_BABY + N_GIANT, ROW) uint16, cached at `path` (a few seconds of integer arithmetic the first time)."""
-    if not force and os.path.exists(path):
-        try:
-            t = np.load(path)
-            if t.shape == (N_BABY + N_GIANT, ROW) and t.dtype == np.uint16:
-                return t
-        except Exception:
-            pass
-    t = np.stack([_expand(g) for g in jump_polynomials()])
+# ---- the cached file: the rows, then one row that says what they are -------------------------------------------------------------------
+# uint16 (N_BABY + N_GIANT + 1, ROW). The last row is the key: magic, format version, the constants the rows depend on (a file built
+# with another JUMP is another table of the same shape) and the CRC-32 of the rows' bytes. A file is used only if its key is this
+# module's, the checksum holds, and the four corner rows - the first and last baby step, the first and last giant step - equal what
+# _square_power() computes for them here, by a route that shares no multiplication with jump_polynomials() (squarings and shifts only:
+# 0.14 s against the 5 s of the build). The checksum covers every row, so one flipped bit anywhere is caught by construction; the
+# corner rows catch a file whose key and checksum are right for rows that are not this module's. Anything else is rebuilt and rewritten.
+TABLE_MAGIC, TABLE_VERSION = 0x4D54, 2          # (version 1: the rows alone, accepted on shape and dtype)
+
+
+def _key_row(rows):
+    import zlib
+    crc = zlib.crc32(np.ascontiguousarray(rows, dtype="<u2").tobytes())
+    key = np.zeros(ROW, dtype=np.uint16)
+    key[:11] = [TABLE_MAGIC, TABLE_VERSION, JUMP & 0xFFFF, JUMP >> 16, N_BABY, N_GIANT, GROUP, ROW & 0xFFFF, ROW >> 16, crc & 0xFFFF, crc >> 16]
+    return key
+
+
+def _square_power(F, e):
+    """t^e mod p from the top bit of e down: square (in GF(2)[t]: a zero between every two coefficients), times t where the bit is set."""
+    res = 1
+    for bit in bin(e)[2:]:
+        res = F.reduce(int("0".join(bin(res)[2:]), 2))
+        if bit == "1":
+            res = F.reduce(res << 1)
+    return res
+
+
+def _corner_rows():
+    """{row index: the row} of the first and last baby step and the first and last giant step."""
+    F = _Field()
+    return {i: _expand(_square_power(F, e)) for i, e in ((0, JUMP), (N_BABY - 1, N_BABY * JUMP), (N_BABY, (N_BABY + 1) * JUMP),
+                                                         (N_BABY + N_GIANT - 1, N_GIANT * (N_BABY + 1) * JUMP))}
+
+
+def _load_table(path):
+    """The rows of a cached file that is this module's table, else None."""
     try:
-        tmp = f"{path}.{os.getpid()}.tmp"
+        t = np.load(path)
+    except Exception:
+        return None                             # truncated, not an array file, unreadable
+    if not isinstance(t, np.ndarray) or t.shape != (N_BABY + N_GIANT + 1, ROW) or t.dtype != np.uint16:
+        return None                             # (the old format has one row less)
+    rows = t[:-1]
+    if not np.array_equal(t[-1], _key_row(rows)):
+        return None
+    if any(not np.array_equal(rows[i], row) for i, row in _corner_rows().items()):
+        return None
+    return np.ascontiguousarray(rows)
+
+
+def build_table(path=TABLE_PATH, force=False):
+    """(N_BABY + N_GIANT, ROW) uint16, cached at `path` (a few seconds of integer arithmetic the first time). A cached file that is
+    stale, damaged or of an older format is rebuilt and rewritten (see above); where the file cannot be written the table is kept in
+    memory only."""
+    if not force and os.path.exists(path):
+        t = _load_table(path)
+        if t is not None:
+            return t
+    t = np.stack([_expand(g) for g in jump_polynomials()])
+    tmp = f"{path}.{os.getpid()}.tmp"
+    try:
         with open(tmp, "wb") as f:
-            np.save(f, t)
+            np.save(f, np.concatenate([t, _key_row(t)[None]]))
         os.replace(tmp, path)
-    except OSError:
-        pass                                    # read-only tree: keep it in memory
+    except OSError:                             # read-only tree: keep it in memory
+        try:
+            os.remove(tmp)
+        except OSError:
+            pass
     return t
 
 
@@ -264,7 +317,9 @@ def _randn_from_state(words, left, out, max_piece=None):
 class _PendingState:
     """The generator state a device draw leaves behind, on its way to the host: the words were copied to pinned memory right behind the
     generating kernels (an event marks the copy), `finish()` waits for that event only and installs the state. Between the draw and
-    finish() the CPU generator still holds the state from BEFORE the draw - the caller finishes before it hands control back."""
+    finish() the CPU generator still holds the state from BEFORE the draw - the caller finishes before it hands control back.
+    finish() looks whether the generator still holds that state: if somebody drew from it in between, it warns once (RuntimeWarning)
+    and installs its own state all the same."""
 
     def __init__(self, state, words, left_after, state_dev):
         import torch
@@ -282,6 +337,13 @@ class _PendingState:
         if self.event is not None:
             self.event.synchronize()
             self.words = self.pinned.numpy().view(np.uint32)
+        if not torch.equal(torch.get_rng_state(), self.state):
+            import warnings
+            warnings.warn("dasp_pytorch_amd: torch's global CPU generator was used between a device draw of its stream (the reverb's default "
+                          "noise) and the moment that draw installed the generator's new state. The state of the device draw is installed "
+                          "now, so the values drawn in between will repeat: they are the first values of the stream the reverb's noise was "
+                          "taken from. Draw from a torch.Generator of your own in hooks and other threads, or pass noise= / noise_seed=.",
+                          RuntimeWarning, stacklevel=2)
         torch.set_rng_state(format_state(self.state, self.words, self.left_after))
         self.state = None
 
@@ -301,7 +363,11 @@ def randn_cpu_stream(*size, device, defer=False):
     queues more device work first (the reverb's kernels) so that the host does not sit out the generation; it must finish before
     anything else can draw from the CPU generator. (torch.randn holds the generator's mutex for the whole fill; between this function's
     get_rng_state and set_rng_state another host THREAD drawing from the global generator would be overwritten - as racy as two threads
-    sharing one seeded stream are in the reference, but with a wider window.)"""
+    sharing one seeded stream are in the reference, but with a wider window.)
+    Such a draw is noticed, not prevented: finish() compares the generator's state with the one this function read, and where they
+    differ it issues one RuntimeWarning that says what follows - the state of the device draw is installed as always, so the values the
+    interloper drew will be handed out again - and goes on. A call that nobody interrupts raises no warning.
+    The once-per-device self-check draws from a private torch.Generator: no global generator, host or device, is touched by it."""
     import torch
     dev = torch.device(device)
     n = 1
@@ -343,18 +409,20 @@ def randn_cpu_stream(*size, device, defer=False):
 
 def _run_self_check(dev):
     """Once per device and process: 16 K + 3 values (several chunks' worth would cost a second; this covers regeneration, groups across
-    block borders and the tail rule) from a scratch copy of the generator against torch.randn itself, and the state afterwards."""
+    block borders and the tail rule) from a private generator against torch.randn itself, and the state afterwards. A private
+    torch.Generator has the global one's state layout and stream (tests/test_call_state_cpu.py); torch.manual_seed would reseed every
+    device generator of the process as well."""
     import torch
-    keep = torch.get_rng_state()
     try:
         ok = True
         for seed, burn, n in ((20240601, 0, 16387), (7, 100, 4096)):
-            torch.manual_seed(seed)
+            g = torch.Generator()
+            g.manual_seed(seed)
             if burn:
-                torch.rand(burn)
-            s0 = torch.get_rng_state()
-            ref = torch.randn(n)
-            s1 = torch.get_rng_state()
+                torch.rand(burn, generator=g)
+            s0 = g.get_state()
+            ref = torch.randn(n, generator=g)
+            s1 = g.get_state()
             words, left = parse_state(s0)
             with torch.cuda.device(dev):
                 out = torch.empty(n, dtype=torch.float32, device=dev)
@@ -364,5 +432,3 @@ def _run_self_check(dev):
         return ok
     except Exception:
         return False
-    finally:
-        torch.set_rng_state(keep)

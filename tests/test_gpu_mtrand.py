@@ -130,6 +130,51 @@ def test_successive_draws_continue_the_stream(mt):
     assert float((a.cpu() - a_ref).abs().max()) <= 4e-6 and torch.equal(b, b_ref) and float((c.cpu() - c_ref).abs().max()) <= 4e-6
 
 
+def test_a_draw_nobody_interrupts_raises_no_warning(mt):
+    """finish() compares the generator's state with the one the draw read: equal on the normal path, deferred or not."""
+    import warnings
+    torch.manual_seed(8)
+    ref = torch.randn(2, 12, 300)
+    s_ref = torch.get_rng_state()
+    for defer in (False, True):
+        torch.manual_seed(8)
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            got = mt.randn_cpu_stream(2, 12, 300, device=DEV, defer=defer)
+            if defer:
+                got, pending = got
+                pending.finish()
+        assert float((got.cpu() - ref).abs().max()) <= 4e-6 and torch.equal(torch.get_rng_state(), s_ref)
+
+
+def test_a_host_draw_before_finish_is_noticed(mt):
+    """defer=True and somebody draws from the CPU generator before finish(): one RuntimeWarning that names the consequence; the device
+    draw's state is installed all the same, so the interloper's values are handed out again."""
+    torch.manual_seed(8)
+    torch.randn(2, 12, 300)
+    s_ref = torch.get_rng_state()
+    torch.manual_seed(8)
+    got, pending = mt.randn_cpu_stream(2, 12, 300, device=DEV, defer=True)
+    stolen = torch.rand(4)
+    with pytest.warns(RuntimeWarning, match="will repeat"):
+        pending.finish()
+    assert torch.equal(torch.get_rng_state(), s_ref)
+    torch.manual_seed(8)
+    assert torch.equal(torch.rand(4), stolen)
+
+
+def test_the_first_draw_on_a_device_leaves_the_device_generators_alone(mt):
+    """The self-check again, in this process (tests/test_gpu_call_state.py has the first call of a fresh process): device generators and
+    the CPU generator as a run without it leaves them."""
+    torch.manual_seed(4321)
+    torch.rand(2, device=DEV)
+    before = [s.clone() for s in torch.cuda.get_rng_state_all()]
+    cpu = torch.get_rng_state()
+    assert mt._run_self_check(torch.device(DEV)) is True
+    assert all(torch.equal(a, b) for a, b in zip(before, torch.cuda.get_rng_state_all())) and torch.equal(cpu, torch.get_rng_state())
+    assert torch.cuda.initial_seed() == 4321
+
+
 def test_fallbacks_draw_on_the_host(mt):
     torch.manual_seed(3)
     ref = torch.randn(8)                         # fewer than 16 values: torch takes another code path (double normal_distribution)
