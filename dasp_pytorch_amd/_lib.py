@@ -94,6 +94,12 @@ SIGNATURES = {
     "dasp_moddelay_partial_floats": (_l, [_l, _l, _i, _i]),
     "dasp_moddelay_forward": (_i, [_p] * 4 + [_i, _i, _l, _i, _i, _d, _d, _d, _p]),
     "dasp_moddelay_backward": (_i, [_p] * 8 + [_i, _i, _l, _i, _i, _d, _d, _d, _p]),
+    "dasp_fbdelay_max_delay_samples": (_i, []),
+    "dasp_fbdelay_block": (_i, [_i, _l]),
+    "dasp_fbdelay_partial_floats": (_l, [_l, _l, _i]),
+    "dasp_fbdelay_prepare": (_i, []),
+    "dasp_fbdelay_forward": (_i, [_p] * 4 + [_i, _i, _l, _i, _d, _d, _p]),
+    "dasp_fbdelay_backward": (_i, [_p] * 7 + [_i, _i, _l, _i, _d, _d, _p]),
     "dasp_mrstft_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i]),
     "dasp_mrstft_table": (_i, [_p, _p]),
     "dasp_mrstft_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
@@ -177,6 +183,7 @@ def lib():
         _lib = L
         if torch.cuda.is_available():
             L.dasp_device_error()           # allocates the current device's error words now - not under some later stream capture
+            L.dasp_fbdelay_prepare()        # feedback_delay's LDS ring is above the default limit: raised now, not inside a call
     return _lib
 
 

@@ -10,7 +10,7 @@ from . import signal as _signal
 from . import _mt19937
 from . import ops as _ops
 from . import _lib
-from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
+from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, FeedbackDelayFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
                   StereoMixFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
@@ -102,7 +102,7 @@ def modulated_delay(x: torch.Tensor, sample_rate: float, delay_ms: torch.Tensor,
         tap_v[n] = Catmull-Rom interpolation of x[i-1], x[i], x[i+1], x[i+2] at f;   y[n] = (1 - mix) x[n] + mix (1/V) sum_v tap_v[n]
     A flanger is one voice of 1-5 ms with mix = 0.5; a chorus a few voices of 10-30 ms at different phases; a vibrato mix = 1. The read
     position is float64 in the kernel, the interpolation float32 (csrc/moddelay.hip). The op works on whole tensors, not on a stream:
-    where d < 1 sample the four-point footprint reaches x[n+1]. There is no feedback path.
+    where d < 1 sample the four-point footprint reaches x[n+1]. There is no feedback path: feedback_delay is the line that has one.
     Differentiable in x and in all five controls; the delay gradients take no contribution from samples where d was clamped - size
     max_delay_ms (a plain float, like stereo_spread; at most 8192 samples) so that delay_ms + depth_ms stays inside it.
     float32 only. A wrong control count raises RuntimeError naming the control; more than 8 voices or a max_delay_ms beyond 8192
@@ -123,6 +123,40 @@ def modulated_delay(x: torch.Tensor, sample_rate: float, delay_ms: torch.Tensor,
     require_fp32_ok(x, "modulated_delay")
     H = max(1, math.ceil(float(sample_rate) / 1000.0 * max_delay_ms))
     return ModulatedDelayFunction.apply(x, delay_ms, depth_ms, rate_hz, phase, mix, float(sample_rate), max_delay_ms, stereo_spread, H)
+
+
+def feedback_delay(x: torch.Tensor, sample_rate: float, delay_ms: torch.Tensor, feedback: torch.Tensor, damping_hz: torch.Tensor,
+                   mix: torch.Tensor, max_delay_ms: float = 500.0):
+    """Echo / slap-back / comb resonator: a delay line that feeds its own output back through a one-pole low-pass (the damping), mixed
+    with the dry signal. x (bs, chs, seq_len); delay_ms, feedback, damping_hz and mix hold bs values each. For item b, every channel and
+    sample n, with the line empty (zero) before sample 0:
+        D = clamp(sample_rate/1000 delay_ms, 2, sample_rate/1000 max_delay_ms);  i = floor(D), f = D - i
+        a = exp(-2 pi max(damping_hz, 0) / sample_rate)                          (damping_hz = inf: a = 0, no filter in the loop)
+        r[n] = Catmull-Rom interpolation of v[n-i+1], v[n-i], v[n-i-1], v[n-i-2] at f              (the line read D samples back)
+        w[n] = x[n] + feedback r[n];   v[n] = (1 - a) w[n] + a v[n-1];   y[n] = (1 - mix) x[n] + mix r[n]
+    An echo is 100-500 ms with feedback 0.3-0.7; a slap-back 60-120 ms with little feedback; a comb resonator a few ms with feedback
+    near +-1. The delay is at least two samples (the interpolation's footprint must lie in the past). feedback is not clamped: for
+    |feedback| >= 1 the output grows, which is the caller's business; below 1 the loop is stable. D and a are float64 in the kernel,
+    everything after them float32 (csrc/fbdelay.hip). The op works on whole tensors, not on a stream.
+    Differentiable in x and in all four controls. The delay_ms gradient is zero where D was clamped - size max_delay_ms (a plain float;
+    at most dasp_fbdelay_max_delay_samples() = 34816 samples, 789 ms at 44.1 kHz) so that delay_ms stays inside it; the damping_hz gradient
+    is zero where damping_hz < 0 and at inf. A NaN delay_ms makes its item NaN (an infinite one is clamped like any other).
+    One workgroup walks one (item, channel) row in steps shorter than the delay: the op cannot fill the chip at training batch sizes,
+    and delays of a few samples are slow.
+    Out of scope: an LFO on the fed-back delay (modulated_delay has one, without feedback), cross-channel (ping-pong) feedback, and
+    float64. A wrong control count raises RuntimeError naming the control; a bad sample_rate or max_delay_ms (sample_rate/1000
+    max_delay_ms below two samples included) ValueError; a max_delay_ms beyond the maximum DaspHipError (unsupported configuration)."""
+    bs, chs, seq_len = x.size()
+    for name, c in (("delay_ms", delay_ms), ("feedback", feedback), ("damping_hz", damping_hz), ("mix", mix)):
+        if c.numel() != bs:
+            raise RuntimeError(f"{name}: shape '[{bs}]' is invalid for input of size {c.numel()}")
+    sr, max_delay_ms = float(sample_rate), float(max_delay_ms)
+    if not (sr > 0.0 and sr != float("inf")) or not (max_delay_ms != float("inf") and sr / 1000.0 * max_delay_ms >= 2.0):
+        raise ValueError(f"feedback_delay: finite sample_rate > 0 and finite max_delay_ms of at least two samples, got {sample_rate}, {max_delay_ms}")
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "feedback_delay")
+    H = math.ceil(sr / 1000.0 * max_delay_ms)
+    return FeedbackDelayFunction.apply(x, delay_ms, feedback, damping_hz, mix, sr, max_delay_ms, H)
 
 
 def stereo_bus(x: torch.Tensor, sample_rate: int, send_db: torch.Tensor):

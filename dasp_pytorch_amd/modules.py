@@ -368,6 +368,21 @@ class ModulatedDelay(Processor):
         return F.modulated_delay(x, sample_rate, *ctl, kwargs["mix"], max_delay_ms=self.max_delay_ms, stereo_spread=self.stereo_spread)
 
 
+class FeedbackDelay(Processor):
+    """Echo / slap-back / comb (functional.feedback_delay). The parameters delay_ms, feedback, damping_hz and mix are the functional's own
+    argument names; its max_delay_ms is the upper end of the delay range, so no value inside the range is ever clamped."""
+
+    def __init__(self, sample_rate: int, min_delay_ms: float = 1.0, max_delay_ms: float = 500.0, min_feedback: float = 0.0,
+                 max_feedback: float = 0.95, min_damping_hz: float = 200.0, max_damping_hz: float = 20000.0, min_mix: float = 0.0,
+                 max_mix: float = 1.0):
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.max_delay_ms = float(max_delay_ms)
+        self.process_fn = functools.partial(F.feedback_delay, max_delay_ms=self.max_delay_ms)
+        self.param_ranges = {"delay_ms": (min_delay_ms, max_delay_ms), "feedback": (min_feedback, max_feedback),
+                             "damping_hz": (min_damping_hz, max_damping_hz), "mix": (min_mix, max_mix)}
+
+
 def _eq_ranges(sample_rate, g, q):
     top = (sample_rate // 2) - 1000
     cut = {"low_shelf": (20, 2000), "band0": (80, 2000), "band1": (2000, 8000), "band2": (8000, 12000), "band3": (12000, top),

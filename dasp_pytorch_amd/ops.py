@@ -16,7 +16,7 @@ import torch
 
 from . import _lib, config
 from ._ctypes_ops import (FILTER_TYPES, BiquadFunction, BusFunction, ChainControlsFunction, DistortionFunction, DistortionSampleFunction,   # noqa: F401
-                          DynamicsCtlFunction, DynamicsFunction, DynamicsMatrixFunction, GainFunction, ModulatedDelayFunction, OversampledDistortionFunction,
+                          DynamicsCtlFunction, DynamicsFunction, DynamicsMatrixFunction, FeedbackDelayFunction, GainFunction, ModulatedDelayFunction, OversampledDistortionFunction,
                           PannerFunction,
                           ParametricEQFunction,
                           ParametricEQNormFunction, ReverbFunction, SosFiltFunction, StereoMixFunction, WidenerFunction, _dyn_counters, _filter_spectrum, _seed_offset,

@@ -443,6 +443,38 @@ int dasp_moddelay_backward(const float* x, const float* ctl, const float* mix, c
                            float* partials, int B, int C, long N, int V, int H, double sample_rate, double max_delay_ms, double stereo_spread,
                            void* stream);
 
+/* feedback_delay: echo / slap-back / comb - one delay line read with Catmull-Rom interpolation and fed back into itself through a
+ * one-pole low-pass, mixed with the dry signal; a recurrence evaluated in place, one workgroup per (b, c) row (csrc/fbdelay.hip).
+ * x, y, v, gy, gx (B, C, N) fp32; ctl, gctl (B, 4) fp32: delay_ms, feedback, damping_hz, mix.  For item b, every channel, sample n, with
+ * v zero before sample 0:
+ *   D = clamp(sample_rate/1000 delay_ms, 2, sample_rate/1000 max_delay_ms),  i = floor(D),  f = D - i
+ *   a = exp(-2 pi max(damping_hz, 0) / sample_rate)                                   (damping_hz = +inf: a = 0, no filter)
+ *   r[n] = sum_{k = -1 .. 2} w_k(f) v[n - i - k]  (Catmull-Rom),   w[n] = x[n] + feedback r[n],   v[n] = (1 - a) w[n] + a v[n - 1]
+ *   y[n] = (1 - mix) x[n] + mix r[n]
+ * D, i and a are float64 in the kernels; f and a are rounded to float32 and everything after them is float32. feedback is not clamped.
+ * H: a whole number of samples with 2 <= sample_rate/1000 max_delay_ms <= H <= dasp_fbdelay_max_delay_samples(); it sets the ring of
+ * LDS that holds the line. A row is walked in sequential steps of dasp_fbdelay_block(H, i - 1) = min(i - 1, 2048) samples.
+ * Forward: v (NULL: not saved) is the line's input, which the backward pass reads.  Backward: gx (NULL: not written), gctl; r, w and
+ * the derivative taps are recomputed from v; partials is scratch of dasp_fbdelay_partial_floats(B * C, N, H) = 4 floats per row,
+ * summed over an item's channels in fp64 in a fixed order by a second launch. No atomics. y, v, gx and gctl are bit-identical run to
+ * run. The delay_ms gradient is zero where D was clamped, the damping_hz gradient zero where damping_hz < 0 and at +inf.
+ * dasp_fbdelay_prepare() raises the kernels' dynamic-LDS limit on the current device; the binding calls it once when it loads the
+ * library, and the first call on a device that was not prepared does it itself.
+ * A null pointer (v in forward and gx apart), a non-positive size, H < 2, sample_rate/1000 max_delay_ms below 2 or above H, a sample rate
+ * that is not positive and finite, a lag outside [1, H - 1]: DASP_ERR_ARG (-1 from the queries); H above its maximum or B * C >= 2^31:
+ * DASP_ERR_UNSUPPORTED (-2 from the queries). All of it is checked before any launch.
+ * Non-finite input: all four products of a tap are always formed - a NaN or inf under a zero weight gives NaN - and a NaN or inf
+ * sample stays in the line from then on. A NaN delay_ms reads at i = 2 (nothing out of range) with f = NaN: the item's y, gx and
+ * control gradients are NaN; an infinite one is clamped. Other items keep every bit. */
+int dasp_fbdelay_max_delay_samples(void);
+int dasp_fbdelay_block(int H, long lag);
+long dasp_fbdelay_partial_floats(long rows, long N, int H);
+int dasp_fbdelay_prepare(void);
+int dasp_fbdelay_forward(const float* x, const float* ctl, float* y, float* v, int B, int C, long N, int H, double sample_rate,
+                         double max_delay_ms, void* stream);
+int dasp_fbdelay_backward(const float* x, const float* ctl, const float* v, const float* gy, float* gx, float* gctl, float* partials, int B,
+                          int C, long N, int H, double sample_rate, double max_delay_ms, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Multi-resolution STFT loss, the op downstream of the effect chain in the reference's training loops
  * (auraloss.freq.MultiResolutionSTFTLoss(): examples/style_transfer.py:341,363, auto_eq.py:252, virtual_analog.py:288; auraloss is
