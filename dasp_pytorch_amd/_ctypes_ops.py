@@ -21,7 +21,7 @@ import ctypes
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _lib, config
+from . import _lib, _resample_design, config
 from ._lib import call, check, ptr, stream
 
 FILTER_TYPES = {"peaking": 0, "low_shelf": 1, "high_shelf": 2, "low_pass": 3, "high_pass": 4}
@@ -961,6 +961,109 @@ class FeedbackDelayFunction(FeedbackDelayKernels, torch.autograd.Function):
     table of tests/autograd_contract_cases.py - one entry for every Function of the package that defines one - is closed: its size is
     pinned by tests/test_call_state_cpu.py. This op's contract is checked by the same batteries from tests/test_gpu_feedback_delay.py,
     which watches FeedbackDelayKernels."""
+
+
+_RESAMPLE_DESIGNS, _RESAMPLE_TABLES = {}, {}
+
+
+def resample_design(o, n, lowpass_filter_width, rolloff, resampling_method, beta):
+    """The host side of a resampler for reduced rates o : n (_resample_design.Design: float64 design, float32 taps, the tables of both
+    directions), kept per set of arguments. NotImplementedError, before anything is launched, for a design that csrc/resample.hip
+    refuses in either direction: a table of more than dasp_resample_table_limit() taps or a span of taps that does not fit the
+    staged window."""
+    key = (int(o), int(n), int(lowpass_filter_width), float(rolloff), resampling_method, None if beta is None else float(beta))
+    d = _RESAMPLE_DESIGNS.get(key)
+    if d is None:
+        d = _resample_design.Design(*key)
+        d.key = key
+        L = _lib.lib()
+        d.tile = tuple(int(L.dasp_resample_tile(t.A, t.B, t.P, t.span)) for t in (d.fwd, d.bwd))
+        if len(_RESAMPLE_DESIGNS) >= 64:
+            _RESAMPLE_DESIGNS.clear()
+        _RESAMPLE_DESIGNS[key] = d
+    if min(d.tile) < 0:
+        raise NotImplementedError(
+            f"resample {o}:{n}: the compact tables hold {d.fwd.floats} (forward) and {d.bwd.floats} (backward) taps over spans of {d.fwd.span} and "
+            f"{d.bwd.span} samples; at most {_lib.lib().dasp_resample_table_limit()} taps and {_lib.lib().dasp_resample_window_limit()} samples "
+            "are implemented. Resample in two stages, or lower lowpass_filter_width")
+    return d
+
+
+def _resample_table(design, which, dev):
+    """One direction's table on the device (dasp_resample_table_store), one per (design, direction, device). The first use outside a
+    capture fills it and waits for the fill once, so that the table is complete for every stream from then on - captures included: a
+    graph reads it like any other constant. A design first used INSIDE a HIP-graph capture gets a table of the graph's own, built fresh
+    and not kept (the rule of _filter_spectrum: memory allocated while capturing belongs to that graph); the fill - kernels that carry
+    the words in their arguments - is then kernel nodes of the graph, not a copy from host memory, and runs on every replay: use a
+    design once before capturing it."""
+    key = (design.key, which, dev.index)
+    hit = _RESAMPLE_TABLES.get(key)
+    if hit is not None:
+        return hit
+    capturing = torch.cuda.is_current_stream_capturing()
+    words = getattr(design, which).words
+    tab = torch.empty(len(words), dtype=torch.int32, device=dev)
+    call("dasp_resample_table_store", ptr(tab), words.ctypes.data_as(ctypes.c_void_p), len(words), stream())
+    if not capturing:
+        torch.cuda.current_stream(dev).synchronize()
+        _RESAMPLE_TABLES[key] = tab          # never dropped (at most 128 KiB each): a captured graph may hold its address
+    return tab
+
+
+def _resample_call(name, *args):
+    try:
+        call(name, *args)
+    except _lib.DaspHipError as e:
+        if "unsupported configuration" in str(e):
+            raise NotImplementedError(str(e)) from None
+        raise
+
+
+class ResampleKernels:
+    """The two directions of resample over the C ABI, as the forward / backward pair of a torch.autograd.Function: x (rows, N) ->
+    y (rows, ceil(n N / o)) by the polyphase filter of `design` (resample_design), and gy -> gx by its transpose, evaluated as a gather
+    (dasp_resample_forward / _backward, csrc/resample.hip). The op is linear: nothing is saved for the backward pass."""
+
+    @staticmethod
+    def forward(ctx, x, design):
+        _lib.require_device(x, "x")
+        rows, N = x.shape
+        M = design.out_len(N)
+        ctx.meta = (x.dtype, rows, N, M)
+        ctx.design = design
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            return torch.empty((rows, M), dtype=x.dtype, device=x.device)
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            t = design.fwd
+            tab = _resample_table(design, "fwd", x.device)
+            y = torch.empty((rows, M), dtype=torch.float32, device=x.device)
+            _resample_call("dasp_resample_forward", ptr(x32), ptr(tab), ptr(y), rows, N, M, design.o, design.n, t.P, t.lo, t.span, stream())
+        return y.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xd, rows, N, M = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        if ctx.empty:
+            return torch.zeros((rows, N), dtype=xd, device=gy.device), None
+        design = ctx.design
+        with torch.cuda.device(gy.device):
+            g32 = _f32c(gy)
+            t = design.bwd
+            tab = _resample_table(design, "bwd", gy.device)
+            gx = torch.empty((rows, N), dtype=torch.float32, device=gy.device)
+            _resample_call("dasp_resample_backward", ptr(g32), ptr(tab), ptr(gx), rows, N, M, design.o, design.n, t.P, t.lo, t.span, stream())
+        return gx.to(xd), None
+
+
+class ResampleFunction(ResampleKernels, torch.autograd.Function):
+    """ResampleKernels bound to autograd. As for feedback_delay the pair lives in a plain class and this one defines no forward of its
+    own: the table of tests/autograd_contract_cases.py is closed. The op's contract is checked by the same batteries from
+    tests/test_gpu_resample.py, which watches ResampleKernels."""
 
 
 _FSPEC_CACHE = {}

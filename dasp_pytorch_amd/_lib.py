@@ -100,6 +100,14 @@ SIGNATURES = {
     "dasp_fbdelay_prepare": (_i, []),
     "dasp_fbdelay_forward": (_i, [_p] * 4 + [_i, _i, _l, _i, _d, _d, _p]),
     "dasp_fbdelay_backward": (_i, [_p] * 7 + [_i, _i, _l, _i, _d, _d, _p]),
+    "dasp_resample_table_limit": (_i, []),
+    "dasp_resample_window_limit": (_i, []),
+    "dasp_resample_tile": (_i, [_i, _i, _i, _i]),
+    "dasp_resample_table_words": (_l, [_i, _i]),
+    "dasp_resample_prepare": (_i, []),
+    "dasp_resample_table_store": (_i, [_p, _p, _l, _p]),
+    "dasp_resample_forward": (_i, [_p] * 3 + [_l, _l, _l, _i, _i, _i, _i, _i, _p]),
+    "dasp_resample_backward": (_i, [_p] * 3 + [_l, _l, _l, _i, _i, _i, _i, _i, _p]),
     "dasp_mrstft_partial_floats": (_l, [_l, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i]),
     "dasp_mrstft_table": (_i, [_p, _p]),
     "dasp_mrstft_forward": (_i, [_p, _p, _p, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 3 + [_i, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)] + [ctypes.c_float] * 4 + [_i, _p]),
@@ -184,6 +192,7 @@ def lib():
         if torch.cuda.is_available():
             L.dasp_device_error()           # allocates the current device's error words now - not under some later stream capture
             L.dasp_fbdelay_prepare()        # feedback_delay's LDS ring is above the default limit: raised now, not inside a call
+            L.dasp_resample_prepare()       # resample's table and window together can be: the same
     return _lib
 
 

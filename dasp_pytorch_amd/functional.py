@@ -11,7 +11,7 @@ from . import _mt19937
 from . import ops as _ops
 from . import _lib
 from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, FeedbackDelayFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
-                  StereoMixFunction, WidenerFunction)
+                  ResampleFunction, StereoMixFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
 
@@ -157,6 +157,39 @@ def feedback_delay(x: torch.Tensor, sample_rate: float, delay_ms: torch.Tensor, 
     require_fp32_ok(x, "feedback_delay")
     H = math.ceil(sr / 1000.0 * max_delay_ms)
     return FeedbackDelayFunction.apply(x, delay_ms, feedback, damping_hz, mix, sr, max_delay_ms, H)
+
+
+def resample(x: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+             resampling_method: str = "sinc_interp_hann", beta: float = None):
+    """Sample-rate conversion by a polyphase windowed sinc: torchaudio.functional.resample's signature and published algorithm, restated
+    (torchaudio itself is not a dependency). x (..., N), time last, every leading dimension a row; returns
+    (..., ceil(n N / o)) with o : n the rates divided by their gcd - (44100, 48000) and (147, 160) give the same bits. Equal rates
+    return x itself. With h, width = signal.resample_taps(...) rounded once to float32 and x zero outside [0, N):
+        y[q n + r] = sum_k h[r][k] x[q o + k - width]
+    in float32, one fused kernel per direction that forms only the products inside each phase's compact span (13 of 161 taps at
+    44.1 -> 48 kHz; csrc/resample.hip). One deviation from torchaudio: h is exactly 0 where the window's argument was clamped, so a
+    NaN or inf sample reaches only the outputs whose span covers it - in torchaudio's conv1d form it poisons every output of the
+    2 width + o window. resampling_method: "sinc_interp_hann" or "sinc_interp_kaiser" (beta = 14.769656459379492 when None).
+    Differentiable in x: the gradient is the transposed filter applied to the upstream gradient, a gather without atomics; y and the
+    gradient are bit-identical run to run and for a row alone or inside a batch. Nothing is saved for the backward pass. The rates and
+    the design are not differentiable; double backward is refused. float32 compute (half and bfloat16 are converted), float64 refused.
+    ValueError for bad arguments (signal.check_resampling); NotImplementedError, before any launch, for a design whose compact table
+    has more than 16384 taps in either direction or whose span of taps does not fit the staged window - every ratio with both reduced
+    rates up to 1024 at the default parameters fits."""
+    o, n = _signal.check_resampling(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+    if o == n:
+        return x
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "resample")
+    if x.dim() < 1:
+        raise RuntimeError("resample: x must have at least one dimension (..., time)")
+    design = _ops.resample_design(o, n, lowpass_filter_width, rolloff, resampling_method, beta)
+    lead, N = x.shape[:-1], x.shape[-1]
+    rows = 1
+    for s in lead:
+        rows *= s
+    y = ResampleFunction.apply(x.reshape(rows, N), design)
+    return y.reshape(*lead, design.out_len(N))
 
 
 def stereo_bus(x: torch.Tensor, sample_rate: int, send_db: torch.Tensor):

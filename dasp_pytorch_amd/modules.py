@@ -383,6 +383,22 @@ class FeedbackDelay(Processor):
                              "damping_hz": (min_damping_hz, max_damping_hz), "mix": (min_mix, max_mix)}
 
 
+class Resample(torch.nn.Module):
+    """functional.resample with torchaudio.transforms.Resample's constructor: callable on (..., N), returns (..., ceil(new N / orig)).
+    No parameters and no buffers: the design is built on the host on first use and its tables are kept per device by the binding. The
+    arguments are checked at construction (signal.check_resampling)."""
+
+    def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, resampling_method: str = "sinc_interp_hann",
+                 lowpass_filter_width: int = 6, rolloff: float = 0.99, beta: float = None):
+        super().__init__()
+        F._signal.check_resampling(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.resampling_method, self.lowpass_filter_width, self.rolloff, self.beta = resampling_method, lowpass_filter_width, rolloff, beta
+
+    def forward(self, x: torch.Tensor):
+        return F.resample(x, self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method, self.beta)
+
+
 def _eq_ranges(sample_rate, g, q):
     top = (sample_rate // 2) - 1000
     cut = {"low_shelf": (20, 2000), "band0": (80, 2000), "band1": (2000, 8000), "band2": (8000, 12000), "band3": (12000, top),

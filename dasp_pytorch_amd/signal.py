@@ -18,7 +18,7 @@ import numpy as np
 import scipy.signal
 import torch
 
-from . import _lib
+from . import _lib, _resample_design
 from . import ops as _ops
 from .ops import FILTER_TYPES, BiquadFunction, SosFiltFunction
 from .ops64 import LFilterFunction, SosFilt64Function, is_f64
@@ -66,6 +66,27 @@ def oversampling_taps(oversample: int, half_width: int = 12, beta: float = 8.0, 
     L, H = int(oversample), int(half_width)
     c = np.arange(-H * L, H * L + 1, dtype=np.float64)
     return torch.from_numpy(cutoff * np.sinc(cutoff * c / L) * np.kaiser(2 * H * L + 1, beta))
+
+
+check_resampling = _resample_design.check_resampling
+
+
+def resample_taps(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+                  resampling_method: str = "sinc_interp_hann", beta: float = None):
+    """The polyphase filter of functional.resample (torchaudio.functional.resample's published design, restated). With
+    o : n the rates divided by their gcd, base = min(o, n) rolloff, width = ceil(lowpass_filter_width o / base) and K = 2 width + o:
+        t = (-r / n + (k - width) / o) base, clamped to +-lowpass_filter_width = +-W                  r in [0, n), k in [0, K)
+        window = cos^2(pi t / (2 W))  ("sinc_interp_hann")   or   I0(beta sqrt(1 - (t / W)^2)) / I0(beta)  ("sinc_interp_kaiser",
+                                                                  beta = 14.769656459379492 when None)
+        h[r][k] = sinc(t) window base / o
+    One deviation from torchaudio: where t was clamped, h[r][k] is exactly 0 (torchaudio's formula gives at most 1e-20 there for the
+    Kaiser window and a float32 zero for the Hann window), so every phase has a compact span of taps. Output q n + r of the resampler is
+    sum_k h[r][k] x[q o + k - width]. Returns (h as a float64 CPU tensor (n, K), width). check_resampling(...) is the argument check:
+    ValueError for rates that are not positive integers, lowpass_filter_width < 1, a rolloff outside (0, 1], an unknown method, a
+    negative or non-finite beta."""
+    o, n = check_resampling(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+    h, width, _ = _resample_design.taps(o, n, lowpass_filter_width, rolloff, resampling_method, beta)
+    return torch.from_numpy(h), width
 
 
 def lfilter_via_fsm(x: torch.Tensor, b: torch.Tensor, a: torch.Tensor = None):

@@ -475,6 +475,38 @@ int dasp_fbdelay_forward(const float* x, const float* ctl, float* y, float* v, i
 int dasp_fbdelay_backward(const float* x, const float* ctl, const float* v, const float* gy, float* gx, float* gctl, float* partials, int B,
                           int C, long N, int H, double sample_rate, double max_delay_ms, void* stream);
 
+/* resample: polyphase windowed-sinc sample-rate conversion by the reduced ratio orig : new_ = o : n, and its adjoint
+ * (csrc/resample.hip; the definition is DESIGN.md 3.15, a restatement of torchaudio.functional.resample's published algorithm with
+ * the taps exactly zero where the window's argument was clamped). x, gx (rows, N) fp32; y, gy (rows, M) fp32, M = ceil(n N / o):
+ *   forward   y[q n + r] = sum_k h[r][k] x[q o + k - width]        x zero outside [0, N)
+ *   backward  gx[i] = sum over the (q, r) whose span covers i of h[r][i + width - q o] gy[q n + r]       a gather, no atomics
+ * Both directions are one form, out[Q A + p] = sum_{m < cnt[p]} T[m][p] in[Q B + off[p] + m], forward with (A, B) = (n, o), backward
+ * with (A, B) = (o, n); `table` is that direction's table in device memory, dasp_resample_table_words(A, taps) = A taps + A 32-bit
+ * words: the float32 taps tap-major, T[m A + p], zero for m >= cnt[p], then per phase (off[p] - lo) | cnt[p] << 16, with
+ * taps = max cnt, lo = min off, span = max (off + cnt) - lo. The host builds both in float64 and rounds once
+ * (dasp_pytorch_amd/_resample_design.py); dasp_resample_table_store copies host words into device memory with kernels that carry them
+ * in their arguments - kernel nodes under stream capture, no copy from host memory.
+ * One workgroup computes dasp_resample_tile(A, B, taps, span) consecutive outputs of one row: a whole number of frames of A outputs,
+ * about 2048 where the staged input window (at most dasp_resample_window_limit() = 20480 words) allows it. A table of more than
+ * dasp_resample_table_limit() = 16384 taps, a span beyond the window limit, or table and window together beyond 158 KiB of LDS:
+ * DASP_ERR_UNSUPPORTED (-2 from the queries), as are more than 2^31 - 1 workgroups. A null pointer, a non-positive size, taps < 1,
+ * span < taps, M other than ceil(n N / o), lo outside [-20480, B]: DASP_ERR_ARG (-1 from the queries). All of it is checked before any
+ * launch. dasp_resample_prepare() raises the kernels' dynamic-LDS limit on the current device; the binding calls it once when it
+ * loads the library, and the first call on a device that was not prepared does it itself.
+ * Exactly cnt[p] products are formed per output, in ascending m, float32 FMAs from zero: an output depends on its phase and its
+ * inputs only - y and gx are bit-identical run to run, for a row alone or in a batch. A NaN or inf sample reaches exactly the outputs
+ * whose span covers it (in the conv1d form of the same filter it reaches every output of the 2 width + o window). */
+int dasp_resample_table_limit(void);
+int dasp_resample_window_limit(void);
+int dasp_resample_tile(int out_period, int in_period, int taps, int span);
+long dasp_resample_table_words(int out_period, int taps);
+int dasp_resample_prepare(void);
+int dasp_resample_table_store(void* dst, const void* host_words, long words, void* stream);
+int dasp_resample_forward(const float* x, const void* table, float* y, long rows, long N, long M, int orig, int new_, int taps, int lo, int span,
+                          void* stream);
+int dasp_resample_backward(const float* gy, const void* table, float* gx, long rows, long N, long M, int orig, int new_, int taps, int lo, int span,
+                           void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Multi-resolution STFT loss, the op downstream of the effect chain in the reference's training loops
  * (auraloss.freq.MultiResolutionSTFTLoss(): examples/style_transfer.py:341,363, auto_eq.py:252, virtual_analog.py:288; auraloss is
