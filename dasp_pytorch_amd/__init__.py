@@ -1,6 +1,8 @@
 """dasp_pytorch_amd -- MI355X-native hot path of dasp_pytorch.functional."""
 from . import chain, config, functional, losses, modules, signal  # noqa: F401
 from .functional import (advanced_distortion, compressor, distortion, expander, feedback_delay, gain, graphic_eq, loudness, loudness_normalize,  # noqa: F401
-                         modulated_delay, noise_shaped_reverberation, oversampled_distortion, parametric_eq, peak_normalize, resample, stereo_bus, stereo_mix, stereo_panner, stereo_widener)
-from .modules import Compressor, Distortion, Expander, FeedbackDelay, Gain, ModulatedDelay, NoiseShapedReverb, OversampledDistortion, ParametricEQ, Processor, Resample  # noqa: F401
+                         modulated_delay, noise_shaped_reverberation, oversampled_distortion, parametric_eq, peak_normalize, phaser, resample, stereo_bus, stereo_mix, stereo_panner,
+                         stereo_widener)
+from .modules import (Compressor, Distortion, Expander, FeedbackDelay, Gain, ModulatedDelay, NoiseShapedReverb, OversampledDistortion, ParametricEQ, Phaser, Processor,  # noqa: F401
+                      Resample)
 from .signal import resample_taps  # noqa: F401

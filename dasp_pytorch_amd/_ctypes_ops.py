@@ -963,6 +963,61 @@ class FeedbackDelayFunction(FeedbackDelayKernels, torch.autograd.Function):
     which watches FeedbackDelayKernels."""
 
 
+class PhaserKernels:
+    """The two directions of phaser over the C ABI, as the forward / backward pair of a torch.autograd.Function:
+    y = (1 - mix) x + mix s_K, s_K the output of K first-order all-pass stages whose shared coefficient a sine LFO sweeps
+    (dasp_phaser_forward / _backward, csrc/phaser.hip). rate_hz, center_hz, depth, phase, mix: bs values each; sample_rate, stereo_spread:
+    floats; stages: K. Saves x, the controls packed as (bs, 5) and, when anything needs a gradient, the K stage states before every tile
+    (dasp_phaser_state_floats): the backward kernel rebuilds the stage signals of a tile from them."""
+
+    @staticmethod
+    def forward(ctx, x, rate_hz, center_hz, depth, phase, mix, sample_rate, stages, stereo_spread):
+        _lib.require_device(x, "x")
+        B, C, N = x.shape
+        ctls = (rate_hz, center_hz, depth, phase, mix)
+        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
+        ctx.cfg = (float(sample_rate), int(stages), float(stereo_spread))
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            return torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            ctl = torch.stack([c.detach().reshape(B).to(device=x.device, dtype=torch.float32) for c in ctls], dim=-1).contiguous()
+            y = torch.empty_like(x32)
+            states = None
+            if any(ctx.needs_input_grad[:6]):
+                states = torch.empty(_lib.lib().dasp_phaser_state_floats(B * C, N, int(stages)), dtype=torch.float32, device=x.device)
+            call("dasp_phaser_forward", ptr(x32), ptr(ctl), ptr(y), ptr(states), B, C, N, int(stages), ctx.cfg[0], ctx.cfg[2], stream())
+            if states is not None:
+                ctx.save_for_backward(x32, ctl, states)
+        return y.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xd, cmeta = ctx.meta
+        if ctx.empty:
+            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 3))
+        sample_rate, stages, stereo_spread = ctx.cfg
+        x32, ctl, states = ctx.saved_tensors
+        B, C, N = x32.shape
+        with torch.cuda.device(x32.device):
+            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # not written when x needs no gradient; the scans still run
+            gctl = torch.empty_like(ctl)
+            partials = torch.empty(_lib.lib().dasp_phaser_partial_floats(B * C), dtype=torch.float32, device=x32.device)
+            g32 = _f32c(gy)
+            call("dasp_phaser_backward", ptr(x32), ptr(ctl), ptr(states), ptr(g32), ptr(gx), ptr(gctl), ptr(partials), B, C, N, stages, sample_rate,
+                 stereo_spread, stream())
+        gc = tuple(gctl[:, q].reshape(s).to(d) if need else None for q, ((d, s), need) in enumerate(zip(cmeta, ctx.needs_input_grad[1:6])))
+        return (None if gx is None else gx.to(xd),) + gc + (None,) * 3
+
+
+class PhaserFunction(PhaserKernels, torch.autograd.Function):
+    """PhaserKernels bound to autograd. As for feedback_delay the pair lives in a plain class and this one defines no forward of its own:
+    the table of tests/autograd_contract_cases.py is closed, and this op's contract is checked by the same batteries from
+    tests/test_gpu_phaser.py, which watches PhaserKernels."""
+
+
 _RESAMPLE_DESIGNS, _RESAMPLE_TABLES = {}, {}
 
 

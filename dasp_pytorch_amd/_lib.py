@@ -100,6 +100,13 @@ SIGNATURES = {
     "dasp_fbdelay_prepare": (_i, []),
     "dasp_fbdelay_forward": (_i, [_p] * 4 + [_i, _i, _l, _i, _d, _d, _p]),
     "dasp_fbdelay_backward": (_i, [_p] * 7 + [_i, _i, _l, _i, _d, _d, _p]),
+    "dasp_phaser_max_stages": (_i, []),
+    "dasp_phaser_tile": (_i, [_i]),
+    "dasp_phaser_state_floats": (_l, [_l, _l, _i]),
+    "dasp_phaser_partial_floats": (_l, [_l]),
+    "dasp_phaser_prepare": (_i, []),
+    "dasp_phaser_forward": (_i, [_p] * 4 + [_i, _i, _l, _i, _d, _d, _p]),
+    "dasp_phaser_backward": (_i, [_p] * 7 + [_i, _i, _l, _i, _d, _d, _p]),
     "dasp_resample_table_limit": (_i, []),
     "dasp_resample_window_limit": (_i, []),
     "dasp_resample_tile": (_i, [_i, _i, _i, _i]),
@@ -193,6 +200,7 @@ def lib():
             L.dasp_device_error()           # allocates the current device's error words now - not under some later stream capture
             L.dasp_fbdelay_prepare()        # feedback_delay's LDS ring is above the default limit: raised now, not inside a call
             L.dasp_resample_prepare()       # resample's table and window together can be: the same
+            L.dasp_phaser_prepare()         # and the phaser's rebuilt stage signals in its backward kernel
     return _lib
 
 

@@ -11,7 +11,7 @@ from . import _mt19937
 from . import ops as _ops
 from . import _lib
 from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, FeedbackDelayFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
-                  ResampleFunction, StereoMixFunction, WidenerFunction)
+                  PhaserFunction, ResampleFunction, StereoMixFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
 
@@ -157,6 +157,41 @@ def feedback_delay(x: torch.Tensor, sample_rate: float, delay_ms: torch.Tensor, 
     require_fp32_ok(x, "feedback_delay")
     H = math.ceil(sr / 1000.0 * max_delay_ms)
     return FeedbackDelayFunction.apply(x, delay_ms, feedback, damping_hz, mix, sr, max_delay_ms, H)
+
+
+def phaser(x: torch.Tensor, sample_rate: float, rate_hz: torch.Tensor, center_hz: torch.Tensor, depth: torch.Tensor, phase: torch.Tensor,
+           mix: torch.Tensor, stages: int = 4, stereo_spread: float = 0.25):
+    """Phaser: `stages` first-order all-pass sections in series whose shared break frequency a sine LFO sweeps, mixed with the dry
+    signal. x (bs, chs, seq_len); rate_hz, center_hz, depth, phase and mix hold bs values each. phase and stereo_spread are in turns,
+    depth in octaves (the conventions of modulated_delay); stages is a plain int K, 1 <= K <= 12, stereo_spread a plain float. For item
+    b, channel c and sample n, with every state zero before sample 0:
+        theta = 2 pi (rate_hz n / sample_rate + phase + c stereo_spread)
+        f[n] = clamp(center_hz 2^(depth sin theta), sample_rate/4096, 0.49 sample_rate)
+        t = tan(pi f / sample_rate);   a[n] = (t - 1) / (t + 1)                                        (|a| < 1 by the clamp)
+        s_0 = x;   s_k[n] = a[n] (s_{k-1}[n] - s_k[n-1]) + s_{k-1}[n-1],  k = 1..K                      (all stages share a[n])
+        y[n] = (1 - mix) x[n] + mix s_K[n]
+    mix = 0.5 gives the classic notches, K / 2 of them; mix = 1 is the pure all-pass, a vibrato-like phase wobble. The LFO's phase is
+    float64 in the kernel and reduced to a turn before it is rounded; everything after it is float32 (csrc/phaser.hip). The op works on
+    whole tensors, not on a stream.
+    Differentiable in x and in all five controls. The gradients of rate_hz, center_hz, depth and phase take no contribution from samples
+    where f was clamped. A NaN control makes its own item NaN and no other.
+    One workgroup walks one (item, channel) row tile by tile: the op cannot fill the chip at training batch sizes.
+    Out of scope: a feedback ("resonance") path around the cascade - it couples the K stages into one (K+1)-dimensional time-varying
+    system whose scan composes (K+1) x (K+1) matrices instead of scalar pairs -, per-stage break frequencies, LFO shapes other than
+    sine, and float64. A wrong control count raises RuntimeError naming the control; a sample_rate that is not positive and finite, a
+    non-finite stereo_spread or stages outside 1..12 ValueError, before anything touches the device."""
+    bs, chs, seq_len = x.size()
+    for name, c in (("rate_hz", rate_hz), ("center_hz", center_hz), ("depth", depth), ("phase", phase), ("mix", mix)):
+        if c.numel() != bs:
+            raise RuntimeError(f"{name}: shape '[{bs}]' is invalid for input of size {c.numel()}")
+    sr, spread = float(sample_rate), float(stereo_spread)
+    if not (sr > 0.0 and sr != float("inf")) or spread - spread != 0.0:
+        raise ValueError(f"phaser: finite sample_rate > 0 and finite stereo_spread, got {sample_rate}, {stereo_spread}")
+    if isinstance(stages, bool) or int(stages) != stages or not 1 <= stages <= 12:
+        raise ValueError(f"phaser: stages must be an integer from 1 to 12, got {stages}")
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "phaser")
+    return PhaserFunction.apply(x, rate_hz, center_hz, depth, phase, mix, sr, int(stages), spread)
 
 
 def resample(x: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,

@@ -383,6 +383,24 @@ class FeedbackDelay(Processor):
                              "damping_hz": (min_damping_hz, max_damping_hz), "mix": (min_mix, max_mix)}
 
 
+class Phaser(Processor):
+    """Phaser (functional.phaser) with `stages` all-pass stages. The parameters rate_hz, center_hz, depth, phase and mix are the
+    functional's own argument names; stages and stereo_spread are fixed at construction."""
+
+    def __init__(self, sample_rate: int, stages: int = 4, min_rate_hz: float = 0.05, max_rate_hz: float = 10.0, min_center_hz: float = 200.0,
+                 max_center_hz: float = 4000.0, min_depth: float = 0.0, max_depth: float = 2.0, min_phase: float = 0.0, max_phase: float = 1.0,
+                 min_mix: float = 0.0, max_mix: float = 1.0, stereo_spread: float = 0.25):
+        super().__init__()
+        if isinstance(stages, bool) or int(stages) != stages or not 1 <= stages <= 12:
+            raise ValueError(f"stages must be an integer from 1 to 12, got {stages}")
+        self.sample_rate = sample_rate
+        self.stages = int(stages)
+        self.stereo_spread = stereo_spread
+        self.process_fn = functools.partial(F.phaser, stages=self.stages, stereo_spread=stereo_spread)
+        self.param_ranges = {"rate_hz": (min_rate_hz, max_rate_hz), "center_hz": (min_center_hz, max_center_hz), "depth": (min_depth, max_depth),
+                             "phase": (min_phase, max_phase), "mix": (min_mix, max_mix)}
+
+
 class Resample(torch.nn.Module):
     """functional.resample with torchaudio.transforms.Resample's constructor: callable on (..., N), returns (..., ceil(new N / orig)).
     No parameters and no buffers: the design is built on the host on first use and its tables are kept per device by the binding. The

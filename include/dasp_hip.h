@@ -475,6 +475,38 @@ int dasp_fbdelay_forward(const float* x, const float* ctl, float* y, float* v, i
 int dasp_fbdelay_backward(const float* x, const float* ctl, const float* v, const float* gy, float* gx, float* gctl, float* partials, int B,
                           int C, long N, int H, double sample_rate, double max_delay_ms, void* stream);
 
+/* phaser: `stages` first-order all-pass sections in series whose shared coefficient a sine LFO sweeps, mixed with the dry signal; a
+ * recurrence whose coefficient changes with every sample, evaluated as a scan, one workgroup per (b, c) row (csrc/phaser.hip).
+ * x, y, gy, gx (B, C, N) fp32; ctl, gctl (B, 5) fp32: rate_hz, center_hz, depth (octaves), phase (turns), mix.  For item b, channel c,
+ * sample n, with every state zero before sample 0:
+ *   theta = 2 pi (rate_hz n / sample_rate + phase + c stereo_spread)
+ *   f = clamp(center_hz 2^(depth sin theta), sample_rate/4096, 0.49 sample_rate),  t = tan(pi f / sample_rate),  a = (t - 1) / (t + 1)
+ *   s_0 = x,  s_k[n] = a[n] (s_{k-1}[n] - s_k[n-1]) + s_{k-1}[n-1]  (k = 1 .. stages),   y[n] = (1 - mix) x[n] + mix s_stages[n]
+ * The phase is float64 in the kernels and reduced to a turn before it is rounded; everything after it is float32.
+ * A row is walked in tiles of dasp_phaser_tile(stages) samples, 1 <= stages <= dasp_phaser_max_stages().
+ * Forward: states (NULL: not saved) receives dasp_phaser_state_floats(B * C, N, stages) = rows * ceil(N / tile) * stages floats, the
+ * stage states before every tile - all the backward pass needs beyond x and ctl.  Backward: gx (NULL: not written), gctl; the stage
+ * signals of a tile are rebuilt from states; partials is scratch of dasp_phaser_partial_floats(B * C) = 5 floats per row, summed over
+ * an item's channels in fp64 in a fixed order by a second launch. No atomics. y, states, gx and gctl are bit-identical run to run.
+ * The gradients of rate_hz, center_hz, depth and phase take no contribution from samples where f was clamped.
+ * dasp_phaser_prepare() raises the backward kernel's dynamic-LDS limit on the current device; the binding calls it once when it loads
+ * the library, and the first backward call on a device that was not prepared does it itself.
+ * A null pointer (states in forward and gx apart), a non-positive size, stages < 1, a sample rate that is not positive and finite or a
+ * non-finite stereo_spread: DASP_ERR_ARG (-1 from the queries); stages above its maximum or B * C >= 2^31: DASP_ERR_UNSUPPORTED (-2
+ * from the queries). All of it is checked before any launch.
+ * Non-finite input: a NaN or inf sample stays in the stages' states - it reaches every later sample of its row. A NaN control passes
+ * the clamp and makes the item's y, gx and control gradients NaN (a NaN mix its own gradient too, which holds no term with mix). Other
+ * items keep every bit. */
+int dasp_phaser_max_stages(void);
+int dasp_phaser_tile(int stages);
+long dasp_phaser_state_floats(long rows, long N, int stages);
+long dasp_phaser_partial_floats(long rows);
+int dasp_phaser_prepare(void);
+int dasp_phaser_forward(const float* x, const float* ctl, float* y, float* states, int B, int C, long N, int stages, double sample_rate,
+                        double stereo_spread, void* stream);
+int dasp_phaser_backward(const float* x, const float* ctl, const float* states, const float* gy, float* gx, float* gctl, float* partials, int B,
+                         int C, long N, int stages, double sample_rate, double stereo_spread, void* stream);
+
 /* resample: polyphase windowed-sinc sample-rate conversion by the reduced ratio orig : new_ = o : n, and its adjoint
  * (csrc/resample.hip; the definition is DESIGN.md 3.15, a restatement of torchaudio.functional.resample's published algorithm with
  * the taps exactly zero where the window's argument was clamped). x, gx (rows, N) fp32; y, gy (rows, M) fp32, M = ceil(n N / o):
