@@ -1018,6 +1018,65 @@ class PhaserFunction(PhaserKernels, torch.autograd.Function):
     tests/test_gpu_phaser.py, which watches PhaserKernels."""
 
 
+TVFILTER_MODES = ("lowpass", "bandpass", "highpass", "notch")
+
+
+class TimeVaryingFilterKernels:
+    """The two directions of time_varying_filter over the C ABI, as the forward / backward pair of a torch.autograd.Function:
+    y = (1 - mix) x + mix w, w the output of a trapezoidal state-variable filter whose g and k follow the curves cutoff_hz and q
+    (dasp_tvfilter_forward / _backward, csrc/tvfilter.hip). cutoff_hz, q: (bs, F), F = signal.control_frames(seq_len, hop); mix: bs values;
+    sample_rate: a float; hop: an int; mode: an index into TVFILTER_MODES. Saves x, the curves, mix and, when anything needs a gradient,
+    the two states before every tile (dasp_tvfilter_state_floats): the backward kernel rebuilds a tile from them."""
+
+    @staticmethod
+    def forward(ctx, x, cutoff_hz, q, mix, sample_rate, hop, mode):
+        _lib.require_device(x, "x")
+        B, C, N = x.shape
+        ctls = (cutoff_hz, q, mix)
+        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
+        ctx.cfg = (float(sample_rate), int(hop), int(mode))
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            return torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            cut, qq = (c.detach().reshape(B, -1).to(device=x.device, dtype=torch.float32).contiguous() for c in (cutoff_hz, q))
+            mx = mix.detach().reshape(B).to(device=x.device, dtype=torch.float32).contiguous()
+            y = torch.empty_like(x32)
+            states = None
+            if any(ctx.needs_input_grad[:4]):
+                states = torch.empty(_lib.lib().dasp_tvfilter_state_floats(B * C, N), dtype=torch.float32, device=x.device)
+            call("dasp_tvfilter_forward", ptr(x32), ptr(cut), ptr(qq), ptr(mx), ptr(y), ptr(states), B, C, N, ctx.cfg[1], ctx.cfg[2], ctx.cfg[0], stream())
+            if states is not None:
+                ctx.save_for_backward(x32, cut, qq, mx, states)
+        return y.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xd, cmeta = ctx.meta
+        if ctx.empty:
+            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 3))
+        sample_rate, hop, mode = ctx.cfg
+        x32, cut, qq, mx, states = ctx.saved_tensors
+        B, C, N = x32.shape
+        with torch.cuda.device(x32.device):
+            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # not written when x needs no gradient; the scans still run
+            gcut, gq, gmix = torch.empty_like(cut), torch.empty_like(qq), torch.empty_like(mx)
+            scratch = torch.empty(_lib.lib().dasp_tvfilter_scratch_floats(B * C, N, hop), dtype=torch.float32, device=x32.device)
+            g32 = _f32c(gy)
+            call("dasp_tvfilter_backward", ptr(x32), ptr(cut), ptr(qq), ptr(mx), ptr(states), ptr(g32), ptr(gx), ptr(gcut), ptr(gq), ptr(gmix), ptr(scratch),
+                 B, C, N, hop, mode, sample_rate, stream())
+        gc = tuple(g.reshape(s).to(d) if need else None for g, (d, s), need in zip((gcut, gq, gmix), cmeta, ctx.needs_input_grad[1:4]))
+        return (None if gx is None else gx.to(xd),) + gc + (None,) * 3
+
+
+class TimeVaryingFilterFunction(TimeVaryingFilterKernels, torch.autograd.Function):
+    """TimeVaryingFilterKernels bound to autograd. As for phaser the pair lives in a plain class and this one defines no forward of its
+    own: the table of tests/autograd_contract_cases.py is closed, and this op's contract is checked by the same batteries from
+    tests/test_gpu_tvfilter.py, which watches TimeVaryingFilterKernels."""
+
+
 _RESAMPLE_DESIGNS, _RESAMPLE_TABLES = {}, {}
 
 

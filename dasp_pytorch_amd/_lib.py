@@ -107,6 +107,12 @@ SIGNATURES = {
     "dasp_phaser_prepare": (_i, []),
     "dasp_phaser_forward": (_i, [_p] * 4 + [_i, _i, _l, _i, _d, _d, _p]),
     "dasp_phaser_backward": (_i, [_p] * 7 + [_i, _i, _l, _i, _d, _d, _p]),
+    "dasp_tvfilter_tile": (_i, []),
+    "dasp_tvfilter_frames": (_l, [_l, _i]),
+    "dasp_tvfilter_state_floats": (_l, [_l, _l]),
+    "dasp_tvfilter_scratch_floats": (_l, [_l, _l, _i]),
+    "dasp_tvfilter_forward": (_i, [_p] * 6 + [_i, _i, _l, _i, _i, _d, _p]),
+    "dasp_tvfilter_backward": (_i, [_p] * 11 + [_i, _i, _l, _i, _i, _d, _p]),
     "dasp_resample_table_limit": (_i, []),
     "dasp_resample_window_limit": (_i, []),
     "dasp_resample_tile": (_i, [_i, _i, _i, _i]),

@@ -11,7 +11,7 @@ from . import _mt19937
 from . import ops as _ops
 from . import _lib
 from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, FeedbackDelayFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
-                  PhaserFunction, ResampleFunction, StereoMixFunction, WidenerFunction)
+                  PhaserFunction, ResampleFunction, StereoMixFunction, TVFILTER_MODES, TimeVaryingFilterFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
 
@@ -192,6 +192,50 @@ def phaser(x: torch.Tensor, sample_rate: float, rate_hz: torch.Tensor, center_hz
     _lib.require_device(x, "x")
     require_fp32_ok(x, "phaser")
     return PhaserFunction.apply(x, rate_hz, center_hz, depth, phase, mix, sr, int(stages), spread)
+
+
+def time_varying_filter(x: torch.Tensor, sample_rate: float, cutoff_hz: torch.Tensor, q: torch.Tensor, mix: torch.Tensor, hop: int = 64,
+                        mode: str = "lowpass"):
+    """Resonant filter whose cutoff and resonance follow control curves: Simper's trapezoidal (TPT) state-variable filter, the published
+    Cytomic form, which stays well-behaved when its coefficients move every sample - wah, filter sweeps, the synth low-pass, automation
+    of an EQ band. x (bs, chs, seq_len); cutoff_hz and q (bs, F) with F = signal.control_frames(seq_len, hop) = ceil(seq_len / hop) + 1,
+    frame point j at sample j hop, shared by an item's channels; mix holds bs values. hop is a plain int, a power of two from 8 to 2048;
+    mode one of "lowpass", "bandpass", "highpass", "notch". For item b, every channel and sample n, with both states zero before sample 0:
+        G_j = tan(pi clamp(cutoff_hz[b,j], sample_rate/4096, 0.49 sample_rate) / sample_rate);   K_j = 1 / clamp(q[b,j], 0.1, 100)
+        j = n // hop;   t = (n mod hop) / hop;   g = G_j + t (G_{j+1} - G_j);   k = K_j + t (K_{j+1} - K_j)
+        a1 = 1 / (1 + g (g + k));   a2 = g a1;   a3 = g a2
+        v3 = x[n] - ic2;   v1 = a1 ic1 + a2 v3;   v2 = ic2 + a2 ic1 + a3 v3;   ic1 <- 2 v1 - ic1;   ic2 <- 2 v2 - ic2
+        w = v2 (lowpass) | k v1 (bandpass, 0 dB at the centre) | x - k v1 - v2 (highpass) | x - k v1 (notch)
+        y[n] = (1 - mix) x[n] + mix w
+    What is interpolated is G and K, not Hz: the frame points are taken in float64 in the kernel and rounded once, everything after them
+    is float32 (csrc/tvfilter.hip). With constant curves the outputs are the RBJ low-pass, high-pass and constant-peak band-pass biquads
+    at the same frequency and Q. The op works on whole tensors, not on a stream.
+    Differentiable in x, cutoff_hz, q and mix, every frame value included. The gradient of a frame value that was clamped is exactly
+    zero. The clamps are comparisons, which a NaN passes: a NaN frame value j makes its item NaN from sample (j - 1) hop on and leaves
+    earlier samples and other items alone.
+    One workgroup walks one (item, channel) row tile by tile: the op cannot fill the chip at training batch sizes.
+    Out of scope: an envelope follower that drives the cutoff from x itself, per-channel curves, cascaded sections or a morphing mode
+    mix, look-back segments for few rows, float64, and a torch.ops.dasp registration. A wrong frame count raises RuntimeError naming the
+    control and the expected F; a hop that is no power of two from 8 to 2048, an unknown mode or a sample_rate that is not positive and
+    finite ValueError, before anything touches the device."""
+    bs, chs, seq_len = x.size()
+    sr = float(sample_rate)
+    if not (sr > 0.0 and sr != float("inf")):
+        raise ValueError(f"time_varying_filter: finite sample_rate > 0, got {sample_rate}")
+    if mode not in TVFILTER_MODES:
+        raise ValueError(f"time_varying_filter: mode must be one of {', '.join(TVFILTER_MODES)}, got {mode!r}")
+    try:
+        frames = _signal.control_frames(seq_len, hop)
+    except ValueError as e:
+        raise ValueError(f"time_varying_filter: {e}") from None
+    for name, c in (("cutoff_hz", cutoff_hz), ("q", q)):
+        if c.dim() != 2 or tuple(c.shape) != (bs, frames):
+            raise RuntimeError(f"{name}: expected shape [{bs}, {frames}] (F = ceil({seq_len} / {hop}) + 1 = {frames} frame points), got {list(c.shape)}")
+    if mix.numel() != bs:
+        raise RuntimeError(f"mix: shape '[{bs}]' is invalid for input of size {mix.numel()}")
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "time_varying_filter")
+    return TimeVaryingFilterFunction.apply(x, cutoff_hz, q, mix, sr, int(hop), TVFILTER_MODES.index(mode))
 
 
 def resample(x: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,

@@ -28,6 +28,7 @@ import weakref
 import torch
 
 from . import functional as F
+from . import signal as S
 
 
 def denormalize(norm_val, max_val, min_val):
@@ -399,6 +400,39 @@ class Phaser(Processor):
         self.process_fn = functools.partial(F.phaser, stages=self.stages, stereo_spread=stereo_spread)
         self.param_ranges = {"rate_hz": (min_rate_hz, max_rate_hz), "center_hz": (min_center_hz, max_center_hz), "depth": (min_depth, max_depth),
                              "phase": (min_phase, max_phase), "mix": (min_mix, max_mix)}
+
+
+class TimeVaryingFilter(Processor):
+    """Time-varying state-variable filter (functional.time_varying_filter); hop and mode are fixed at construction. Its controls are
+    curves, so the parameter tensor of process_normalized is (bs, 2 F + 1) with F = signal.control_frames(seq_len, hop): F columns of
+    cutoff_hz, F of q, one of mix, each on [0, 1] and mapped linearly onto its range of `param_ranges`."""
+
+    def __init__(self, sample_rate: int, hop: int = 64, mode: str = "lowpass", min_cutoff_hz: float = 50.0, max_cutoff_hz: float = 12000.0,
+                 min_q: float = 0.5, max_q: float = 8.0, min_mix: float = 0.0, max_mix: float = 1.0):
+        super().__init__()
+        S.control_frames(0, hop)
+        if mode not in F.TVFILTER_MODES:
+            raise ValueError(f"mode must be one of {', '.join(F.TVFILTER_MODES)}, got {mode!r}")
+        self.sample_rate = sample_rate
+        self.hop = int(hop)
+        self.mode = mode
+        self.process_fn = functools.partial(F.time_varying_filter, hop=self.hop, mode=mode)
+        self.param_ranges = {"cutoff_hz": (min_cutoff_hz, max_cutoff_hz), "q": (min_q, max_q), "mix": (min_mix, max_mix)}
+
+    def process_normalized(self, x: torch.Tensor, param_tensor: torch.Tensor):
+        frames = S.control_frames(x.shape[-1], self.hop)
+        if param_tensor.dim() != 2 or param_tensor.shape[1] != 2 * frames + 1:
+            raise ValueError(f"Parameter tensor has {param_tensor.shape[-1]} parameters, but processor has {2 * frames + 1} parameters "
+                             f"({frames} frame points of cutoff_hz, {frames} of q, mix).")
+        if self.validate_range and not getattr(_validated, "on", False) and not (param_tensor.is_cuda and torch.cuda.is_current_stream_capturing()):
+            names = ["cutoff_hz"] * frames + ["q"] * frames + ["mix"]              # _check_range, with a name per column
+            if self.validate_range == "deferred":
+                self._deferred().submit(param_tensor, names)
+            else:
+                check_unit_range(param_tensor, names)
+        (clo, chi), (qlo, qhi), (mlo, mhi) = (self.param_ranges[k] for k in ("cutoff_hz", "q", "mix"))
+        return self.process_fn(x, self.sample_rate, cutoff_hz=denormalize(param_tensor[:, :frames], chi, clo),
+                               q=denormalize(param_tensor[:, frames:2 * frames], qhi, qlo), mix=denormalize(param_tensor[:, 2 * frames], mhi, mlo))
 
 
 class Resample(torch.nn.Module):

@@ -68,6 +68,17 @@ def oversampling_taps(oversample: int, half_width: int = 12, beta: float = 8.0, 
     return torch.from_numpy(cutoff * np.sinc(cutoff * c / L) * np.kaiser(2 * H * L + 1, beta))
 
 
+def control_frames(seq_len: int, hop: int):
+    """The number of frame points F = ceil(seq_len / hop) + 1 that a control curve of functional.time_varying_filter holds for a signal of
+    seq_len samples: frame point j sits at sample j hop, and every sample lies between two of them. ValueError for a hop that is no
+    power of two from 8 to 2048 or a negative seq_len."""
+    if isinstance(hop, bool) or not isinstance(hop, numbers.Integral) or not 8 <= hop <= 2048 or hop & (hop - 1):
+        raise ValueError(f"hop must be a power of two from 8 to 2048, got {hop!r}")
+    if isinstance(seq_len, bool) or not isinstance(seq_len, numbers.Integral) or seq_len < 0:
+        raise ValueError(f"seq_len must be a non-negative integer, got {seq_len!r}")
+    return -(-int(seq_len) // int(hop)) + 1
+
+
 check_resampling = _resample_design.check_resampling
 
 

@@ -507,6 +507,38 @@ int dasp_phaser_forward(const float* x, const float* ctl, float* y, float* state
 int dasp_phaser_backward(const float* x, const float* ctl, const float* states, const float* gy, float* gx, float* gctl, float* partials, int B,
                          int C, long N, int stages, double sample_rate, double stereo_spread, void* stream);
 
+/* time_varying_filter: Simper's trapezoidal state-variable filter (the published Cytomic form) whose cutoff and resonance follow control
+ * curves; a recurrence that couples two states, evaluated as a scan over 2 x 2 affine maps, one workgroup per (b, c) row
+ * (csrc/tvfilter.hip). x, y, gy, gx (B, C, N) fp32; cutoff_hz, q, gcutoff, gq (B, F) fp32, F = dasp_tvfilter_frames(N, hop) =
+ * ceil(N / hop) + 1, shared by an item's channels; mix, gmix (B) fp32. hop: a power of two from 8 to 2048. mode: 0 lowpass, 1 bandpass,
+ * 2 highpass, 3 notch. For item b, every channel and sample n, with both states zero before sample 0:
+ *   G_j = tan(pi clamp(cutoff_hz[b,j], sample_rate/4096, 0.49 sample_rate) / sample_rate),  K_j = 1 / clamp(q[b,j], 0.1, 100)
+ *                                                                                        (float64, then rounded once to float32)
+ *   j = n / hop,  t = (n mod hop) / hop,  g = G_j + t (G_{j+1} - G_j),  k = K_j + t (K_{j+1} - K_j)          (float32 from here on)
+ *   a1 = 1 / (1 + g (g + k)),  a2 = g a1,  a3 = g a2
+ *   v3 = x[n] - ic2,  v1 = a1 ic1 + a2 v3,  v2 = ic2 + a2 ic1 + a3 v3,  ic1 <- 2 v1 - ic1,  ic2 <- 2 v2 - ic2
+ *   w = v2 | k v1 | x - k v1 - v2 | x - k v1  by mode,   y[n] = (1 - mix) x[n] + mix w
+ * A row is walked in tiles of dasp_tvfilter_tile() samples.
+ * Forward: states (NULL: not saved) receives dasp_tvfilter_state_floats(B * C, N) = rows * ceil(N / tile) * 2 floats, (ic1, ic2) before
+ * every tile - all the backward pass needs beyond x and the curves.  Backward: gx (NULL: not written), gcutoff, gq, gmix; scratch holds
+ * dasp_tvfilter_scratch_floats(B * C, N, hop) = rows * (2 F + 1) floats, the rows' sums per frame point, added over an item's channels
+ * in fp64 in a fixed order by a second launch. No atomics. y, states, gx, gcutoff, gq and gmix are bit-identical run to run.
+ * gcutoff and gq are exactly zero where the frame value was clamped.
+ * A null pointer (states in forward and gx apart), a non-positive size or hop, a mode outside 0 .. 3 or a sample rate that is not positive
+ * and finite: DASP_ERR_ARG (-1 from the queries); a hop that is no power of two from 8 to 2048, B * C >= 2^31 or B * F >= 2^37:
+ * DASP_ERR_UNSUPPORTED (-2 from the queries). All of it is checked before any launch.
+ * Non-finite input: a NaN or inf sample stays in the states - it reaches every later sample of its row. The clamps are comparisons,
+ * which a NaN passes: a NaN frame value j makes its item NaN from sample (j - 1) hop on; earlier samples and other items keep every bit. */
+int dasp_tvfilter_tile(void);
+long dasp_tvfilter_frames(long N, int hop);
+long dasp_tvfilter_state_floats(long rows, long N);
+long dasp_tvfilter_scratch_floats(long rows, long N, int hop);
+int dasp_tvfilter_forward(const float* x, const float* cutoff_hz, const float* q, const float* mix, float* y, float* states, int B, int C, long N,
+                          int hop, int mode, double sample_rate, void* stream);
+int dasp_tvfilter_backward(const float* x, const float* cutoff_hz, const float* q, const float* mix, const float* states, const float* gy, float* gx,
+                           float* gcutoff, float* gq, float* gmix, float* scratch, int B, int C, long N, int hop, int mode, double sample_rate,
+                           void* stream);
+
 /* resample: polyphase windowed-sinc sample-rate conversion by the reduced ratio orig : new_ = o : n, and its adjoint
  * (csrc/resample.hip; the definition is DESIGN.md 3.15, a restatement of torchaudio.functional.resample's published algorithm with
  * the taps exactly zero where the window's argument was clamped). x, gx (rows, N) fp32; y, gy (rows, M) fp32, M = ceil(n N / o):
