@@ -963,6 +963,67 @@ class FeedbackDelayFunction(FeedbackDelayKernels, torch.autograd.Function):
     which watches FeedbackDelayKernels."""
 
 
+class FdnReverbKernels:
+    """The two directions of fdn_reverb over the C ABI, as the forward / backward pair of a torch.autograd.Function:
+    y = (1 - mix) x + mix wet, wet the sum of K delay lines coupled through a Householder matrix and damped by one-pole low-passes
+    (dasp_fdn_forward / _backward, csrc/fdn.hip). decay_s, damping_hz, mix: bs values each; sample_rate: a float; delays: a tuple of K
+    ints; decorrelate: a bool. Saves x, the controls packed as (bs, 3) and, when a control needs a gradient, the K line signals v
+    (bs, chs, K, seq_len): the backward kernel recomputes r, w and wet from them. With only x needing one no v is written: gx depends
+    on the controls alone, and the backward call with v = NULL writes nothing else."""
+
+    @staticmethod
+    def forward(ctx, x, decay_s, damping_hz, mix, sample_rate, delays, decorrelate):
+        _lib.require_device(x, "x")
+        B, C, N = x.shape
+        ctls = (decay_s, damping_hz, mix)
+        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
+        ctx.cfg = (float(sample_rate), tuple(int(m) for m in delays), bool(decorrelate))
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            return torch.empty_like(x)
+        K = len(ctx.cfg[1])
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            ctl = torch.stack([c.detach().reshape(B).to(device=x.device, dtype=torch.float32) for c in ctls], dim=-1).contiguous()
+            y = torch.empty_like(x32)
+            ctx.saved_v = any(ctx.needs_input_grad[1:4])
+            v = torch.empty((B, C, K, N), dtype=torch.float32, device=x.device) if ctx.saved_v else None      # 4 K B per sample, only for the controls
+            call("dasp_fdn_forward", ptr(x32), ptr(ctl), (ctypes.c_int * K)(*ctx.cfg[1]), ptr(y), ptr(v), B, C, N, K, ctx.cfg[0], int(ctx.cfg[2]),
+                 stream())
+            if ctx.saved_v:
+                ctx.save_for_backward(x32, ctl, v)
+            elif ctx.needs_input_grad[0]:
+                ctx.save_for_backward(x32, ctl)
+        return y.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xd, cmeta = ctx.meta
+        if ctx.empty:
+            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 3))
+        sample_rate, delays, decorrelate = ctx.cfg
+        K = len(delays)
+        x32, ctl = ctx.saved_tensors[:2]
+        B, C, N = x32.shape
+        with torch.cuda.device(x32.device):
+            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # not written when x needs no gradient; the recurrence still runs
+            v = ctx.saved_tensors[2] if ctx.saved_v else None                     # None: gx alone, one launch, no control sums
+            gctl = torch.empty_like(ctl) if ctx.saved_v else None
+            partials = torch.empty(_lib.lib().dasp_fdn_partial_floats(B * C), dtype=torch.float32, device=x32.device) if ctx.saved_v else None
+            g32 = _f32c(gy)
+            call("dasp_fdn_backward", ptr(x32), ptr(ctl), (ctypes.c_int * K)(*delays), ptr(v), ptr(g32), ptr(gx), ptr(gctl), ptr(partials), B, C, N, K,
+                 sample_rate, int(decorrelate), stream())
+        gc = tuple(gctl[:, q].reshape(s).to(d) if need else None for q, ((d, s), need) in enumerate(zip(cmeta, ctx.needs_input_grad[1:4])))      # (need implies saved_v)
+        return (None if gx is None else gx.to(xd),) + gc + (None,) * 3
+
+
+class FdnReverbFunction(FdnReverbKernels, torch.autograd.Function):
+    """FdnReverbKernels bound to autograd. As for feedback_delay the pair lives in a plain class and this one defines no forward of its
+    own: the table of tests/autograd_contract_cases.py is closed, and this op's contract is checked by the same batteries from
+    tests/test_gpu_fdn_reverb.py, which watches FdnReverbKernels."""
+
+
 class PhaserKernels:
     """The two directions of phaser over the C ABI, as the forward / backward pair of a torch.autograd.Function:
     y = (1 - mix) x + mix s_K, s_K the output of K first-order all-pass stages whose shared coefficient a sine LFO sweeps

@@ -10,7 +10,7 @@ from . import signal as _signal
 from . import _mt19937
 from . import ops as _ops
 from . import _lib
-from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, FeedbackDelayFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
+from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, FdnReverbFunction, FeedbackDelayFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
                   PhaserFunction, ResampleFunction, StereoMixFunction, TVFILTER_MODES, TimeVaryingFilterFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
@@ -157,6 +157,48 @@ def feedback_delay(x: torch.Tensor, sample_rate: float, delay_ms: torch.Tensor, 
     require_fp32_ok(x, "feedback_delay")
     H = math.ceil(sr / 1000.0 * max_delay_ms)
     return FeedbackDelayFunction.apply(x, delay_ms, feedback, damping_hz, mix, sr, max_delay_ms, H)
+
+
+def fdn_reverb(x: torch.Tensor, sample_rate: float, decay_s: torch.Tensor, damping_hz: torch.Tensor, mix: torch.Tensor, delays,
+               decorrelate: bool = True):
+    """Feedback delay network reverb: K delay lines coupled through the Householder matrix I - (2/K) 1 1^T, each fed through a one-pole
+    low-pass (the damping), mixed with the dry signal. x (bs, chs, seq_len); decay_s, damping_hz and mix hold bs values each; delays is a
+    plain sequence of K ints, the line lengths m_k in samples (1 <= K <= 16, every m_k >= 1, repeats allowed; signal.fdn_delay_lengths
+    gives a sensible set), shared by the batch; decorrelate a plain bool. For item b, channel c and sample n, with every line empty
+    (zero) before sample 0:
+        T = clamp(decay_s, 0.01, 100);  g_k = 10^(-3 m_k / (sample_rate T))      (the low-frequency tail falls by 60 dB in T seconds)
+        a = exp(-2 pi max(damping_hz, 0) / sample_rate)                          (damping_hz = inf: a = 0, no filter in the loop)
+        r_k[n] = v_k[n - m_k];   u_k[n] = g_k r_k[n];   w_k[n] = x[n] + u_k[n] - (2/K) sum_j u_j[n];   v_k[n] = (1 - a) w_k[n] + a v_k[n-1]
+        wet[n] = K^(-1/2) sum_k s_ck r_k[n],  s_ck = (-1)^(k c) if decorrelate else 1;   y[n] = (1 - mix) x[n] + mix wet[n]
+    Every g_k < 1, the matrix is orthogonal and the one-pole's gain is at most 1: the loop is stable for every finite input. With
+    decorrelate the odd channels sum the lines with alternating signs, so that a stereo pair gets two different tails from one set of
+    lines; channel 0 is the same with and without it. g_k and a are float64 in the kernel and rounded once, everything after them
+    float32 (csrc/fdn.hip). The op works on whole tensors, not on a stream.
+    Differentiable in x, decay_s, damping_hz and mix, once (no double backward). The decay_s gradient is zero where decay_s was clamped,
+    the damping_hz gradient zero where damping_hz < 0 and at inf. A NaN control makes its own item NaN, gradients included, and no other.
+    One workgroup walks one (item, channel) row in steps of min(shortest line, 1024) samples with all K rings in LDS: the op cannot fill
+    the chip at training batch sizes, short lines are slow, and sum(delays) is at most 38912 - 1024 (K + 1) samples (29696 at K = 8:
+    0.67 s at 44.1 kHz; 21504 at K = 16). A gradient for a control keeps the K line signals: 4 K bytes per sample.
+    Out of scope: fractional or modulated line lengths, learnable or non-Householder matrices, per-line absorption filters matched to
+    the line length (a frequency-dependent RT60 target), per-line input and output gains, an early-reflection section, checkpointing
+    instead of the saved line signals, several rows per workgroup for short lines, float64, and a torch.ops.dasp op.
+    A wrong control count raises RuntimeError naming the control; delays that are not 1 - 16 ints >= 1 (bools refused) or a sample_rate
+    that is not positive and finite ValueError, before anything touches the device; delays beyond the sum limit DaspHipError
+    (unsupported configuration)."""
+    bs, chs, seq_len = x.size()
+    for name, c in (("decay_s", decay_s), ("damping_hz", damping_hz), ("mix", mix)):
+        if c.numel() != bs:
+            raise RuntimeError(f"{name}: shape '[{bs}]' is invalid for input of size {c.numel()}")
+    try:
+        sr = float(sample_rate)
+    except (TypeError, ValueError):
+        sr = float("nan")
+    if not (sr > 0.0 and sr != float("inf")):
+        raise ValueError(f"fdn_reverb: finite sample_rate > 0, got {sample_rate}")
+    lines = _signal.check_fdn_delays(delays)
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "fdn_reverb")
+    return FdnReverbFunction.apply(x, decay_s, damping_hz, mix, sr, lines, bool(decorrelate))
 
 
 def phaser(x: torch.Tensor, sample_rate: float, rate_hz: torch.Tensor, center_hz: torch.Tensor, depth: torch.Tensor, phase: torch.Tensor,

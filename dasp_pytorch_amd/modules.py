@@ -384,6 +384,21 @@ class FeedbackDelay(Processor):
                              "damping_hz": (min_damping_hz, max_damping_hz), "mix": (min_mix, max_mix)}
 
 
+class FDNReverb(Processor):
+    """Feedback delay network reverb (functional.fdn_reverb). The parameters decay_s, damping_hz and mix are the functional's own
+    argument names; the line lengths (delays=None: signal.fdn_delay_lengths(sample_rate), eight primes from 23 to 83 ms) and decorrelate
+    are fixed at construction."""
+
+    def __init__(self, sample_rate: int, delays=None, decorrelate: bool = True, min_decay_s: float = 0.1, max_decay_s: float = 10.0,
+                 min_damping_hz: float = 500.0, max_damping_hz: float = 20000.0, min_mix: float = 0.0, max_mix: float = 1.0):
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.delays = S.check_fdn_delays(S.fdn_delay_lengths(sample_rate) if delays is None else delays)
+        self.decorrelate = bool(decorrelate)
+        self.process_fn = functools.partial(F.fdn_reverb, delays=self.delays, decorrelate=self.decorrelate)
+        self.param_ranges = {"decay_s": (min_decay_s, max_decay_s), "damping_hz": (min_damping_hz, max_damping_hz), "mix": (min_mix, max_mix)}
+
+
 class Phaser(Processor):
     """Phaser (functional.phaser) with `stages` all-pass stages. The parameters rate_hz, center_hz, depth, phase and mix are the
     functional's own argument names; stages and stereo_spread are fixed at construction."""

@@ -79,6 +79,66 @@ def control_frames(seq_len: int, hop: int):
     return -(-int(seq_len) // int(hop)) + 1
 
 
+FDN_MAX_LINES = 16
+
+
+def check_fdn_delays(delays):
+    """The line lengths of functional.fdn_reverb as a tuple of ints: ValueError unless they are a sequence of 1 to 16 ints >= 1 (bools
+    and tensors refused; repeats allowed)."""
+    if isinstance(delays, (str, bytes, torch.Tensor, np.ndarray)) or not isinstance(delays, (list, tuple, range)):
+        raise ValueError(f"delays must be a list or tuple of 1 to {FDN_MAX_LINES} ints >= 1, got {delays!r}")
+    if not 1 <= len(delays) <= FDN_MAX_LINES:
+        raise ValueError(f"delays must hold 1 to {FDN_MAX_LINES} line lengths, got {len(delays)}")
+    for m in delays:
+        if isinstance(m, bool) or not isinstance(m, numbers.Integral) or not 1 <= m < 2 ** 31:
+            raise ValueError(f"delays must be ints >= 1 (samples), got {m!r}")
+    return tuple(int(m) for m in delays)
+
+
+def _is_prime(n):
+    if n < 2:
+        return False
+    d = 2
+    while d * d <= n:
+        if n % d == 0:
+            return False
+        d += 1
+    return True
+
+
+def fdn_delay_lengths(sample_rate: float, lines: int = 8, shortest_ms: float = 23.0, longest_ms: float = 83.0):
+    """A default delay set for functional.fdn_reverb: `lines` distinct primes, in samples and in ascending order. Point k of a logarithmic
+    spacing from sample_rate/1000 shortest_ms to sample_rate/1000 longest_ms (the shortest alone when lines = 1) goes to the prime
+    nearest to it (the smaller on a tie), and on to the next larger free prime where that one is taken. Primes share no factor, so the
+    lines' echoes do not pile up on common multiples. Pure Python, no device. ValueError for a sample rate that is not positive and
+    finite, lines outside 1 .. 16, or lengths that are not 0 < shortest_ms <= longest_ms < inf."""
+    try:
+        sr, lo, hi = float(sample_rate), float(shortest_ms), float(longest_ms)
+    except (TypeError, ValueError):
+        raise ValueError(f"fdn_delay_lengths: numbers expected, got {sample_rate!r}, {shortest_ms!r}, {longest_ms!r}") from None
+    if not (0.0 < sr < float("inf")):
+        raise ValueError(f"sample_rate must be positive and finite, got {sample_rate!r}")
+    if isinstance(lines, bool) or not isinstance(lines, numbers.Integral) or not 1 <= lines <= FDN_MAX_LINES:
+        raise ValueError(f"lines must be an integer from 1 to {FDN_MAX_LINES}, got {lines!r}")
+    if not (0.0 < lo <= hi < float("inf")):
+        raise ValueError(f"0 < shortest_ms <= longest_ms < inf expected, got {shortest_ms!r}, {longest_ms!r}")
+    a, b = sr / 1000.0 * lo, sr / 1000.0 * hi
+    taken = []
+    for k in range(lines):
+        point = a if lines == 1 else a * (b / a) ** (k / (lines - 1))
+        below = max(int(point), 2)
+        while not _is_prime(below):
+            below -= 1
+        above = max(int(point), 2)
+        while not _is_prime(above) or above < point:
+            above += 1
+        p = below if point - below <= above - point else above
+        while p in taken or not _is_prime(p):
+            p += 1
+        taken.append(p)
+    return sorted(taken)
+
+
 check_resampling = _resample_design.check_resampling
 
 

@@ -475,6 +475,39 @@ int dasp_fbdelay_forward(const float* x, const float* ctl, float* y, float* v, i
 int dasp_fbdelay_backward(const float* x, const float* ctl, const float* v, const float* gy, float* gx, float* gctl, float* partials, int B,
                           int C, long N, int H, double sample_rate, double max_delay_ms, void* stream);
 
+/* fdn_reverb: feedback delay network - K delay lines of whole lengths coupled through the Householder matrix I - (2/K) 1 1^T, each fed
+ * through a one-pole low-pass, mixed with the dry signal; a recurrence evaluated in place, one workgroup per (b, c) row (csrc/fdn.hip).
+ * x, y, gy, gx (B, C, N) fp32; v (B, C, K, N) fp32; ctl, gctl (B, 3) fp32: decay_s, damping_hz, mix. delays: K ints in HOST memory, the
+ * line lengths m_k >= 1 in samples (repeats allowed), read before the call returns. decorrelate: 0 or 1.  For item b, channel c, sample
+ * n, with every v_k zero before sample 0:
+ *   T = clamp(decay_s, 0.01, 100),  g_k = 10^(-3 m_k / (sample_rate T)),  a = exp(-2 pi max(damping_hz, 0) / sample_rate)   (+inf: a = 0)
+ *   r_k[n] = v_k[n - m_k],  u_k[n] = g_k r_k[n],  w_k[n] = x[n] + u_k[n] - (2/K) sum_j u_j[n],  v_k[n] = (1 - a) w_k[n] + a v_k[n - 1]
+ *   wet[n] = K^(-1/2) sum_k s_ck r_k[n],  s_ck = (-1)^(k c) if decorrelate else 1,   y[n] = (1 - mix) x[n] + mix wet[n]
+ * g_k and a are float64 in the kernels, rounded once to float32; everything after them is float32.
+ * 1 <= K <= dasp_fdn_max_lines() = 16 and sum_k m_k <= dasp_fdn_max_delay_sum(K): the K rings of m_k + S floats and S staged words share
+ * a workgroup's LDS. A row is walked in sequential steps of S = dasp_fdn_block(K, min_k m_k) = min(min_k m_k, 1024) samples.
+ * Forward: v (NULL: not saved) receives the K line signals, which the backward pass reads.  Backward: gx (NULL: not written), gctl; r, w
+ * and wet are recomputed from v; partials is scratch of dasp_fdn_partial_floats(B * C) = 18 floats per row, summed over an item's
+ * channels in fp64 in a fixed order by a second launch. No atomics. y, v, gx and gctl are bit-identical run to run. The decay_s gradient
+ * is zero where decay_s was clamped, the damping_hz gradient zero where damping_hz < 0 and at +inf. Backward with v = NULL writes gx
+ * alone (it depends on no line signal), the same bits, in one launch: gctl and partials are not touched and may be NULL, gx may not.
+ * dasp_fdn_prepare() raises the kernels' dynamic-LDS limit on the current device; the binding calls it once when it loads the library,
+ * and the first call on a device that was not prepared does it itself.
+ * A null pointer (v in forward and gx apart), a non-positive size, K outside 1 .. 16, an m_k < 1, a sample rate that is not positive and
+ * finite: DASP_ERR_ARG (-1 from the queries); sum_k m_k above its maximum (K * shortest above it, for dasp_fdn_block) or B * C >= 2^31:
+ * DASP_ERR_UNSUPPORTED (-2 from the queries). All of it is checked before any launch.
+ * Non-finite input: a NaN or inf sample stays in the lines from then on. A NaN decay_s or damping_hz passes its clamp: the item's y, gx
+ * and control gradients are NaN. No sample and no control forms an address. Other items keep every bit. */
+int dasp_fdn_max_lines(void);
+int dasp_fdn_block(int K, long shortest);
+long dasp_fdn_max_delay_sum(int K);
+long dasp_fdn_partial_floats(long rows);
+int dasp_fdn_prepare(void);
+int dasp_fdn_forward(const float* x, const float* ctl, const int* delays, float* y, float* v, int B, int C, long N, int K, double sample_rate,
+                     int decorrelate, void* stream);
+int dasp_fdn_backward(const float* x, const float* ctl, const int* delays, const float* v, const float* gy, float* gx, float* gctl,
+                      float* partials, int B, int C, long N, int K, double sample_rate, int decorrelate, void* stream);
+
 /* phaser: `stages` first-order all-pass sections in series whose shared coefficient a sine LFO sweeps, mixed with the dry signal; a
  * recurrence whose coefficient changes with every sample, evaluated as a scan, one workgroup per (b, c) row (csrc/phaser.hip).
  * x, y, gy, gx (B, C, N) fp32; ctl, gctl (B, 5) fp32: rate_hz, center_hz, depth (octaves), phase (turns), mix.  For item b, channel c,
