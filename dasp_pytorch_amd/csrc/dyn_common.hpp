@@ -22,8 +22,16 @@ __device__ __forceinline__ float gain_computer(float x_db, const DynItem& it, fl
     const bool in_knee = (x_db >= lo) && (x_db <= hi) && (it.knee > 0.f);
     // Outside the knee and the active branch x_sc = x_db and g_c = x_sc - x_db (functional.py:369): 0 for a finite level, NaN for a NaN
     // level (every comparison is false for it) and for +inf (inf - inf), so that a non-finite sample reaches the smoothing state as in the
-    // reference. Needs IEEE NaN semantics from the compiler: build.py HIPCC_FLAGS.
-    float g = x_db - x_db;
+    // reference. Needs IEEE NaN semantics from the compiler: build.py HIPCC_FLAGS. And no contraction: the callers pass the product
+    // DB_PER_LOG2 * log2f(..), and with -ffp-contract=fast (hipcc's default) the compressor's branch of this difference was fused into
+    // fma(DB_PER_LOG2, log2f(..), -x_db), the rounding error of that product (up to 1.9e-6 dB) instead of 0: the gain below the knee
+    // was not exactly the make-up gain, and the attack_ms gradient there 1e-8 of the make-up column instead of exactly 0
+    // (tests/test_gpu_dynamics_exact.py, compressor below the knee).
+    float g;
+    {
+#pragma clang fp contract(off)
+        g = x_db - x_db;
+    }
     if (D) { d_x = d_t = d_r = d_w = 0.f; }
     if (MODE == 0) {   // compressor, functional.py:350-369
         const float sl = it.inv_ratio - 1.f;   // 1/R - 1

@@ -8,10 +8,10 @@
 // textbook downward expander with the same structure (no reference behaviour to match).
 //
 // Work decomposition: batch item -> one workgroup of W waves (the side chain is shared by the
-// item's channels); tile = 1024 consecutive samples -> one wave, tiles round-robin; inside a tile
-// the samples stay in the *coalesced* layout (sub-tile j = 256 samples, lane l holds 4 consecutive
+// item's channels); tile = 512 consecutive samples (DY_TS) -> one wave, tiles round-robin; inside a tile
+// the samples stay in the *coalesced* layout (2 sub-tiles j of 256 samples, lane l holds 4 consecutive
 // samples 256 j + 4 l ..) so there is no LDS transpose: each lane runs its 4 samples, a DPP scan
-// (row_shr 1/2/4/8 + row_bcast 15/31, powers of alpha) joins the 64 lanes, the 4 sub-tiles chain
+// (row_shr 1/2/4/8 + row_bcast 15/31, powers of alpha) joins the 64 lanes, the 2 sub-tiles chain
 // through one FMA each, and the tile carry travels wave -> wave through an LDS mailbox.
 // HBM-bound: forward 8 B per channel-sample (read x, write y), backward 12 B (x, gy, gx).
 #include "common.hpp"

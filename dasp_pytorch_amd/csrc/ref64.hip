@@ -113,7 +113,11 @@ template <int MODE, bool D>
 __device__ __forceinline__ double gain_computer64(double x_db, const Dyn64& it, double& d_x, double& d_t, double& d_r, double& d_w) {
     const double half = 0.5 * it.knee, lo = it.thr - half, hi = it.thr + half;
     const bool in_knee = (x_db >= lo) && (x_db <= hi) && (it.knee > 0.0);
-    double g = x_db - x_db;                    // 0, and NaN for a NaN level: dyn_common.hpp gain_computer
+    double g;                                  // 0, and NaN for a NaN level - never fused with the product behind x_db: dyn_common.hpp gain_computer
+    {
+#pragma clang fp contract(off)
+        g = x_db - x_db;
+    }
     if (D) { d_x = d_t = d_r = d_w = 0.0; }
     if (MODE == 0) {
         const double ir = 1.0 / it.ratio, sl = ir - 1.0;

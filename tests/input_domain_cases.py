@@ -20,7 +20,7 @@ the CPU against central differences of it, and its compressor mode against orc.c
 Kinds of bound (d = got - ref, per array):
   "abs1" max|d| <  b * max(1, max|ref|)          "max"  max|d| <= b * max|ref|
   "peak" per item: max|d| < b * max|ref item|     "col"  per column j of a (B, K) matrix: max|d[:, j]| <= b * max|ref[:, j]|
-  "fd"   as "col" plus 1e-6 (tests/test_gpu_dynamics.py:152)
+  "fd"   as "col" plus 1e-6 (the form of the central-difference check in tests/test_gpu_dynamics.py; no case of the table uses it now)
 Where the reference is exactly zero there is no peak to divide by: y must then be exactly zero and a gradient within b * max|gy|.
 Every comparison carries an absolute floor of FLT_MIN = 1.18e-38: the outputs are float32, and what lies below its smallest normal
 number (the expander's gain on near-silence is thousands of dB down) has no relative precision to hold anything to. The columns of a
@@ -166,10 +166,15 @@ def lfilter_exact(x, b, a, gy):
     return y, gx, gb, ga
 
 
-def dynamics_exact(mode, x, sr, p, gy, look=0, eps=1e-8):
+def dynamics_exact(mode, x, sr, p, gy, look=0, eps=1e-8, terms=False, scale=None):
     """compressor (mode 0) / expander (mode 1) with the one-pole smoother as a true recursion, and the analytic adjoint: x (B, C, N),
     p (B, 6) columns DYN_KEYS -> y, gx, gp (B, 6). Conventions of orc.compressor_vjp: no gradient through the clamp below eps,
-    sign(0) = 0, release_ms without a path to the output. Static curves: orc._compressor_core / orc.expander."""
+    sign(0) = 0, release_ms without a path to the output. Static curves: orc._compressor_core / orc.expander. Any look >= 0: from
+    look >= N on the delayed signal, and with it the output and every gradient, is zero.
+    terms: also return (B, 6) sums of the ABSOLUTE per-sample terms behind each control gradient (their ratio to |gp| is the cancellation
+    of that column's sum) and (B,) peaks of the sum of absolute terms behind grad x.
+    scale: {"d_thr" | "d_rat" | "d_knee" | "d_xdb": factor} multiplies one partial derivative of the static curve - a deliberately wrong
+    adjoint, for tests that measure how far a wrong formula moves what they compare."""
     x = np.asarray(x, np.float64); gy = np.asarray(gy, np.float64); p = np.asarray(p, np.float64)
     B, C, N = x.shape
     col = lambda j: p[:, j].reshape(B, 1, 1)
@@ -199,6 +204,10 @@ def dynamics_exact(mode, x, sr, p, gy, look=0, eps=1e-8):
             d_thr = np.where(act, 1 - rat, np.where(ik, -(1 - rat) * qk / knee, 0.0))
             d_rat = np.where(act, x_db - thr, np.where(ik, -(qk ** 2) / (2 * knee), 0.0))
             d_knee = np.where(ik, (1 - rat) * (-qk / (2 * knee) - qk ** 2 / (2 * knee ** 2)), 0.0)
+    if scale:
+        assert set(scale) <= {"d_thr", "d_rat", "d_knee", "d_xdb"}, scale
+        d_thr, d_rat = d_thr * scale.get("d_thr", 1.0), d_rat * scale.get("d_rat", 1.0)
+        d_knee, d_xdb = d_knee * scale.get("d_knee", 1.0), d_xdb * scale.get("d_xdb", 1.0)
     g_c = x_sc - x_db
     g = np.empty_like(g_c); g_gc = np.empty_like(g_c); dg_da = np.empty_like(g_c)
     x_d = x
@@ -214,7 +223,8 @@ def dynamics_exact(mode, x, sr, p, gy, look=0, eps=1e-8):
     gx = gxd.copy()
     if look > 0:
         gx = np.zeros_like(gxd)
-        gx[:, :, :N - look] = gxd[:, :, look:]
+        if look < N:
+            gx[:, :, :N - look] = gxd[:, :, look:]
     ggs = np.sum(gy * x_d, 1, keepdims=True) * lin * (math.log(10.0) / 20.0)
     for b in range(B):
         a = float(alpha[b, 0, 0])
@@ -230,7 +240,25 @@ def dynamics_exact(mode, x, sr, p, gy, look=0, eps=1e-8):
     gp[:, 4] = np.sum(g_gc * d_knee, (1, 2))
     gp[:, 5] = ggs.sum((1, 2))
     g_side = np.where(np.abs(s) >= eps, g_gc * d_xdb * (20.0 / math.log(10.0)) * np.sign(s) / mag, 0.0)
-    return y, gx + g_side, gp
+    if not terms:
+        return y, gx + g_side, gp
+    absum = np.zeros((B, 6))
+    absum[:, 0] = np.abs(g_gc * d_thr).sum((1, 2))
+    absum[:, 1] = np.abs(g_gc * d_rat).sum((1, 2))
+    absum[:, 2] = np.abs(ggs * dg_da).sum((1, 2)) * np.abs(a1 * math.log(9.0) / (n1 * n1) * (sr / 1e3))
+    absum[:, 4] = np.abs(g_gc * d_knee).sum((1, 2))
+    absum[:, 5] = np.abs(ggs).sum((1, 2))
+    # ... and behind grad x: per item the peak over the samples of |gy| lin + (the adjoint smoother over sum_c |gy x_d| lin) |d_xdb| / |s|.
+    # The adjoint state is a running sum of terms that carry the sign of gy; at a sample where |s| is tiny (1 / |s| makes it the peak of
+    # grad x) that sum can have cancelled to a small part of its terms
+    gabs = np.empty_like(g_gc)
+    ggs_abs = np.sum(np.abs(gy * x_d), 1, keepdims=True) * lin * (math.log(10.0) / 20.0)
+    for b in range(B):
+        a = float(alpha[b, 0, 0])
+        gabs[b] = _ss.lfilter([1 - a], [1.0, -a], ggs_abs[b][..., ::-1], axis=-1)[..., ::-1]
+    side_abs = np.where(np.abs(s) >= eps, gabs * np.abs(d_xdb) * (20.0 / math.log(10.0)) / mag, 0.0)
+    gx_abs = (np.abs(gx) + side_abs).reshape(B, -1).max(1)
+    return y, gx + g_side, gp, absum, gx_abs
 
 
 def dyn_pad_len(N, sr, attack_ms):
@@ -456,12 +484,19 @@ def _ref_exp(sr, a, gy):
 
 # y and grad x 2e-5 L-inf / peak per item, the six control gradients 1e-4 of the column maximum: tests/test_gpu_dynamics.py:63, 68 (CTL_TOL)
 COMP_TOL = dict(y=("peak", 2e-5), g_x=("peak", 2e-5), g_params=("col", 1e-4))
-# the expander: y 2e-5 (:147), control gradients 2e-3 of the column maximum + 1e-6 (:152). Its grad x has no bound against an oracle in the
-# existing suite (a directional derivative at 2e-3, :162); it comes from mode 1 of the compressor's kernels, and is held to the bound of
+# the expander: y 2e-5 (tests/test_gpu_dynamics.py::test_expander_design_model_and_gradcheck). Control gradients: EXP_CTL_TOL of the column
+# maximum against the analytic adjoint dynamics_exact(1) - no longer the ten times wider bound of that test's central
+# differences of a kinked curve. Its grad x comes from mode 1 of the compressor's kernels, and is held to the bound of
 # their grad x against the oracle on random draws over the modules' whole control ranges, 5e-5 (:206, ratio up to 20 - the draws used
 # here; the goldens' 2e-5 was measured at 2.4e-5 for one segmented item at 32 kHz: an expander's gain in dB swings (ratio - 1) times as
 # far as a compressor's, and the dB -> linear map amplifies float32 rounding by ln10 / 20 x |gain in dB|, tests/test_gpu_dynamics.py:4-7)
-EXP_TOL = dict(y=("peak", 2e-5), g_x=("peak", 5e-5), g_params=("fd", 2e-3))
+# EXP_CTL_TOL = 4 x the worst column error of the 24 float32 expander cases of tests/test_gpu_dynamics_exact.py on an MI355X, 4.69e-5
+# (profiles/r23/dynamics_exact/parity.jsonl; the compressor's 1e-4 would have been adopted at <= 2.5e-5). The worst column is attack_ms, on
+# the knee-region case (3,2,4612): the kernels form it as sum r[n] (g[n-1] - g_c[n]), whose terms cancel because the smoothed gain g tracks
+# g_c; a plain sequential float32 evaluation of that sum in numpy is 7.1e-5 off on the same inputs (compressor: 4.6e-5, kernels 3.2e-5).
+# Next: the make-up column at 4.4e-5 on a speech-like signal with a Gaussian upstream gradient, where that column cancels 1153-fold.
+EXP_CTL_TOL = 1.9e-4
+EXP_TOL = dict(y=("peak", 2e-5), g_x=("peak", 5e-5), g_params=("col", EXP_CTL_TOL))
 
 
 def _build_widener(rng, B, C, N, sr):

@@ -1,5 +1,6 @@
 """GPU parity of compressor (vs reference-generated goldens and the numpy oracle) and expander
-(reference stub -> parity unpinned: checked against the fp64 design model and finite differences).
+(reference stub -> parity unpinned: checked against the fp64 design model, finite differences of it and its analytic adjoint
+tests/input_domain_cases.py::dynamics_exact; the sharp comparisons by region of the static curve are in tests/test_gpu_dynamics_exact.py).
 
 Tolerances (L-inf / peak per batch item): y and grad_x 2e-5 (north_star bar 1e-4; the dB->linear
 map amplifies fp32 log2/exp2 rounding by ~ln10/20*|gain dB|, the reference's own fp32 run sits at
@@ -12,6 +13,8 @@ import torch
 from dasp_pytorch_amd import config
 
 from oracle import dasp_oracle as orc
+from tests import dynamics_exact_cases as dx
+from tests import input_domain_cases as idc
 from tests.util import linf_peak, load_golden, record
 
 pytestmark = pytest.mark.gpu
@@ -105,6 +108,16 @@ def test_compressor_shapes_vs_oracle(D, B, C, N, look):
         g = one_pole_ref(c["g_c"][:, 0], c["alpha"][:, 0, 0])[:, None]
         yo = c["x_d"] * 10 ** ((g + c["mk"]) / 20)
         assert np.abs(y - yo).max() < 2e-5 * max(1.0, np.abs(yo).max())
+        # ... and the analytic adjoint of that recursion for grad x and the six control gradients, at the long branch's bounds (these
+        # shapes take the backward kernel's register-staged variant: N % 4 != 0, C > 2 or look > 0)
+        ye, gxo, gpo = idc.dynamics_exact(0, x, SR, pd, w, look)
+        assert np.abs(ye - yo).max() < 1e-12 * max(1.0, np.abs(yo).max())
+        egx = linf_peak(gx, gxo)
+        eg = [np.abs(gp[:, j] - gpo[:, j]).max() / max(np.abs(gpo[:, j]).max(), 1e-30) for j in range(6)]
+        record(f"compressor_shapes[{B},{C},{N},{look}]", y=linf_peak(y, yo).max(), gx=egx.max(), gctl=eg)
+        assert np.all(egx < 2e-5), egx
+        for j in range(6):
+            assert eg[j] <= CTL_TOL_SHAPES, (KEYS[j], gp[:, j], gpo[:, j])
     assert np.isfinite(y).all() and np.isfinite(gx).all() and np.isfinite(gp).all()
 
 
@@ -151,6 +164,13 @@ def test_expander_design_model_and_gradcheck(D):
         fd = ((f(x, pp) - f(x, pm)) * w).sum((1, 2)) / (2 * h)
         assert np.abs(gp[:, j] - fd).max() <= 2e-3 * np.abs(fd).max() + 1e-6, (KEYS[j], gp[:, j], fd)
     assert np.all(gp[:, 3] == 0)
+    # ... and against the analytic adjoint of the model (tests/dynamics_exact_cases.py: the bound that does not come from differences)
+    ye, gxo, gpo = idc.dynamics_exact(1, x, SR, pd, w)
+    assert np.abs(ye - yo).max() < 1e-12 * np.abs(yo).max()
+    eg = dx.col_errors(gp, gpo)
+    record("expander_design_model_vs_exact_adjoint", y=linf_peak(y, yo).max(), gx=linf_peak(gx, gxo).max(), gctl=eg)
+    assert linf_peak(gx, gxo).max() < dx.GX_TOL[1]
+    assert eg.max() <= dx.EXP_CTL_TOL, eg
     # grad_x by directional derivative, on a signal whose side chain stays away from zero (d log|s| / ds = 1/s makes
     # finite differences meaningless next to zero crossings, and the expander is active exactly at low levels)
     sign = rng.choice([-1.0, 1.0], size=(B, 1, N))
@@ -255,6 +275,22 @@ def test_config3_full_size_expander(D, monkeypatch):
     assert ey.max() < 2e-5, ey
     assert max(eg) <= 2e-3, eg                      # (the bound of test_expander_design_model_and_gradcheck: finite differences of a kinked curve)
     assert np.all(gp[:, 3] == 0)
+    # ... and the same items against the analytic adjoint of the model: grad x and the control gradients without finite differences
+    # The control gradients at the bound of tests/test_gpu_dynamics_exact.py. grad x relative to the peak of the sum of ABSOLUTE terms
+    # behind it, not to its own peak: with uniform noise in two channels the side chain passes within 1e-6 of zero somewhere in 262144
+    # samples, 1 / |s| makes that sample the peak of grad x, and what stands there is the adjoint smoother's running sum of terms that
+    # carry the sign of the Gaussian upstream gradient - cancelled to a few per cent of its terms. A float32 sum has no digits below
+    # 6e-8 of its terms: a plain sequential float32 evaluation of the same formulas in numpy is 1.2e-4 and 6.9e-5 of the peak off on
+    # the controls of items 0 and 1 (the slowest attacks at the largest gain swings) where y agrees to 4e-6; the kernels measure
+    # 9.5e-5 and 5.4e-5 there and <= 5e-6 on the other six. Relative to the terms it is the bound of EXP_TOL again.
+    ye, gxo, gpo, _, gx_abs = idc.dynamics_exact(1, xs, SR, ps, ws, terms=True)
+    assert np.abs(ye - yo).max() < 1e-12 * np.abs(yo).max()
+    dgx = np.abs(gx1[idx].cpu().numpy() - gxo).reshape(len(idx), -1).max(1)
+    egc = dx.col_errors(gp, gpo)
+    record("expander_config3_full_size_sampled_items_vs_exact_adjoint", gx_of_own_peak=linf_peak(gx1[idx].cpu().numpy(), gxo).max(),
+           gx_of_peak_of_terms=(dgx / gx_abs).max(), gctl=egc)
+    assert np.all(dgx < dx.GX_TOL[1] * gx_abs), (dgx / gx_abs)
+    assert egc.max() <= dx.EXP_CTL_TOL, egc
 
 
 @pytest.mark.parametrize("B,C,N,look,tiles,mode", [(2, 2, 40000, 0, None, "compressor"), (3, 1, 65536, 0, 32, "compressor"), (1, 2, 262144, 0, None, "compressor"),
