@@ -13,7 +13,10 @@ tests/input_domain_cases.py:
 Bounds are those of each op's existing shapes-vs-oracle test (restated in the table with their lines). Where the order of a float sum is
 documented as not fixed, "equal" means the bound of the existing test that says so: the control gradients of the segmented dynamics
 (tests/test_gpu_dynamics.py:336, 1e-4 of the largest entry) and the band-split reverb's float atomics (tests/test_gpu_reverb.py:184-185:
-y / grad x 2e-6, control gradients 1e-5)."""
+y / grad x 2e-6, control gradients 1e-5). The two fused passes also run with the expander's curve (chain_forward_expander,
+chain_forward_saving_expander): their references compare a quantity with the float64 chain only where the float32 rounding of the EQ's
+output in front of the expander leaves that possible (tests/input_domain_cases.py, beside EQ_PROBE); every bit-equality, NaN-propagation
+and exact-zero part runs for them as for the others."""
 import copy
 import functools
 
@@ -406,7 +409,8 @@ def test_b_poisoned_item_leaves_its_neighbours_alone(D, monkeypatch, case):
 
 def _silence_applies(case, kind):
     if kind == "cancel":
-        return case.name in ("compressor", "compressor_look3", "expander", "stereo_widener", "chain_forward", "chain_forward_saving")
+        return case.name in ("compressor", "compressor_look3", "expander", "stereo_widener", "chain_forward", "chain_forward_saving",
+                             "chain_forward_expander", "chain_forward_saving_expander")
     return True
 
 
@@ -473,7 +477,8 @@ def test_d_biquad_design_matches_reference_at_every_rate(D, dtype):
             assert linf_peak(gp, g[f"sr{sr}_{t}_g64"]).max() < 1e-5, (sr, t)
 
 
-DYN_RATE_CASES = ["compressor", "compressor_look3", "expander", "chain_forward", "chain_forward_saving"]
+DYN_RATE_CASES = ["compressor", "compressor_look3", "expander", "chain_forward", "chain_forward_saving", "chain_forward_expander",
+                  "chain_forward_saving_expander"]
 
 
 def _dyn_rate_case(case, sr, B, C, N):
