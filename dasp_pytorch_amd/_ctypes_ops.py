@@ -1024,6 +1024,61 @@ class FdnReverbFunction(FdnReverbKernels, torch.autograd.Function):
     tests/test_gpu_fdn_reverb.py, which watches FdnReverbKernels."""
 
 
+class LimiterKernels:
+    """The two directions of limiter over the C ABI, as the forward / backward pair of a torch.autograd.Function: y = x G, G the gain of
+    a look-ahead brickwall limiter with linked channels (dasp_limiter_forward / _backward, csrc/limiter.hip). threshold_db, release_ms:
+    bs values each; sample_rate, eps: floats; lookahead: L in samples. Saves x, the controls packed as (bs, 2) and, when anything needs
+    a gradient, G and the winning sample of every gain value, (bs, seq_len) each: 8 bytes per sample of an item. Nothing otherwise."""
+
+    @staticmethod
+    def forward(ctx, x, threshold_db, release_ms, sample_rate, lookahead, eps):
+        _lib.require_device(x, "x")
+        B, C, N = x.shape
+        ctls = (threshold_db, release_ms)
+        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
+        ctx.cfg = (float(sample_rate), int(lookahead), float(eps))
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            return torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            ctl = torch.stack([c.detach().reshape(B).to(device=x.device, dtype=torch.float32) for c in ctls], dim=-1).contiguous()
+            y = torch.empty_like(x32)
+            gain = winner = None
+            if any(ctx.needs_input_grad[:3]):
+                gain = torch.empty((B, N), dtype=torch.float32, device=x.device)
+                winner = torch.empty((B, N), dtype=torch.int32, device=x.device)
+            call("dasp_limiter_forward", ptr(x32), ptr(ctl), ptr(y), ptr(gain), ptr(winner), B, C, N, ctx.cfg[1], ctx.cfg[0], ctx.cfg[2], stream())
+            if gain is not None:
+                ctx.save_for_backward(x32, ctl, gain, winner)
+        return y.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xd, cmeta = ctx.meta
+        if ctx.empty:
+            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 3))
+        sample_rate, lookahead, eps = ctx.cfg
+        x32, ctl, gain, winner = ctx.saved_tensors
+        B, C, N = x32.shape
+        with torch.cuda.device(x32.device):
+            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # not written when x needs no gradient; the scans still run
+            gctl = torch.empty_like(ctl)
+            scratch = torch.empty(_lib.lib().dasp_limiter_partial_floats(B, N), dtype=torch.float32, device=x32.device)
+            g32 = _f32c(gy)
+            call("dasp_limiter_backward", ptr(x32), ptr(ctl), ptr(gain), ptr(winner), ptr(g32), ptr(gx), ptr(gctl), ptr(scratch), B, C, N, lookahead,
+                 sample_rate, eps, stream())
+        gc = tuple(gctl[:, q].reshape(s).to(d) if need else None for q, ((d, s), need) in enumerate(zip(cmeta, ctx.needs_input_grad[1:3])))
+        return (None if gx is None else gx.to(xd),) + gc + (None,) * 3
+
+
+class LimiterFunction(LimiterKernels, torch.autograd.Function):
+    """LimiterKernels bound to autograd. As for feedback_delay the pair lives in a plain class and this one defines no forward of its own:
+    the table of tests/autograd_contract_cases.py is closed, and this op's contract is checked by the same batteries from
+    tests/test_gpu_limiter.py, which watches LimiterKernels."""
+
+
 class PhaserKernels:
     """The two directions of phaser over the C ABI, as the forward / backward pair of a torch.autograd.Function:
     y = (1 - mix) x + mix s_K, s_K the output of K first-order all-pass stages whose shared coefficient a sine LFO sweeps

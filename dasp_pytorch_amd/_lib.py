@@ -107,6 +107,13 @@ SIGNATURES = {
     "dasp_fdn_prepare": (_i, []),
     "dasp_fdn_forward": (_i, [_p, _p, ctypes.POINTER(ctypes.c_int), _p, _p, _i, _i, _l, _i, _d, _i, _p]),
     "dasp_fdn_backward": (_i, [_p, _p, ctypes.POINTER(ctypes.c_int)] + [_p] * 5 + [_i, _i, _l, _i, _d, _i, _p]),
+    "dasp_limiter_tile": (_i, []),
+    "dasp_limiter_max_lookahead": (_i, []),
+    "dasp_limiter_state_floats": (_l, [_l, _l]),
+    "dasp_limiter_partial_floats": (_l, [_l, _l]),
+    "dasp_limiter_prepare": (_i, []),
+    "dasp_limiter_forward": (_i, [_p] * 5 + [_i, _i, _l, _i, _d, _d, _p]),
+    "dasp_limiter_backward": (_i, [_p] * 8 + [_i, _i, _l, _i, _d, _d, _p]),
     "dasp_phaser_max_stages": (_i, []),
     "dasp_phaser_tile": (_i, [_i]),
     "dasp_phaser_state_floats": (_l, [_l, _l, _i]),
@@ -213,6 +220,7 @@ def lib():
             L.dasp_device_error()           # allocates the current device's error words now - not under some later stream capture
             L.dasp_fbdelay_prepare()        # feedback_delay's LDS ring is above the default limit: raised now, not inside a call
             L.dasp_fdn_prepare()            # fdn_reverb's K rings: the same
+            L.dasp_limiter_prepare()        # limiter's keys, prefix sums and halo: the same
             L.dasp_resample_prepare()       # resample's table and window together can be: the same
             L.dasp_phaser_prepare()         # and the phaser's rebuilt stage signals in its backward kernel
     return _lib

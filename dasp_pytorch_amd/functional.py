@@ -10,7 +10,7 @@ from . import signal as _signal
 from . import _mt19937
 from . import ops as _ops
 from . import _lib
-from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, FdnReverbFunction, FeedbackDelayFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
+from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, FdnReverbFunction, FeedbackDelayFunction, LimiterFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
                   PhaserFunction, ResampleFunction, StereoMixFunction, TVFILTER_MODES, TimeVaryingFilterFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
@@ -199,6 +199,67 @@ def fdn_reverb(x: torch.Tensor, sample_rate: float, decay_s: torch.Tensor, dampi
     _lib.require_device(x, "x")
     require_fp32_ok(x, "fdn_reverb")
     return FdnReverbFunction.apply(x, decay_s, damping_hz, mix, sr, lines, bool(decorrelate))
+
+
+LIMITER_MAX_LOOKAHEAD = 1024          # samples: dasp_limiter_max_lookahead() (csrc/limiter.hip), checked here before the device is touched
+
+
+def limiter_lookahead(sample_rate: float, lookahead_ms: float) -> int:
+    """The look-ahead of `limiter` in samples, L = round(sample_rate * lookahead_ms / 1000), after the checks of its arguments."""
+    try:
+        sr, ms = float(sample_rate), float(lookahead_ms)
+    except (TypeError, ValueError):
+        sr = ms = float("nan")
+    if not (sr > 0.0 and sr != float("inf")):
+        raise ValueError(f"limiter: finite sample_rate > 0, got {sample_rate}")
+    if not (ms >= 0.0 and ms != float("inf")):
+        raise ValueError(f"limiter: finite lookahead_ms >= 0, got {lookahead_ms}")
+    L = round(sr * ms / 1000.0)
+    if L > LIMITER_MAX_LOOKAHEAD:
+        raise ValueError(f"limiter: a look-ahead of {L} samples ({lookahead_ms} ms at {sample_rate} Hz) is above the maximum of {LIMITER_MAX_LOOKAHEAD}")
+    return int(L)
+
+
+def limiter(x: torch.Tensor, sample_rate: float, threshold_db: torch.Tensor, release_ms: torch.Tensor, lookahead_ms: float = 5.0,
+            eps: float = 1e-8):
+    """Look-ahead brickwall limiter with linked channels: the op that guarantees a ceiling. x (bs, chs, seq_len); threshold_db and
+    release_ms hold bs values each; lookahead_ms and eps are plain floats. y has the shape of x and is aligned with it: the op works on
+    whole tensors and looks into the future, there is no latency. For item b, with N = seq_len and an internal timeline m in
+    [0, N + L); everything before 0 and the level from N on are zero:
+        L   = round(sample_rate * lookahead_ms / 1000)          0 <= L <= 1024
+        thr = clamp(threshold_db, -120, 40);  t = clamp(release_ms, 0.1, 10000)
+        rho = exp(-ln 9 / (sample_rate * t / 1000))             (the compressor's 10-90 % constant)
+        p[m] = max_c |x[b,c,m]|                                 (channels linked; the lowest channel wins a tie)
+        r[m] = max(0, 20 log10(max(p[m], eps)) - thr)           (required reduction in dB; 0 for m >= N)
+        h[m] = max_{0<=k<=L} r[m-k]                             (hold; the latest sample wins a tie)
+        e[m] = max(h[m], rho * e[m-1])                          (release; h wins a tie) = max_j rho^max(0, m-j-L) * r[j]
+        s[m] = (1/(L+1)) * sum_{j=0..L} e[m-j]                  (attack: a box of the look-ahead's length, in dB)
+        G[m] = 10^(-s[m]/20);     y[b,c,n] = x[b,c,n] * G[n+L]
+    Each e[n+L-j], 0 <= j <= L, is at least r[n], so |y| <= 10^(thr/20) at every sample (to the rounding of r, G and the product: a
+    few 1e-7 of the ceiling); an item that stays below its threshold comes back bit for bit. The release is linear in dB: the
+    reduction falls to a ninth in release_ms. r, the powers of rho, the box and G are float64 in the kernel and rounded once, e is
+    float32 (it underflows to 0 after about 87 / |ln rho| samples of release) (csrc/limiter.hip).
+    Differentiable in x, threshold_db and release_ms, once (no double backward), by a hand-derived adjoint that follows the winning
+    sample of every e[m]; both control gradients are exactly zero where the control was clamped. No atomics: every result is
+    bit-identical run to run and for an item alone or inside a batch. A gradient keeps G and the winners, 8 bytes per sample of an
+    item; nothing is kept without one. A NaN control makes its own item NaN, gradients included; a NaN or inf sample stays in its item.
+    One workgroup walks one item tile by tile: bs items use bs compute units.
+    Out of scope: true-peak (oversampled) detection, input gain and makeup gain (compose `gain`), unlinked channels, a soft knee,
+    program-dependent release, streaming state, float64, a torch.ops.dasp registration and a chain.py entry.
+    A wrong control count raises RuntimeError naming the control; a sample_rate that is not positive and finite, a lookahead_ms that
+    is negative or not finite, a look-ahead beyond 1024 samples or an eps that is negative or not finite ValueError, before anything
+    touches the device."""
+    bs, chs, seq_len = x.size()
+    for name, c in (("threshold_db", threshold_db), ("release_ms", release_ms)):
+        if c.numel() != bs:
+            raise RuntimeError(f"{name}: shape '[{bs}]' is invalid for input of size {c.numel()}")
+    L = limiter_lookahead(sample_rate, lookahead_ms)
+    e = float(eps)
+    if not (e >= 0.0 and e != float("inf")):
+        raise ValueError(f"limiter: finite eps >= 0, got {eps}")
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "limiter")
+    return LimiterFunction.apply(x, threshold_db, release_ms, float(sample_rate), L, e)
 
 
 def phaser(x: torch.Tensor, sample_rate: float, rate_hz: torch.Tensor, center_hz: torch.Tensor, depth: torch.Tensor, phase: torch.Tensor,

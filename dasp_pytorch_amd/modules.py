@@ -399,6 +399,20 @@ class FDNReverb(Processor):
         self.param_ranges = {"decay_s": (min_decay_s, max_decay_s), "damping_hz": (min_damping_hz, max_damping_hz), "mix": (min_mix, max_mix)}
 
 
+class Limiter(Processor):
+    """Look-ahead brickwall limiter (functional.limiter). The parameters threshold_db and release_ms are the functional's own argument
+    names; lookahead_ms is fixed at construction."""
+
+    def __init__(self, sample_rate: int, lookahead_ms: float = 5.0, min_threshold_db: float = -40.0, max_threshold_db: float = 0.0,
+                 min_release_ms: float = 5.0, max_release_ms: float = 500.0):
+        super().__init__()
+        F.limiter_lookahead(sample_rate, lookahead_ms)
+        self.sample_rate = sample_rate
+        self.lookahead_ms = float(lookahead_ms)
+        self.process_fn = functools.partial(F.limiter, lookahead_ms=self.lookahead_ms)
+        self.param_ranges = {"threshold_db": (min_threshold_db, max_threshold_db), "release_ms": (min_release_ms, max_release_ms)}
+
+
 class Phaser(Processor):
     """Phaser (functional.phaser) with `stages` all-pass stages. The parameters rate_hz, center_hz, depth, phase and mix are the
     functional's own argument names; stages and stereo_spread are fixed at construction."""

@@ -508,7 +508,42 @@ int dasp_fdn_forward(const float* x, const float* ctl, const int* delays, float*
 int dasp_fdn_backward(const float* x, const float* ctl, const int* delays, const float* v, const float* gy, float* gx, float* gctl,
                       float* partials, int B, int C, long N, int K, double sample_rate, int decorrelate, void* stream);
 
-/* phaser: `stages` first-order all-pass sections in series whose shared coefficient a sine LFO sweeps, mixed with the dry signal; a
+/* limiter: look-ahead brickwall limiter - hold, release and attack of the required gain reduction as a scan over the (max, x) semiring
+ * and a box, one workgroup per ITEM, all channels linked (csrc/limiter.hip).
+ * x, y, gy, gx (B, C, N) fp32; ctl, gctl (B, 2) fp32: threshold_db, release_ms; gain (B, N) fp32; winner (B, N) int32; lookahead = L in
+ * samples, 0 <= L <= dasp_limiter_max_lookahead() = 1024.  For item b on the timeline m in [0, N + L), zero before 0, the level zero
+ * from N on:
+ *   thr = clamp(threshold_db, -120, 40),  t = clamp(release_ms, 0.1, 10000),  rho = exp(-ln 9 / (sample_rate t / 1000))
+ *   p[m] = max_c |x[b,c,m]|  (lowest channel wins a tie),   r[m] = max(0, 20 log10(max(p[m], eps)) - thr)
+ *   h[m] = max_{0<=k<=L} r[m-k]  (latest sample wins a tie),   e[m] = max(h[m], rho e[m-1])  (h wins a tie),   w[m] the winning sample of e[m]
+ *   s[m] = (1/(L+1)) sum_{j=0..L} e[m-j],   G[m] = 10^(-s[m]/20),   y[b,c,n] = x[b,c,n] G[n+L]
+ * so that |y| <= 10^(thr/20) at every sample, and an item below its threshold comes back bit for bit. r, the powers of rho, the box sum
+ * and G are float64 in the kernels and rounded once; e is float32.
+ * An item is walked in tiles of dasp_limiter_tile() = 2048 samples of the timeline.
+ * Forward: gain and winner (both NULL: nothing saved) receive G[n+L] and w[n+L] (-1 where e = 0), n in [0, N):
+ * dasp_limiter_state_floats(B, N) = 2 B N words, 8 bytes per sample of an item.  Backward: gx (NULL: not written), gctl; w[m] for m < L is
+ * rebuilt from x; scratch: dasp_limiter_partial_floats(B, N) = 2 B N floats, the segmented sums of the winners' runs, zeroed by a kernel
+ * of the call (it may be dirty). No atomics: y, gain, winner, gx and gctl are bit-identical run to run and for an item alone or in a batch.
+ * Both control gradients are exactly zero where the control was clamped.
+ * dasp_limiter_prepare() raises the kernels' dynamic-LDS limit on the current device; the binding calls it once when it loads the
+ * library, and a call on a device that was not prepared does it itself.
+ * A null pointer (gain and winner together in forward, gx in backward apart), a non-positive size, lookahead < 0, a sample rate that is not
+ * positive and finite, an eps that is negative or not finite: DASP_ERR_ARG (-1 from the queries); lookahead above its maximum or
+ * N >= 2^31 - 4096: DASP_ERR_UNSUPPORTED. All of it is checked before any launch.
+ * Non-finite input: comparisons decide. A NaN peak asks for no reduction (the sample itself stays NaN), an inf peak for an infinite
+ * one from there on. A NaN control makes y, gx and both control gradients of its item NaN. What the backward kernel reads from
+ * winner is checked against [0, N) before it forms an address. Other items keep every bit. */
+int dasp_limiter_tile(void);
+int dasp_limiter_max_lookahead(void);
+long dasp_limiter_state_floats(long B, long N);
+long dasp_limiter_partial_floats(long B, long N);
+int dasp_limiter_prepare(void);
+int dasp_limiter_forward(const float* x, const float* ctl, float* y, float* gain, int* winner, int B, int C, long N, int lookahead,
+                         double sample_rate, double eps, void* stream);
+int dasp_limiter_backward(const float* x, const float* ctl, const float* gain, const int* winner, const float* gy, float* gx, float* gctl,
+                          float* scratch, int B, int C, long N, int lookahead, double sample_rate, double eps, void* stream);
+
+/* phaser:`stages` first-order all-pass sections in series whose shared coefficient a sine LFO sweeps, mixed with the dry signal; a
  * recurrence whose coefficient changes with every sample, evaluated as a scan, one workgroup per (b, c) row (csrc/phaser.hip).
  * x, y, gy, gx (B, C, N) fp32; ctl, gctl (B, 5) fp32: rate_hz, center_hz, depth (octaves), phase (turns), mix.  For item b, channel c,
  * sample n, with every state zero before sample 0:

@@ -1,0 +1,140 @@
+"""functional.limiter restated in torch on the CPU, with the hand-written adjoint and the tie rules of its definition
+(dasp_pytorch_amd/functional.py limiter): a Python loop over the samples of the internal timeline. `arith` is the dtype everything is
+computed in (rho apart: float64, rounded once), so that the same code is the float64 yardstick and the float32 one.
+
+  limiter(...)            the definition in differentiable torch ops (autograd is the check of the hand-written adjoint)
+  forward_backward(...)   y, gx, gthr, grel from the explicit winners; also w (B, N + L), the winning channel cs (B, N), and `gap`: per
+                          kind of decision the smallest relative gap between winner and runner-up over the decisions that route a
+                          value or a gradient - the hold maximum and h against rho e wherever the larger one is positive, the channel
+                          maximum and r > 0 at the samples that win some e[m]
+"""
+import math
+
+import torch
+
+LN9 = math.log(9.0)
+NAMES = ("y", "gx", "gthr", "grel")
+GRADS = ("gthr", "grel")
+CTL = ("threshold_db", "release_ms")
+THR_RANGE, REL_RANGE = (-120.0, 40.0), (0.1, 10000.0)
+
+
+def lookahead_samples(sample_rate, lookahead_ms):
+    return int(round(float(sample_rate) * float(lookahead_ms) / 1000.0))
+
+
+def rho_of(sample_rate, t, arith):
+    return torch.exp(-LN9 / (float(sample_rate) * t.double() / 1000.0)).to(arith)
+
+
+def limiter(x, sample_rate, threshold_db, release_ms, lookahead_ms=5.0, eps=1e-8, lookahead=None, two_step=False):
+    """The definition, differentiable, in the dtype of x. two_step: e[m] = max_j rho^max(0, m-j-L) r[j] instead of the recurrence."""
+    B, C, N = x.shape
+    L = lookahead_samples(sample_rate, lookahead_ms) if lookahead is None else int(lookahead)
+    thr = threshold_db.reshape(B).to(x.dtype).clamp(*THR_RANGE)
+    t = release_ms.reshape(B).to(x.dtype).clamp(*REL_RANGE)
+    rho = torch.exp(-LN9 / (float(sample_rate) * t / 1000.0))
+    p = x.abs().amax(1)
+    r = (20.0 * torch.log10(p.clamp(min=eps)) - thr[:, None]).clamp(min=0.0)
+    M = N + L
+    r = torch.cat([r, r.new_zeros(B, L)], 1)
+    e = []
+    if two_step:
+        j = torch.arange(M)
+        for m in range(M):
+            k = (m - j[:m + 1] - L).clamp(min=0).to(x.dtype)
+            e.append((rho[:, None] ** k[None] * r[:, :m + 1]).amax(1))
+    else:
+        prev = r.new_zeros(B)
+        for m in range(M):
+            h = r[:, max(0, m - L):m + 1].amax(1)
+            prev = torch.maximum(h, rho * prev)
+            e.append(prev)
+    e = torch.cat([r.new_zeros(B, L), torch.stack(e, 1)], 1)                  # e[m] at column m + L
+    s = sum(e[:, L - j:L - j + M] for j in range(L + 1)) / (L + 1)
+    G = 10.0 ** (-s / 20.0)
+    return x * G[:, None, L:], e[:, L:], G
+
+
+def forward_backward(x, sample_rate, threshold_db, release_ms, gy, lookahead_ms=5.0, eps=1e-8, arith=torch.float64, lookahead=None):
+    B, C, N = x.shape
+    L = lookahead_samples(sample_rate, lookahead_ms) if lookahead is None else int(lookahead)
+    M, W = N + L, L + 1
+    sr = float(sample_rate)
+    xa, ga = x.to(arith), gy.to(arith)
+    thr_raw, rel_raw = threshold_db.reshape(B).to(arith), release_ms.reshape(B).to(arith)
+    thr, t = thr_raw.clamp(*THR_RANGE), rel_raw.clamp(*REL_RANGE)
+    rho = rho_of(sr, t, arith)
+    big = torch.finfo(arith).max
+    gap = dict(hold=big, release=big, channel=big, positive=big)
+
+    ax = xa.abs()
+    p, cs = ax.max(1)                                                        # the first of equal maxima: the lowest channel
+    lvl = 20.0 * torch.log10(torch.clamp(p, min=eps)) - thr[:, None]
+    r = torch.cat([lvl.clamp(min=0.0), lvl.new_zeros(B, L)], 1)
+    e = r.new_zeros(B, M)
+    w = torch.full((B, M), -1, dtype=torch.long)
+    prev, wprev = r.new_zeros(B), torch.full((B,), -1, dtype=torch.long)
+    rows = torch.arange(B)
+    for m in range(M):
+        lo = max(0, m - L)
+        win = r[:, lo:m + 1].flip(1)                                          # latest first: argmax takes the first of equal maxima
+        a = win.argmax(1)
+        h = win[rows, a]
+        hj = m - a
+        if win.shape[1] > 1:
+            top = win.topk(2, dim=1).values
+            live = top[:, 0] > 0
+            if live.any():
+                gap["hold"] = min(gap["hold"], float(((top[:, 0] - top[:, 1]) / top[:, 0])[live].min()))
+        c = rho * prev
+        keep = c > h                                                          # h wins a tie
+        hi = torch.maximum(c, h)
+        live = hi > 0
+        if live.any():
+            gap["release"] = min(gap["release"], float(((c - h).abs() / hi)[live].min()))
+        prev = torch.where(keep, c, h)
+        wprev = torch.where(keep, wprev, hj)
+        e[:, m] = prev
+        w[:, m] = torch.where(prev > 0, wprev, torch.full_like(wprev, -1))
+    ep = torch.cat([e.new_zeros(B, L), e], 1)
+    s = sum(ep[:, L - j:L - j + M] for j in range(L + 1)) / W
+    G = 10.0 ** (-s / 20.0)
+    Gn = G[:, L:]                                                             # G[n + L]
+    y = xa * Gn[:, None]
+
+    # the decisions at the winning samples
+    for b in range(B):
+        js = torch.unique(w[b][w[b] >= 0])
+        if len(js):
+            lv = lvl[b, js]
+            scale = torch.maximum(torch.maximum((lv + thr[b]).abs(), thr[b].abs().expand_as(lv)), torch.ones_like(lv))
+            gap["positive"] = min(gap["positive"], float((lv.abs() / scale).min()))
+            if C > 1:
+                top = ax[b][:, js].topk(2, dim=0).values
+                gap["channel"] = min(gap["channel"], float(((top[0] - top[1]) / top[0]).min()))
+
+    # adjoint
+    gx = ga * Gn[:, None]
+    q = (ga * xa).sum(1) * Gn
+    gs = torch.cat([q.new_zeros(B, L), -(math.log(10.0) / 20.0) * q, q.new_zeros(B, L)], 1)      # gs[m] at column m, zero tail
+    ge = sum(gs[:, j:j + M] for j in range(L + 1)) / W
+    mm = torch.arange(M)[None].expand(B, M)
+    k = (mm - w - L).clamp(min=0)
+    valid = w >= 0
+    pk = torch.where(valid, rho[:, None] ** k.to(arith), torch.zeros_like(ge))
+    gr = torch.zeros(B, N, dtype=arith)
+    gr.scatter_add_(1, w.clamp(min=0), pk * ge * valid)
+    g_rho = (k.to(arith) * e / rho[:, None] * ge * valid).sum(1)
+    gthr = -gr.sum(1)
+    grel = g_rho * rho * LN9 * 1000.0 / (sr * t * t)
+    gthr = torch.where((thr_raw < THR_RANGE[0]) | (thr_raw > THR_RANGE[1]), torch.zeros_like(gthr), gthr)
+    grel = torch.where((rel_raw < REL_RANGE[0]) | (rel_raw > REL_RANGE[1]), torch.zeros_like(grel), grel)
+    limited = lvl > 0
+    xs = xa.gather(1, cs[:, None])[:, 0]
+    add = torch.where(limited, torch.sign(xs) * gr * (20.0 / math.log(10.0)) / torch.where(limited, p, torch.ones_like(p)), torch.zeros_like(gr))
+    gx = gx.scatter_add(1, cs[:, None], add[:, None])
+    out = dict(y=y, gx=gx, gthr=gthr, grel=grel, G=Gn, e=e, s=s)
+    out = {k_: v.double().numpy() for k_, v in out.items()}
+    out.update(w=w.numpy(), cs=cs.numpy(), limited=limited.numpy(), gap=gap, L=L)
+    return out
