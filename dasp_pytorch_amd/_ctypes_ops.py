@@ -821,376 +821,326 @@ class StereoMixFunction(torch.autograd.Function):
         return (None if gx is None else gx.to(xd)), gc[0], gc[1], gc[2]
 
 
-class OversampledDistortionFunction(torch.autograd.Function):
-    """y = decimate(tanh(g * interpolate(x))) at `oversample` times the sample rate, g = 10^(drive_db / 20) with one drive per (b, c) row
-    (dasp_osdist_forward / _backward, csrc/oversample.hip). taps: the 2 * half_width * oversample + 1 float32 taps as a ctypes array
-    (signal.oversampling_taps, rounded once). Saves x and drive_db only: the backward kernel recomputes the oversampled signal in LDS."""
+class _AudioControlsFunction(torch.autograd.Function):
+    """Shared plumbing of the delay, filter and limiter ops: audio x (B, C, N), computed in float32, plus per-item controls that are
+    leaves, plus plain-Python configuration. _run and _grad hold what is common - what a call records, the empty signal in both
+    directions, the controls as the float32 matrix the kernels read, the optional grad x, the gradients back in every leaf's own shape
+    and dtype - and a subclass holds what differs: its C calls, what it saves and the sizes of its state and scratch."""
+    CFG = ()        # one converter per plain-Python argument, in the order of ctx.cfg
 
-    @staticmethod
-    def forward(ctx, x, drive_db, taps, oversample, half_width):
+    @classmethod
+    def _run(cls, ctx, x, ctls, *cfg):
         _lib.require_device(x, "x")
-        B, C, N = x.shape
-        ctx.meta = (x.dtype, drive_db.dtype, drive_db.shape)
-        ctx.cfg = (taps, int(oversample), int(half_width))
+        B, C, N = x.shape                      # (three axes, or a ValueError before anything is recorded)
+        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
+        ctx.cfg = tuple(conv(v) for conv, v in zip(cls.CFG, cfg))
         ctx.empty = x.numel() == 0
         if ctx.empty:
             return torch.empty_like(x)
         with torch.cuda.device(x.device):
             x32 = _f32c(x)
-            d32 = drive_db.detach().reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
+            c32 = cls._controls(x, ctls)
             y = torch.empty_like(x32)
-            call("dasp_osdist_forward", ptr(x32), ptr(d32), taps, ptr(y), B, C, N, int(oversample), int(half_width), stream())
-            ctx.save_for_backward(x32, d32)
+            kept = cls._forward(ctx, x32, c32, y)
+            if kept is not None:               # None: no leaf needs a gradient, nothing is saved
+                ctx.save_for_backward(x32, *c32, *kept)
         return y.to(x.dtype)
+
+    @staticmethod
+    def _f32(x, c, *shape):
+        """One control on x's device, float32, viewed as `shape`."""
+        return c.detach().reshape(*shape).to(device=x.device, dtype=torch.float32)
+
+    @classmethod
+    def _controls(cls, x, ctls, *per_item):
+        """What the kernels read: k controls of bs (x per_item) values each as one (bs, [per_item,] k) float32 matrix."""
+        return (torch.stack([cls._f32(x, c, x.shape[0], *per_item) for c in ctls], dim=-1).contiguous(),)
+
+    @classmethod
+    def _grad(cls, ctx, gy):
+        (xd, cmeta), need = ctx.meta, ctx.needs_input_grad
+        tail = (None,) * (len(need) - 1 - len(cmeta))                             # the configuration
+        if ctx.empty:
+            return _needed(ctx, (torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + tail)
+        x32, *saved = ctx.saved_tensors
+        with torch.cuda.device(x32.device):
+            gx = torch.empty_like(x32) if need[0] else None                       # None: the kernel writes no grad x; its scans still run
+            cols = cls._backward(ctx, x32, saved, gy, gx)
+        gc = tuple(g.reshape(s).to(d) if n else None for g, (d, s), n in zip(cols, cmeta, need[1:]))
+        return (gx.to(xd) if need[0] else None,) + gc + tail
+
+    # A subclass defines, beside forward / backward (autograd wants them on the class itself):
+    #   _forward(ctx, x32, c32, y) -> what backward needs beyond x32 and c32, as a tuple; None: save nothing
+    #   _backward(ctx, x32, saved, gy, gx) -> one float32 gradient per control (None where the leaf cannot need one); it makes the
+    #   contiguous float32 copy of gy itself, after its own allocations
+
+
+class OversampledDistortionFunction(_AudioControlsFunction):
+    """y = decimate(tanh(g * interpolate(x))) at `oversample` times the sample rate, g = 10^(drive_db / 20) with one drive per (b, c) row
+    (dasp_osdist_forward / _backward, csrc/oversample.hip). taps: the 2 * half_width * oversample + 1 float32 taps as a ctypes array
+    (signal.oversampling_taps, rounded once). Saves x and drive_db only: the backward kernel recomputes the oversampled signal in LDS."""
+    CFG = (lambda taps: taps, int, int)
+
+    @staticmethod
+    def forward(ctx, x, drive_db, taps, oversample, half_width):
+        return OversampledDistortionFunction._run(ctx, x, (drive_db,), taps, oversample, half_width)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        xd, dd, dshape = ctx.meta
-        if ctx.empty:
-            return _needed(ctx, (torch.empty_like(gy), torch.zeros(dshape, dtype=dd, device=gy.device), None, None, None))
-        taps, L, H = ctx.cfg
-        x32, d32 = ctx.saved_tensors
+        return OversampledDistortionFunction._grad(ctx, gy)
+
+    @classmethod
+    def _controls(cls, x, ctls):
+        return (cls._f32(x, ctls[0], -1).contiguous(),)
+
+    @staticmethod
+    def _forward(ctx, x32, c32, y):
         B, C, N = x32.shape
-        with torch.cuda.device(x32.device):
-            gx = torch.empty_like(x32)
-            gd = torch.empty_like(d32)
-            partials = torch.empty(_lib.lib().dasp_osdist_partial_floats(B * C, N, L), dtype=torch.float32, device=x32.device)
-            g32 = _f32c(gy)
-            call("dasp_osdist_backward", ptr(x32), ptr(d32), taps, ptr(g32), ptr(gx), ptr(gd), ptr(partials), B, C, N, L, H, stream())
-        return (gx.to(xd) if ctx.needs_input_grad[0] else None), (gd.reshape(dshape).to(dd) if ctx.needs_input_grad[1] else None), None, None, None
+        taps, L, H = ctx.cfg
+        call("dasp_osdist_forward", ptr(x32), ptr(c32[0]), taps, ptr(y), B, C, N, L, H, stream())
+        return ()
+
+    @staticmethod
+    def _backward(ctx, x32, saved, gy, gx):
+        (d32,), (B, C, N), (taps, L, H) = saved, x32.shape, ctx.cfg
+        gx = torch.empty_like(x32) if gx is None else gx                          # this kernel always writes it
+        gd = torch.empty_like(d32)
+        partials = torch.empty(_lib.lib().dasp_osdist_partial_floats(B * C, N, L), dtype=torch.float32, device=x32.device)
+        g32 = _f32c(gy)
+        call("dasp_osdist_backward", ptr(x32), ptr(d32), taps, ptr(g32), ptr(gx), ptr(gd), ptr(partials), B, C, N, L, H, stream())
+        return (gd,)
 
 
-class ModulatedDelayFunction(torch.autograd.Function):
+class ModulatedDelayFunction(_AudioControlsFunction):
     """y = (1 - mix) x + (mix / V) sum of V delay-line taps whose delays a sine LFO moves (dasp_moddelay_forward / _backward,
     csrc/moddelay.hip). delay_ms, depth_ms, rate_hz, phase: bs * V values each; mix: bs values; sample_rate, max_delay_ms, stereo_spread:
     floats; H = ceil(sample_rate / 1000 * max_delay_ms). Saves x, the controls packed as (bs, V, 4), and mix: the backward kernel
     recomputes the taps from x in LDS."""
+    CFG = (float, float, float, int)
 
     @staticmethod
     def forward(ctx, x, delay_ms, depth_ms, rate_hz, phase, mix, sample_rate, max_delay_ms, stereo_spread, H):
-        _lib.require_device(x, "x")
-        B, C, N = x.shape
-        ctls = (delay_ms, depth_ms, rate_hz, phase, mix)
-        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
-        ctx.cfg = (float(sample_rate), float(max_delay_ms), float(stereo_spread), int(H))
-        ctx.empty = x.numel() == 0
-        if ctx.empty:
-            return torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            x32 = _f32c(x)
-            ctl = torch.stack([c.detach().reshape(B, -1).to(device=x.device, dtype=torch.float32) for c in ctls[:4]], dim=-1).contiguous()
-            m32 = mix.detach().reshape(-1).to(device=x.device, dtype=torch.float32).contiguous()
-            y = torch.empty_like(x32)
-            call("dasp_moddelay_forward", ptr(x32), ptr(ctl), ptr(m32), ptr(y), B, C, N, ctl.shape[1], int(H), *ctx.cfg[:3], stream())
-            ctx.save_for_backward(x32, ctl, m32)
-        return y.to(x.dtype)
+        return ModulatedDelayFunction._run(ctx, x, (delay_ms, depth_ms, rate_hz, phase, mix), sample_rate, max_delay_ms, stereo_spread, H)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        xd, cmeta = ctx.meta
-        if ctx.empty:
-            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 4))
-        sample_rate, max_delay_ms, stereo_spread, H = ctx.cfg
-        x32, ctl, m32 = ctx.saved_tensors
-        B, C, N = x32.shape
+        return ModulatedDelayFunction._grad(ctx, gy)
+
+    @classmethod
+    def _controls(cls, x, ctls):
+        return super()._controls(x, ctls[:4], -1) + (cls._f32(x, ctls[4], -1).contiguous(),)
+
+    @staticmethod
+    def _forward(ctx, x32, c32, y):
+        (ctl, m32), (B, C, N) = c32, x32.shape
+        call("dasp_moddelay_forward", ptr(x32), ptr(ctl), ptr(m32), ptr(y), B, C, N, ctl.shape[1], ctx.cfg[3], *ctx.cfg[:3], stream())
+        return ()
+
+    @staticmethod
+    def _backward(ctx, x32, saved, gy, gx):                                       # gx None: the scatter pass is skipped
+        (ctl, m32), (B, C, N), (sample_rate, max_delay_ms, stereo_spread, H) = saved, x32.shape, ctx.cfg
         V = ctl.shape[1]
-        with torch.cuda.device(x32.device):
-            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # the scatter pass is skipped when x needs no gradient
-            gctl = torch.empty_like(ctl)
-            gmix = torch.empty_like(m32)
-            partials = torch.empty(_lib.lib().dasp_moddelay_partial_floats(B * C, N, V, H), dtype=torch.float32, device=x32.device)
-            g32 = _f32c(gy)
-            call("dasp_moddelay_backward", ptr(x32), ptr(ctl), ptr(m32), ptr(g32), ptr(gx), ptr(gctl), ptr(gmix), ptr(partials), B, C, N, V, H,
-                 sample_rate, max_delay_ms, stereo_spread, stream())
-        cols = [gctl[..., q] for q in range(4)] + [gmix]
-        gc = tuple(g.reshape(s).to(d) if need else None for g, (d, s), need in zip(cols, cmeta, ctx.needs_input_grad[1:6]))
-        return (None if gx is None else gx.to(xd),) + gc + (None,) * 4
+        gctl = torch.empty_like(ctl)
+        gmix = torch.empty_like(m32)
+        partials = torch.empty(_lib.lib().dasp_moddelay_partial_floats(B * C, N, V, H), dtype=torch.float32, device=x32.device)
+        g32 = _f32c(gy)
+        call("dasp_moddelay_backward", ptr(x32), ptr(ctl), ptr(m32), ptr(g32), ptr(gx), ptr(gctl), ptr(gmix), ptr(partials), B, C, N, V, H,
+             sample_rate, max_delay_ms, stereo_spread, stream())
+        return gctl.unbind(-1) + (gmix,)
 
 
-class FeedbackDelayKernels:
-    """The two directions of feedback_delay over the C ABI, as the forward / backward pair of a torch.autograd.Function:
-    y = (1 - mix) x + mix r, r the Catmull-Rom read of a delay line that is fed x + feedback r through a one-pole low-pass
+class FeedbackDelayFunction(_AudioControlsFunction):
+    """y = (1 - mix) x + mix r, r the Catmull-Rom read of a delay line that is fed x + feedback r through a one-pole low-pass
     (dasp_fbdelay_forward / _backward, csrc/fbdelay.hip). delay_ms, feedback, damping_hz, mix: bs values each; sample_rate, max_delay_ms:
     floats; H = ceil(sample_rate / 1000 * max_delay_ms). Saves x, the controls packed as (bs, 4) and, when anything needs a gradient,
     the line's input v (bs, chs, seq_len): the backward kernel recomputes the taps from it."""
+    CFG = (float, float, int)
 
     @staticmethod
     def forward(ctx, x, delay_ms, feedback, damping_hz, mix, sample_rate, max_delay_ms, H):
-        _lib.require_device(x, "x")
-        B, C, N = x.shape
-        ctls = (delay_ms, feedback, damping_hz, mix)
-        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
-        ctx.cfg = (float(sample_rate), float(max_delay_ms), int(H))
-        ctx.empty = x.numel() == 0
-        if ctx.empty:
-            return torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            x32 = _f32c(x)
-            ctl = torch.stack([c.detach().reshape(B).to(device=x.device, dtype=torch.float32) for c in ctls], dim=-1).contiguous()
-            y = torch.empty_like(x32)
-            v = torch.empty_like(x32) if any(ctx.needs_input_grad[:5]) else None          # 8 B per sample instead of 12 when nothing needs it
-            call("dasp_fbdelay_forward", ptr(x32), ptr(ctl), ptr(y), ptr(v), B, C, N, int(H), ctx.cfg[0], ctx.cfg[1], stream())
-            if v is not None:
-                ctx.save_for_backward(x32, ctl, v)
-        return y.to(x.dtype)
+        return FeedbackDelayFunction._run(ctx, x, (delay_ms, feedback, damping_hz, mix), sample_rate, max_delay_ms, H)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        xd, cmeta = ctx.meta
-        if ctx.empty:
-            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 3))
-        sample_rate, max_delay_ms, H = ctx.cfg
-        x32, ctl, v = ctx.saved_tensors
-        B, C, N = x32.shape
-        with torch.cuda.device(x32.device):
-            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # not written when x needs no gradient; the recurrence still runs
-            gctl = torch.empty_like(ctl)
-            partials = torch.empty(_lib.lib().dasp_fbdelay_partial_floats(B * C, N, H), dtype=torch.float32, device=x32.device)
-            g32 = _f32c(gy)
-            call("dasp_fbdelay_backward", ptr(x32), ptr(ctl), ptr(v), ptr(g32), ptr(gx), ptr(gctl), ptr(partials), B, C, N, H, sample_rate,
-                 max_delay_ms, stream())
-        gc = tuple(gctl[:, q].reshape(s).to(d) if need else None for q, ((d, s), need) in enumerate(zip(cmeta, ctx.needs_input_grad[1:5])))
-        return (None if gx is None else gx.to(xd),) + gc + (None,) * 3
+        return FeedbackDelayFunction._grad(ctx, gy)
+
+    @staticmethod
+    def _forward(ctx, x32, c32, y):
+        (B, C, N), (sample_rate, max_delay_ms, H) = x32.shape, ctx.cfg
+        v = torch.empty_like(x32) if any(ctx.needs_input_grad[:5]) else None      # 8 B per sample instead of 12 when nothing needs it
+        call("dasp_fbdelay_forward", ptr(x32), ptr(c32[0]), ptr(y), ptr(v), B, C, N, H, sample_rate, max_delay_ms, stream())
+        return None if v is None else (v,)
+
+    @staticmethod
+    def _backward(ctx, x32, saved, gy, gx):
+        (ctl, v), (B, C, N), (sample_rate, max_delay_ms, H) = saved, x32.shape, ctx.cfg
+        gctl = torch.empty_like(ctl)
+        partials = torch.empty(_lib.lib().dasp_fbdelay_partial_floats(B * C, N, H), dtype=torch.float32, device=x32.device)
+        g32 = _f32c(gy)
+        call("dasp_fbdelay_backward", ptr(x32), ptr(ctl), ptr(v), ptr(g32), ptr(gx), ptr(gctl), ptr(partials), B, C, N, H, sample_rate,
+             max_delay_ms, stream())
+        return gctl.unbind(-1)
 
 
-class FeedbackDelayFunction(FeedbackDelayKernels, torch.autograd.Function):
-    """FeedbackDelayKernels bound to autograd. The pair lives in a plain class and this one defines no forward of its own, because the
-    table of tests/autograd_contract_cases.py - one entry for every Function of the package that defines one - is closed: its size is
-    pinned by tests/test_call_state_cpu.py. This op's contract is checked by the same batteries from tests/test_gpu_feedback_delay.py,
-    which watches FeedbackDelayKernels."""
-
-
-class FdnReverbKernels:
-    """The two directions of fdn_reverb over the C ABI, as the forward / backward pair of a torch.autograd.Function:
-    y = (1 - mix) x + mix wet, wet the sum of K delay lines coupled through a Householder matrix and damped by one-pole low-passes
+class FdnReverbFunction(_AudioControlsFunction):
+    """y = (1 - mix) x + mix wet, wet the sum of K delay lines coupled through a Householder matrix and damped by one-pole low-passes
     (dasp_fdn_forward / _backward, csrc/fdn.hip). decay_s, damping_hz, mix: bs values each; sample_rate: a float; delays: a tuple of K
     ints; decorrelate: a bool. Saves x, the controls packed as (bs, 3) and, when a control needs a gradient, the K line signals v
     (bs, chs, K, seq_len): the backward kernel recomputes r, w and wet from them. With only x needing one no v is written: gx depends
     on the controls alone, and the backward call with v = NULL writes nothing else."""
+    CFG = (float, lambda delays: tuple(int(m) for m in delays), bool)
 
     @staticmethod
     def forward(ctx, x, decay_s, damping_hz, mix, sample_rate, delays, decorrelate):
-        _lib.require_device(x, "x")
-        B, C, N = x.shape
-        ctls = (decay_s, damping_hz, mix)
-        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
-        ctx.cfg = (float(sample_rate), tuple(int(m) for m in delays), bool(decorrelate))
-        ctx.empty = x.numel() == 0
-        if ctx.empty:
-            return torch.empty_like(x)
-        K = len(ctx.cfg[1])
-        with torch.cuda.device(x.device):
-            x32 = _f32c(x)
-            ctl = torch.stack([c.detach().reshape(B).to(device=x.device, dtype=torch.float32) for c in ctls], dim=-1).contiguous()
-            y = torch.empty_like(x32)
-            ctx.saved_v = any(ctx.needs_input_grad[1:4])
-            v = torch.empty((B, C, K, N), dtype=torch.float32, device=x.device) if ctx.saved_v else None      # 4 K B per sample, only for the controls
-            call("dasp_fdn_forward", ptr(x32), ptr(ctl), (ctypes.c_int * K)(*ctx.cfg[1]), ptr(y), ptr(v), B, C, N, K, ctx.cfg[0], int(ctx.cfg[2]),
-                 stream())
-            if ctx.saved_v:
-                ctx.save_for_backward(x32, ctl, v)
-            elif ctx.needs_input_grad[0]:
-                ctx.save_for_backward(x32, ctl)
-        return y.to(x.dtype)
+        return FdnReverbFunction._run(ctx, x, (decay_s, damping_hz, mix), sample_rate, delays, decorrelate)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        xd, cmeta = ctx.meta
-        if ctx.empty:
-            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 3))
-        sample_rate, delays, decorrelate = ctx.cfg
+        return FdnReverbFunction._grad(ctx, gy)
+
+    @staticmethod
+    def _forward(ctx, x32, c32, y):
+        (B, C, N), (sample_rate, delays, decorrelate) = x32.shape, ctx.cfg
         K = len(delays)
-        x32, ctl = ctx.saved_tensors[:2]
-        B, C, N = x32.shape
-        with torch.cuda.device(x32.device):
-            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # not written when x needs no gradient; the recurrence still runs
-            v = ctx.saved_tensors[2] if ctx.saved_v else None                     # None: gx alone, one launch, no control sums
-            gctl = torch.empty_like(ctl) if ctx.saved_v else None
-            partials = torch.empty(_lib.lib().dasp_fdn_partial_floats(B * C), dtype=torch.float32, device=x32.device) if ctx.saved_v else None
-            g32 = _f32c(gy)
-            call("dasp_fdn_backward", ptr(x32), ptr(ctl), (ctypes.c_int * K)(*delays), ptr(v), ptr(g32), ptr(gx), ptr(gctl), ptr(partials), B, C, N, K,
-                 sample_rate, int(decorrelate), stream())
-        gc = tuple(gctl[:, q].reshape(s).to(d) if need else None for q, ((d, s), need) in enumerate(zip(cmeta, ctx.needs_input_grad[1:4])))      # (need implies saved_v)
-        return (None if gx is None else gx.to(xd),) + gc + (None,) * 3
+        ctx.saved_v = any(ctx.needs_input_grad[1:4])
+        v = torch.empty((B, C, K, N), dtype=torch.float32, device=x32.device) if ctx.saved_v else None      # 4 K B per sample, only for the controls
+        call("dasp_fdn_forward", ptr(x32), ptr(c32[0]), (ctypes.c_int * K)(*delays), ptr(y), ptr(v), B, C, N, K, sample_rate, int(decorrelate),
+             stream())
+        return (v,) if ctx.saved_v else () if ctx.needs_input_grad[0] else None
+
+    @staticmethod
+    def _backward(ctx, x32, saved, gy, gx):
+        (B, C, N), (sample_rate, delays, decorrelate) = x32.shape, ctx.cfg
+        K = len(delays)
+        ctl = saved[0]
+        v = saved[1] if ctx.saved_v else None                                     # None: gx alone, one launch, no control sums
+        gctl = torch.empty_like(ctl) if ctx.saved_v else None
+        partials = torch.empty(_lib.lib().dasp_fdn_partial_floats(B * C), dtype=torch.float32, device=x32.device) if ctx.saved_v else None
+        g32 = _f32c(gy)
+        call("dasp_fdn_backward", ptr(x32), ptr(ctl), (ctypes.c_int * K)(*delays), ptr(v), ptr(g32), ptr(gx), ptr(gctl), ptr(partials), B, C, N, K,
+             sample_rate, int(decorrelate), stream())
+        return gctl.unbind(-1) if ctx.saved_v else (None,) * 3                    # (a control that needs a gradient implies saved_v)
 
 
-class FdnReverbFunction(FdnReverbKernels, torch.autograd.Function):
-    """FdnReverbKernels bound to autograd. As for feedback_delay the pair lives in a plain class and this one defines no forward of its
-    own: the table of tests/autograd_contract_cases.py is closed, and this op's contract is checked by the same batteries from
-    tests/test_gpu_fdn_reverb.py, which watches FdnReverbKernels."""
-
-
-class LimiterKernels:
-    """The two directions of limiter over the C ABI, as the forward / backward pair of a torch.autograd.Function: y = x G, G the gain of
-    a look-ahead brickwall limiter with linked channels (dasp_limiter_forward / _backward, csrc/limiter.hip). threshold_db, release_ms:
-    bs values each; sample_rate, eps: floats; lookahead: L in samples. Saves x, the controls packed as (bs, 2) and, when anything needs
-    a gradient, G and the winning sample of every gain value, (bs, seq_len) each: 8 bytes per sample of an item. Nothing otherwise."""
+class LimiterFunction(_AudioControlsFunction):
+    """y = x G, G the gain of a look-ahead brickwall limiter with linked channels (dasp_limiter_forward / _backward, csrc/limiter.hip).
+    threshold_db, release_ms: bs values each; sample_rate, eps: floats; lookahead: L in samples. Saves x, the controls packed as (bs, 2)
+    and, when anything needs a gradient, G and the winning sample of every gain value, (bs, seq_len) each: 8 bytes per sample of an
+    item. Nothing otherwise."""
+    CFG = (float, int, float)
 
     @staticmethod
     def forward(ctx, x, threshold_db, release_ms, sample_rate, lookahead, eps):
-        _lib.require_device(x, "x")
-        B, C, N = x.shape
-        ctls = (threshold_db, release_ms)
-        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
-        ctx.cfg = (float(sample_rate), int(lookahead), float(eps))
-        ctx.empty = x.numel() == 0
-        if ctx.empty:
-            return torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            x32 = _f32c(x)
-            ctl = torch.stack([c.detach().reshape(B).to(device=x.device, dtype=torch.float32) for c in ctls], dim=-1).contiguous()
-            y = torch.empty_like(x32)
-            gain = winner = None
-            if any(ctx.needs_input_grad[:3]):
-                gain = torch.empty((B, N), dtype=torch.float32, device=x.device)
-                winner = torch.empty((B, N), dtype=torch.int32, device=x.device)
-            call("dasp_limiter_forward", ptr(x32), ptr(ctl), ptr(y), ptr(gain), ptr(winner), B, C, N, ctx.cfg[1], ctx.cfg[0], ctx.cfg[2], stream())
-            if gain is not None:
-                ctx.save_for_backward(x32, ctl, gain, winner)
-        return y.to(x.dtype)
+        return LimiterFunction._run(ctx, x, (threshold_db, release_ms), sample_rate, lookahead, eps)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        xd, cmeta = ctx.meta
-        if ctx.empty:
-            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 3))
-        sample_rate, lookahead, eps = ctx.cfg
-        x32, ctl, gain, winner = ctx.saved_tensors
-        B, C, N = x32.shape
-        with torch.cuda.device(x32.device):
-            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # not written when x needs no gradient; the scans still run
-            gctl = torch.empty_like(ctl)
-            scratch = torch.empty(_lib.lib().dasp_limiter_partial_floats(B, N), dtype=torch.float32, device=x32.device)
-            g32 = _f32c(gy)
-            call("dasp_limiter_backward", ptr(x32), ptr(ctl), ptr(gain), ptr(winner), ptr(g32), ptr(gx), ptr(gctl), ptr(scratch), B, C, N, lookahead,
-                 sample_rate, eps, stream())
-        gc = tuple(gctl[:, q].reshape(s).to(d) if need else None for q, ((d, s), need) in enumerate(zip(cmeta, ctx.needs_input_grad[1:3])))
-        return (None if gx is None else gx.to(xd),) + gc + (None,) * 3
+        return LimiterFunction._grad(ctx, gy)
+
+    @staticmethod
+    def _forward(ctx, x32, c32, y):
+        (B, C, N), (sample_rate, lookahead, eps) = x32.shape, ctx.cfg
+        gain = winner = None
+        if any(ctx.needs_input_grad[:3]):
+            gain = torch.empty((B, N), dtype=torch.float32, device=x32.device)
+            winner = torch.empty((B, N), dtype=torch.int32, device=x32.device)
+        call("dasp_limiter_forward", ptr(x32), ptr(c32[0]), ptr(y), ptr(gain), ptr(winner), B, C, N, lookahead, sample_rate, eps, stream())
+        return None if gain is None else (gain, winner)
+
+    @staticmethod
+    def _backward(ctx, x32, saved, gy, gx):
+        (ctl, gain, winner), (B, C, N), (sample_rate, lookahead, eps) = saved, x32.shape, ctx.cfg
+        gctl = torch.empty_like(ctl)
+        scratch = torch.empty(_lib.lib().dasp_limiter_partial_floats(B, N), dtype=torch.float32, device=x32.device)
+        g32 = _f32c(gy)
+        call("dasp_limiter_backward", ptr(x32), ptr(ctl), ptr(gain), ptr(winner), ptr(g32), ptr(gx), ptr(gctl), ptr(scratch), B, C, N, lookahead,
+             sample_rate, eps, stream())
+        return gctl.unbind(-1)
 
 
-class LimiterFunction(LimiterKernels, torch.autograd.Function):
-    """LimiterKernels bound to autograd. As for feedback_delay the pair lives in a plain class and this one defines no forward of its own:
-    the table of tests/autograd_contract_cases.py is closed, and this op's contract is checked by the same batteries from
-    tests/test_gpu_limiter.py, which watches LimiterKernels."""
-
-
-class PhaserKernels:
-    """The two directions of phaser over the C ABI, as the forward / backward pair of a torch.autograd.Function:
-    y = (1 - mix) x + mix s_K, s_K the output of K first-order all-pass stages whose shared coefficient a sine LFO sweeps
+class PhaserFunction(_AudioControlsFunction):
+    """y = (1 - mix) x + mix s_K, s_K the output of K first-order all-pass stages whose shared coefficient a sine LFO sweeps
     (dasp_phaser_forward / _backward, csrc/phaser.hip). rate_hz, center_hz, depth, phase, mix: bs values each; sample_rate, stereo_spread:
     floats; stages: K. Saves x, the controls packed as (bs, 5) and, when anything needs a gradient, the K stage states before every tile
     (dasp_phaser_state_floats): the backward kernel rebuilds the stage signals of a tile from them."""
+    CFG = (float, int, float)
 
     @staticmethod
     def forward(ctx, x, rate_hz, center_hz, depth, phase, mix, sample_rate, stages, stereo_spread):
-        _lib.require_device(x, "x")
-        B, C, N = x.shape
-        ctls = (rate_hz, center_hz, depth, phase, mix)
-        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
-        ctx.cfg = (float(sample_rate), int(stages), float(stereo_spread))
-        ctx.empty = x.numel() == 0
-        if ctx.empty:
-            return torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            x32 = _f32c(x)
-            ctl = torch.stack([c.detach().reshape(B).to(device=x.device, dtype=torch.float32) for c in ctls], dim=-1).contiguous()
-            y = torch.empty_like(x32)
-            states = None
-            if any(ctx.needs_input_grad[:6]):
-                states = torch.empty(_lib.lib().dasp_phaser_state_floats(B * C, N, int(stages)), dtype=torch.float32, device=x.device)
-            call("dasp_phaser_forward", ptr(x32), ptr(ctl), ptr(y), ptr(states), B, C, N, int(stages), ctx.cfg[0], ctx.cfg[2], stream())
-            if states is not None:
-                ctx.save_for_backward(x32, ctl, states)
-        return y.to(x.dtype)
+        return PhaserFunction._run(ctx, x, (rate_hz, center_hz, depth, phase, mix), sample_rate, stages, stereo_spread)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        xd, cmeta = ctx.meta
-        if ctx.empty:
-            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 3))
-        sample_rate, stages, stereo_spread = ctx.cfg
-        x32, ctl, states = ctx.saved_tensors
-        B, C, N = x32.shape
-        with torch.cuda.device(x32.device):
-            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # not written when x needs no gradient; the scans still run
-            gctl = torch.empty_like(ctl)
-            partials = torch.empty(_lib.lib().dasp_phaser_partial_floats(B * C), dtype=torch.float32, device=x32.device)
-            g32 = _f32c(gy)
-            call("dasp_phaser_backward", ptr(x32), ptr(ctl), ptr(states), ptr(g32), ptr(gx), ptr(gctl), ptr(partials), B, C, N, stages, sample_rate,
-                 stereo_spread, stream())
-        gc = tuple(gctl[:, q].reshape(s).to(d) if need else None for q, ((d, s), need) in enumerate(zip(cmeta, ctx.needs_input_grad[1:6])))
-        return (None if gx is None else gx.to(xd),) + gc + (None,) * 3
+        return PhaserFunction._grad(ctx, gy)
 
+    @staticmethod
+    def _forward(ctx, x32, c32, y):
+        (B, C, N), (sample_rate, stages, stereo_spread) = x32.shape, ctx.cfg
+        states = None
+        if any(ctx.needs_input_grad[:6]):
+            states = torch.empty(_lib.lib().dasp_phaser_state_floats(B * C, N, stages), dtype=torch.float32, device=x32.device)
+        call("dasp_phaser_forward", ptr(x32), ptr(c32[0]), ptr(y), ptr(states), B, C, N, stages, sample_rate, stereo_spread, stream())
+        return None if states is None else (states,)
 
-class PhaserFunction(PhaserKernels, torch.autograd.Function):
-    """PhaserKernels bound to autograd. As for feedback_delay the pair lives in a plain class and this one defines no forward of its own:
-    the table of tests/autograd_contract_cases.py is closed, and this op's contract is checked by the same batteries from
-    tests/test_gpu_phaser.py, which watches PhaserKernels."""
+    @staticmethod
+    def _backward(ctx, x32, saved, gy, gx):
+        (ctl, states), (B, C, N), (sample_rate, stages, stereo_spread) = saved, x32.shape, ctx.cfg
+        gctl = torch.empty_like(ctl)
+        partials = torch.empty(_lib.lib().dasp_phaser_partial_floats(B * C), dtype=torch.float32, device=x32.device)
+        g32 = _f32c(gy)
+        call("dasp_phaser_backward", ptr(x32), ptr(ctl), ptr(states), ptr(g32), ptr(gx), ptr(gctl), ptr(partials), B, C, N, stages, sample_rate,
+             stereo_spread, stream())
+        return gctl.unbind(-1)
 
 
 TVFILTER_MODES = ("lowpass", "bandpass", "highpass", "notch")
 
 
-class TimeVaryingFilterKernels:
-    """The two directions of time_varying_filter over the C ABI, as the forward / backward pair of a torch.autograd.Function:
-    y = (1 - mix) x + mix w, w the output of a trapezoidal state-variable filter whose g and k follow the curves cutoff_hz and q
+class TimeVaryingFilterFunction(_AudioControlsFunction):
+    """y = (1 - mix) x + mix w, w the output of a trapezoidal state-variable filter whose g and k follow the curves cutoff_hz and q
     (dasp_tvfilter_forward / _backward, csrc/tvfilter.hip). cutoff_hz, q: (bs, F), F = signal.control_frames(seq_len, hop); mix: bs values;
     sample_rate: a float; hop: an int; mode: an index into TVFILTER_MODES. Saves x, the curves, mix and, when anything needs a gradient,
     the two states before every tile (dasp_tvfilter_state_floats): the backward kernel rebuilds a tile from them."""
+    CFG = (float, int, int)
 
     @staticmethod
     def forward(ctx, x, cutoff_hz, q, mix, sample_rate, hop, mode):
-        _lib.require_device(x, "x")
-        B, C, N = x.shape
-        ctls = (cutoff_hz, q, mix)
-        ctx.meta = (x.dtype, [(c.dtype, c.shape) for c in ctls])
-        ctx.cfg = (float(sample_rate), int(hop), int(mode))
-        ctx.empty = x.numel() == 0
-        if ctx.empty:
-            return torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            x32 = _f32c(x)
-            cut, qq = (c.detach().reshape(B, -1).to(device=x.device, dtype=torch.float32).contiguous() for c in (cutoff_hz, q))
-            mx = mix.detach().reshape(B).to(device=x.device, dtype=torch.float32).contiguous()
-            y = torch.empty_like(x32)
-            states = None
-            if any(ctx.needs_input_grad[:4]):
-                states = torch.empty(_lib.lib().dasp_tvfilter_state_floats(B * C, N), dtype=torch.float32, device=x.device)
-            call("dasp_tvfilter_forward", ptr(x32), ptr(cut), ptr(qq), ptr(mx), ptr(y), ptr(states), B, C, N, ctx.cfg[1], ctx.cfg[2], ctx.cfg[0], stream())
-            if states is not None:
-                ctx.save_for_backward(x32, cut, qq, mx, states)
-        return y.to(x.dtype)
+        return TimeVaryingFilterFunction._run(ctx, x, (cutoff_hz, q, mix), sample_rate, hop, mode)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        xd, cmeta = ctx.meta
-        if ctx.empty:
-            return _needed(ctx, ((torch.empty_like(gy),) + tuple(torch.zeros(s, dtype=d, device=gy.device) for d, s in cmeta) + (None,) * 3))
-        sample_rate, hop, mode = ctx.cfg
-        x32, cut, qq, mx, states = ctx.saved_tensors
-        B, C, N = x32.shape
-        with torch.cuda.device(x32.device):
-            gx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None       # not written when x needs no gradient; the scans still run
-            gcut, gq, gmix = torch.empty_like(cut), torch.empty_like(qq), torch.empty_like(mx)
-            scratch = torch.empty(_lib.lib().dasp_tvfilter_scratch_floats(B * C, N, hop), dtype=torch.float32, device=x32.device)
-            g32 = _f32c(gy)
-            call("dasp_tvfilter_backward", ptr(x32), ptr(cut), ptr(qq), ptr(mx), ptr(states), ptr(g32), ptr(gx), ptr(gcut), ptr(gq), ptr(gmix), ptr(scratch),
-                 B, C, N, hop, mode, sample_rate, stream())
-        gc = tuple(g.reshape(s).to(d) if need else None for g, (d, s), need in zip((gcut, gq, gmix), cmeta, ctx.needs_input_grad[1:4]))
-        return (None if gx is None else gx.to(xd),) + gc + (None,) * 3
+        return TimeVaryingFilterFunction._grad(ctx, gy)
 
+    @classmethod
+    def _controls(cls, x, ctls):                                                  # the curves stay two (bs, F) matrices beside mix
+        B = x.shape[0]
+        return tuple(cls._f32(x, c, B, -1).contiguous() for c in ctls[:2]) + (cls._f32(x, ctls[2], B).contiguous(),)
 
-class TimeVaryingFilterFunction(TimeVaryingFilterKernels, torch.autograd.Function):
-    """TimeVaryingFilterKernels bound to autograd. As for phaser the pair lives in a plain class and this one defines no forward of its
-    own: the table of tests/autograd_contract_cases.py is closed, and this op's contract is checked by the same batteries from
-    tests/test_gpu_tvfilter.py, which watches TimeVaryingFilterKernels."""
+    @staticmethod
+    def _forward(ctx, x32, c32, y):
+        (cut, qq, mx), (B, C, N), (sample_rate, hop, mode) = c32, x32.shape, ctx.cfg
+        states = None
+        if any(ctx.needs_input_grad[:4]):
+            states = torch.empty(_lib.lib().dasp_tvfilter_state_floats(B * C, N), dtype=torch.float32, device=x32.device)
+        call("dasp_tvfilter_forward", ptr(x32), ptr(cut), ptr(qq), ptr(mx), ptr(y), ptr(states), B, C, N, hop, mode, sample_rate, stream())
+        return None if states is None else (states,)
+
+    @staticmethod
+    def _backward(ctx, x32, saved, gy, gx):
+        (cut, qq, mx, states), (B, C, N), (sample_rate, hop, mode) = saved, x32.shape, ctx.cfg
+        gcut, gq, gmix = torch.empty_like(cut), torch.empty_like(qq), torch.empty_like(mx)
+        scratch = torch.empty(_lib.lib().dasp_tvfilter_scratch_floats(B * C, N, hop), dtype=torch.float32, device=x32.device)
+        g32 = _f32c(gy)
+        call("dasp_tvfilter_backward", ptr(x32), ptr(cut), ptr(qq), ptr(mx), ptr(states), ptr(g32), ptr(gx), ptr(gcut), ptr(gq), ptr(gmix), ptr(scratch),
+             B, C, N, hop, mode, sample_rate, stream())
+        return gcut, gq, gmix
 
 
 _RESAMPLE_DESIGNS, _RESAMPLE_TABLES = {}, {}
@@ -1249,10 +1199,11 @@ def _resample_call(name, *args):
         raise
 
 
-class ResampleKernels:
-    """The two directions of resample over the C ABI, as the forward / backward pair of a torch.autograd.Function: x (rows, N) ->
-    y (rows, ceil(n N / o)) by the polyphase filter of `design` (resample_design), and gy -> gx by its transpose, evaluated as a gather
-    (dasp_resample_forward / _backward, csrc/resample.hip). The op is linear: nothing is saved for the backward pass."""
+class ResampleFunction(torch.autograd.Function):
+    """x (rows, N) -> y (rows, ceil(n N / o)) by the polyphase filter of `design` (resample_design), and gy -> gx by its transpose,
+    evaluated as a gather (dasp_resample_forward / _backward, csrc/resample.hip). The op is linear: nothing is saved for the backward
+    pass. Not an _AudioControlsFunction: rows instead of (B, C, N), an output of another length, no controls and nothing saved leave
+    _f32c as the only thing it would share."""
 
     @staticmethod
     def forward(ctx, x, design):
@@ -1288,12 +1239,6 @@ class ResampleKernels:
             gx = torch.empty((rows, N), dtype=torch.float32, device=gy.device)
             _resample_call("dasp_resample_backward", ptr(g32), ptr(tab), ptr(gx), rows, N, M, design.o, design.n, t.P, t.lo, t.span, stream())
         return gx.to(xd), None
-
-
-class ResampleFunction(ResampleKernels, torch.autograd.Function):
-    """ResampleKernels bound to autograd. As for feedback_delay the pair lives in a plain class and this one defines no forward of its
-    own: the table of tests/autograd_contract_cases.py is closed. The op's contract is checked by the same batteries from
-    tests/test_gpu_resample.py, which watches ResampleKernels."""
 
 
 _FSPEC_CACHE = {}

@@ -1,5 +1,5 @@
 """Host side of resample: the argument checks, the windowed-sinc design in float64 and the two compact tables that
-csrc/resample.hip reads. numpy only; signal.resample_taps and the binding (_ctypes_ops.ResampleKernels) both build on it.
+csrc/resample.hip reads. numpy only; signal.resample_taps and the binding (_ctypes_ops.ResampleFunction) both build on it.
 
 The design restates torchaudio.functional.resample's published algorithm with one deviation: where the window's argument was clamped
 to +-lowpass_filter_width the tap is exactly 0 (torchaudio's formula gives <= 1e-20 there for the Kaiser window and a float32 zero for

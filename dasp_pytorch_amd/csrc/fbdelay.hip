@@ -30,29 +30,21 @@
 // x -2 pi/sr a for damping_hz, zero where damping_hz < 0). Everything is bit-identical run to run and for an item alone or in a batch.
 #include <atomic>
 
-#include "common.hpp"
+#include "row_helpers.hpp"
 
 namespace dasp {
 
 constexpr int FB_THREADS = 256;
 constexpr int FB_BMAX = 2048;                        // longest step
-constexpr int FB_SPT = 9;                            // most consecutive samples per thread and step: fb_spt(FB_BMAX)
+constexpr int FB_SPT = 9;                            // most consecutive samples per thread and step: odd_spt<FB_THREADS>(FB_BMAX)
 constexpr int FB_HMAX = 34816;                       // ring of 34816 + 2 + 2048 floats and 2048 of staging: 152 KiB of the workgroup's 160
 constexpr int FB_NW = FB_THREADS / 64;
 
 struct FbCfg { double k, sr, dmax; };                // k = sr / 1000 (samples per ms), dmax = k max_delay_ms
 struct FbItem { int i; float f, a, fb, mix; bool inside; };
-struct FbW { float a, b, c, d; };                    // weights of v[n-i+1], v[n-i], v[n-i-1], v[n-i-2]
 
 __host__ __device__ __forceinline__ int fb_block(int lag) { return lag < 1 ? 1 : (lag < FB_BMAX ? lag : FB_BMAX); }
 __host__ __device__ __forceinline__ int fb_ring(int H) { return H + 2 + fb_block(H - 1); }
-// consecutive samples per thread in a step of S: odd, so that the lanes' LDS words (stride spt) fall on distinct banks
-__host__ __device__ __forceinline__ int fb_spt(int S) { return ((S + FB_THREADS - 1) / FB_THREADS) | 1; }
-
-__device__ __forceinline__ double fb_pole(double damping_hz, double sr) {
-    const double dh = damping_hz < 0.0 ? 0.0 : damping_hz;                 // a NaN stays
-    return exp(-6.283185307179586 * dh / sr);
-}
 
 __device__ __forceinline__ FbItem fb_item(const float* __restrict__ ctl, int b, const FbCfg& g) {
     const float* q = ctl + (size_t)b * 4;
@@ -64,36 +56,10 @@ __device__ __forceinline__ FbItem fb_item(const float* __restrict__ ctl, int b, 
     it.i = ok ? (int)fl : 2;
     it.f = ok ? (float)(D - fl) : __builtin_nanf("");
     it.inside = !(raw < 2.0 || raw > g.dmax);                              // a NaN is not a clamped delay: it reaches the gradient
-    it.a = (float)fb_pole((double)q[2], g.sr);
+    it.a = (float)damping_pole((double)q[2], g.sr);
     it.fb = q[1];
     it.mix = q[3];
     return it;
-}
-
-__device__ __forceinline__ FbW fb_weights(float f) {
-    const float f2 = f * f;
-    return FbW{0.5f * f * ((2.f - f) * f - 1.f), 0.5f * ((3.f * f - 5.f) * f2 + 2.f), 0.5f * f * ((4.f - 3.f * f) * f + 1.f), 0.5f * f2 * (f - 1.f)};
-}
-__device__ __forceinline__ FbW fb_dweights(float f) {
-    return FbW{0.5f * ((4.f - 3.f * f) * f - 1.f), 0.5f * f * (9.f * f - 10.f), 0.5f * ((8.f - 9.f * f) * f + 1.f), 0.5f * f * (3.f * f - 2.f)};
-}
-// all four products, always: a NaN or inf sample under a zero weight is a NaN
-__device__ __forceinline__ float fb_dot(const FbW& w, float t0, float t1, float t2, float t3) { return w.a * t0 + w.b * t1 + w.c * t2 + w.d * t3; }
-
-// ring word of a position t in (-R, 2 R); the range holds by construction and is enforced all the same
-__device__ __forceinline__ int fb_wrap(int t, int R) {
-    t += t < 0 ? R : 0;
-    t -= t >= R ? R : 0;
-    return min(max(t, 0), R - 1);
-}
-
-// The barrier of the steps: what the waves exchange goes through LDS only, so a wave waits for its own LDS operations and no more.
-// __syncthreads() is also a fence for global memory: it would wait for the acknowledgement of every store of y, v or gx issued so far and
-// for the loads of the next step's inputs - a memory round trip on the critical path of every step.
-__device__ __forceinline__ void fb_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 // The scan of one step. `run`: the thread's last value of u[j] = in[j] + a u[j-1] taken over its own spt samples from zero; returns the
@@ -110,7 +76,7 @@ __device__ __forceinline__ float fb_scan(float run, float as, float alane, float
     float excl = shift_up(agg, 1);
     if (lane == 0) excl = 0.f;
     if (lane == 63) wtot[wv] = agg;
-    fb_lds_barrier();
+    lds_barrier();
     float cw = carry;                                    // u before the wave's first sample; pw = as^64 is a wave's ratio
     for (int u = 0; u < wv; ++u) cw = __builtin_fmaf(pw, cw, wtot[u]);
     return __builtin_fmaf(alane, cw, excl);
@@ -163,9 +129,9 @@ fbdelay_forward_kernel(const float* __restrict__ x, const float* __restrict__ ct
     __shared__ float last[2];                                             // v of the step's last sample
     const int row = blockIdx.x, tid = threadIdx.x, lane = lane_id();
     const FbItem it = fb_item(ctl, row / C, g);
-    const int R = fb_ring(H), S = fb_block(it.i - 1), spt = fb_spt(S), j0 = tid * spt;
+    const int R = fb_ring(H), S = fb_block(it.i - 1), spt = odd_spt<FB_THREADS>(S), j0 = tid * spt;
     float* stage = fb_lds + R;                                            // the step's y, S words
-    const FbW w = fb_weights(it.f);
+    const CrW w = cr_weights(it.f);
     const float a = it.a, na = 1.f - a, fb = it.fb, mix = it.mix, dry = 1.f - mix;
     float as = 1.f;
     for (int s = 0; s < spt; ++s) as *= a;
@@ -191,7 +157,7 @@ fbdelay_forward_kernel(const float* __restrict__ x, const float* __restrict__ ct
         FB_BY_SPT(spt, fb_load<K>(xn, xr, n0 + S + j0, N))
         const int tb = p0 + j0 - it.i - 2;                                 // word of v[n - i - 2] of the thread's first sample
 #pragma unroll
-        for (int m = 0; m < FB_SPT + 3; ++m) tv[m] = fb_lds[fb_wrap(any ? tb + m : 0, R)];       // all of them, no branch: what is not needed is not used
+        for (int m = 0; m < FB_SPT + 3; ++m) tv[m] = fb_lds[ring_wrap(any ? tb + m : 0, R)];       // all of them, no branch: what is not needed is not used
         float run = 0.f;
 #pragma unroll
         for (int s = 0; s < FB_SPT; ++s) {
@@ -200,7 +166,7 @@ fbdelay_forward_kernel(const float* __restrict__ x, const float* __restrict__ ct
                 const bool act = j0 + s < Sc;
                 float wn = 0.f;
                 if (act) {
-                    rv[s] = fb_dot(w, tv[s + 3], tv[s + 2], tv[s + 1], tv[s]);
+                    rv[s] = cr_dot(w, tv[s + 3], tv[s + 2], tv[s + 1], tv[s]);
                     wn = xv[s] + fb * rv[s];
                 }
                 run = act ? na * wn + a * run : a * run;                   // past the step's end: zero input, the same ratio
@@ -213,18 +179,18 @@ fbdelay_forward_kernel(const float* __restrict__ x, const float* __restrict__ ct
         for (int s = 0; s < FB_SPT; ++s) {
             if (s < spt && j0 + s < Sc) {
                 const float v = __builtin_fmaf(p, cin, lv[s]);
-                fb_lds[fb_wrap(p0 + j0 + s, R)] = v;
+                fb_lds[ring_wrap(p0 + j0 + s, R)] = v;
                 if (j0 + s == Sc - 1) last[par] = v;
                 stage[j0 + s] = __builtin_fmaf(mix, rv[s], dry * xv[s]);
             }
             p *= a;
         }
-        fb_lds_barrier();
+        lds_barrier();
         // y and v leave through LDS, a lane per consecutive sample (a thread's own samples are spt words apart); the next step writes
         // `stage` behind its first barrier, which this thread reaches after these reads
         for (int j = tid; j < Sc; j += FB_THREADS) {
             st_stream(yr + n0 + j, stage[j]);
-            if (SAVE) st_stream(vr + n0 + j, fb_lds[fb_wrap(p0 + j, R)]);
+            if (SAVE) st_stream(vr + n0 + j, fb_lds[ring_wrap(p0 + j, R)]);
         }
         p0 += S;
         p0 -= p0 >= R ? R : 0;
@@ -241,9 +207,9 @@ fbdelay_backward_kernel(const float* __restrict__ x, const float* __restrict__ c
     __shared__ double red[FB_NW][4];
     const int row = blockIdx.x, tid = threadIdx.x, lane = lane_id();
     const FbItem it = fb_item(ctl, row / C, g);
-    const int R = fb_ring(H), S = fb_block(it.i - 1), spt = fb_spt(S), j0 = tid * spt;
+    const int R = fb_ring(H), S = fb_block(it.i - 1), spt = odd_spt<FB_THREADS>(S), j0 = tid * spt;
     float* stage = fb_lds + R;                                            // the step's gx, S words
-    const FbW w = fb_weights(it.f), dw = fb_dweights(it.f);
+    const CrW w = cr_weights(it.f), dw = cr_dweights(it.f);
     const float a = it.a, na = 1.f - a, fb = it.fb, mix = it.mix, dry = 1.f - mix;
     float as = 1.f;
     for (int s = 0; s < spt; ++s) as *= a;
@@ -274,7 +240,7 @@ fbdelay_backward_kernel(const float* __restrict__ x, const float* __restrict__ c
         FB_BY_SPT(spt, fb_load_bwd<K>(nx, gr, xr, vr, nh - S, it.i, N))
         const int tb = p0 + j0 - it.i - 2;                                 // word of gr[n + i + 2] of the thread's first sample
 #pragma unroll
-        for (int m = 0; m < FB_SPT + 3; ++m) tv[m] = fb_lds[fb_wrap(any ? tb + m : 0, R)];       // all of them, no branch: what is not needed is not used
+        for (int m = 0; m < FB_SPT + 3; ++m) tv[m] = fb_lds[ring_wrap(any ? tb + m : 0, R)];       // all of them, no branch: what is not needed is not used
         float run = 0.f;
 #pragma unroll
         for (int s = 0; s < FB_SPT; ++s) {
@@ -283,7 +249,7 @@ fbdelay_backward_kernel(const float* __restrict__ x, const float* __restrict__ c
                 const bool act = j0 + s < Sc;
                 float sn = 0.f;
                 if (act) {
-                    sn = fb_dot(w, tv[s + 3], tv[s + 2], tv[s + 1], tv[s]);    // gr[n+i-1], gr[n+i], gr[n+i+1], gr[n+i+2]
+                    sn = cr_dot(w, tv[s + 3], tv[s + 2], tv[s + 1], tv[s]);    // gr[n+i-1], gr[n+i], gr[n+i+1], gr[n+i+2]
                 }
                 run = act ? sn + a * run : a * run;
                 lv[s] = run;
@@ -297,12 +263,12 @@ fbdelay_backward_kernel(const float* __restrict__ x, const float* __restrict__ c
                 const float q = __builtin_fmaf(p, cin, lv[s]);
                 const float gw = na * q;
                 const float grn = __builtin_fmaf(fb, gw, mix * gv[s]);
-                fb_lds[fb_wrap(p0 + j0 + s, R)] = grn;
+                fb_lds[ring_wrap(p0 + j0 + s, R)] = grn;
                 if (j0 + s == Sc - 1) last[par] = q;
                 stage[j0 + s] = __builtin_fmaf(dry, gv[s], gw);
                 const float xs = xv[s], vp = pv[s];
-                const float r = fb_dot(w, hv[s], hv[s + 1], hv[s + 2], hv[s + 3]);
-                const float dr = fb_dot(dw, hv[s], hv[s + 1], hv[s + 2], hv[s + 3]);
+                const float r = cr_dot(w, hv[s], hv[s + 1], hv[s + 2], hv[s + 3]);
+                const float dr = cr_dot(dw, hv[s], hv[s + 1], hv[s + 2], hv[s + 3]);
                 const float wn = xs + fb * r;
                 t_fb = __builtin_fmaf(gw, r, t_fb);
                 t_mix = __builtin_fmaf(gv[s], r - xs, t_mix);
@@ -312,7 +278,7 @@ fbdelay_backward_kernel(const float* __restrict__ x, const float* __restrict__ c
             p *= a;
         }
         s_fb += (double)t_fb; s_mix += (double)t_mix; s_a += (double)t_a; s_d += (double)t_d;
-        fb_lds_barrier();
+        lds_barrier();
         if (gxr)                                                           // gx leaves through LDS, as y does
             for (int j = tid; j < Sc; j += FB_THREADS) st_stream(gxr + (N - 1 - m0 - j), stage[j]);
         p0 += S;
@@ -348,7 +314,7 @@ __global__ void fbdelay_finalize_kernel(const float* __restrict__ partials, cons
     float* o = gctl + (size_t)b * 4;
     o[0] = (float)(g.k * s[0]);
     o[1] = (float)s[1];
-    o[2] = damping < 0.0 ? 0.f : (float)(-6.283185307179586 / g.sr * fb_pole(damping, g.sr) * s[2]);
+    o[2] = damping < 0.0 ? 0.f : (float)(-6.283185307179586 / g.sr * damping_pole(damping, g.sr) * s[2]);
     o[3] = (float)s[3];
 }
 
@@ -359,10 +325,6 @@ __global__ void fbdelay_finalize_kernel(const float* __restrict__ partials, cons
 using namespace dasp;
 
 namespace {
-inline int fb_check() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DASP_OK : (int)e;
-}
 inline bool fb_h_ok(int H) { return H >= 2 && H <= FB_HMAX; }
 inline size_t fb_lds_bytes(int H) { return (size_t)(fb_ring(H) + fb_block(H - 1)) * sizeof(float); }       // the ring and the staged step
 
@@ -415,7 +377,7 @@ int dasp_fbdelay_forward(const float* x, const float* ctl, float* y, float* v, i
     const dim3 grid((unsigned)((long)B * C)), block(FB_THREADS);
     if (v) hipLaunchKernelGGL(fbdelay_forward_kernel<true>, grid, block, fb_lds_bytes(H), (hipStream_t)stream, x, ctl, y, v, N, C, H, g);
     else hipLaunchKernelGGL(fbdelay_forward_kernel<false>, grid, block, fb_lds_bytes(H), (hipStream_t)stream, x, ctl, y, v, N, C, H, g);
-    return fb_check();
+    return launch_status();
 }
 
 int dasp_fbdelay_backward(const float* x, const float* ctl, const float* v, const float* gy, float* gx, float* gctl, float* partials, int B, int C,
@@ -428,9 +390,9 @@ int dasp_fbdelay_backward(const float* x, const float* ctl, const float* v, cons
     const hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(fbdelay_backward_kernel, dim3((unsigned)((long)B * C)), dim3(FB_THREADS), fb_lds_bytes(H), st, x, ctl, v, gy, gx, partials, N, C,
                        H, g);
-    if ((s = fb_check()) != DASP_OK) return s;
+    if ((s = launch_status()) != DASP_OK) return s;
     hipLaunchKernelGGL(fbdelay_finalize_kernel, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, (const float*)partials, ctl, gctl, B, C, g);
-    return fb_check();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -39,14 +39,14 @@
 // gradient there is no saved v: the backward kernel's other instantiation walks the same steps and writes gx alone, the same bits.
 #include <atomic>
 
-#include "common.hpp"
+#include "row_helpers.hpp"
 
 namespace dasp {
 
 constexpr int FDN_THREADS = 256;
 constexpr int FDN_KMAX = 16;                          // most lines
 constexpr int FDN_CAP = 1024;                         // longest step
-constexpr int FDN_SPT = 5;                            // most consecutive samples per thread and step: fdn_spt(FDN_CAP)
+constexpr int FDN_SPT = 5;                            // most consecutive samples per thread and step: odd_spt<FDN_THREADS>(FDN_CAP)
 constexpr int FDN_WORDS = 38912;                      // floats of dynamic LDS: 152 KiB of the workgroup's 160
 constexpr int FDN_NW = FDN_THREADS / 64;
 constexpr int FDN_PART = FDN_KMAX + 2;                // a row's sums: g_0 .. g_15, a, mix
@@ -55,32 +55,11 @@ struct FdnCfg { double sr; int K, S, odd; int m[FDN_KMAX]; };      // odd: 1 whe
 
 __host__ __device__ __forceinline__ int fdn_block(long shortest) { return shortest < 1 ? 1 : (shortest < FDN_CAP ? (int)shortest : FDN_CAP); }
 __host__ __device__ __forceinline__ long fdn_max_sum(int K) { return (long)FDN_WORDS - (long)(K + 1) * FDN_CAP; }
-// consecutive samples per thread in a step of S: odd, so that the lanes' LDS words (stride spt) fall on distinct banks
-__host__ __device__ __forceinline__ int fdn_spt(int S) { return ((S + FDN_THREADS - 1) / FDN_THREADS) | 1; }
 
-__device__ __forceinline__ double fdn_pole(double damping_hz, double sr) {
-    const double dh = damping_hz < 0.0 ? 0.0 : damping_hz;                 // a NaN stays
-    return exp(-6.283185307179586 * dh / sr);
-}
 __device__ __forceinline__ double fdn_decay(double decay_s) { return decay_s < 0.01 ? 0.01 : (decay_s > 100.0 ? 100.0 : decay_s); }       // a NaN stays
 __device__ __forceinline__ double fdn_gain(int m, double sr, double T) { return pow(10.0, -3.0 * (double)m / (sr * T)); }
 // the input of line k: x + u_k - (2/K) sum_j u_j, in one form for both directions
 __device__ __forceinline__ float fdn_w(float x, float u, float su, float c2) { return __builtin_fmaf(-c2, su, x + u); }
-
-// ring word of a position t in (-R, 2 R); the range holds by construction and is enforced all the same
-__device__ __forceinline__ int fdn_wrap(int t, int R) {
-    t += t < 0 ? R : 0;
-    t -= t >= R ? R : 0;
-    return min(max(t, 0), R - 1);
-}
-
-// The barrier of the steps: what the waves exchange goes through LDS only, so a wave waits for its own LDS operations and no more
-// (__syncthreads() would also wait for every global store and load issued so far: a memory round trip in every step).
-__device__ __forceinline__ void fdn_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // What a workgroup keeps about its lines, filled once from the launch's configuration.
 struct FdnTab {
@@ -155,10 +134,10 @@ fdn_forward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, f
     extern __shared__ __attribute__((aligned(16))) float fdn_lds[];       // ring k: v_k[n] at word off_k + n mod R_k; then the staged y
     __shared__ FdnTab t;
     const int row = blockIdx.x, tid = threadIdx.x, lane = lane_id();
-    const int b = row / C, K = g.K, S = g.S, spt = fdn_spt(S), j0 = tid * spt;
+    const int b = row / C, K = g.K, S = g.S, spt = odd_spt<FDN_THREADS>(S), j0 = tid * spt;
     fdn_setup(t, fdn_lds, g, ctl, b, row % C, words);
     float* stage = fdn_lds + (words - S);
-    const float a = (float)fdn_pole((double)ctl[(size_t)b * 3 + 1], g.sr), na = 1.f - a, mix = ctl[(size_t)b * 3 + 2], dry = 1.f - mix;
+    const float a = (float)damping_pole((double)ctl[(size_t)b * 3 + 1], g.sr), na = 1.f - a, mix = ctl[(size_t)b * 3 + 2], dry = 1.f - mix;
     const float c2 = (float)(2.0 / (double)K), kinv = (float)(1.0 / sqrt((double)K));
     float as = 1.f;
     for (int s = 0; s < spt; ++s) as *= a;
@@ -194,7 +173,7 @@ fdn_forward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, f
 #pragma unroll
             for (int s = 0; s < FDN_SPT; ++s) {
                 if (s < spt) {                                             // no branch on the lane: what is not needed is not used
-                    const float r = ring[fdn_wrap(rb + s, R)];
+                    const float r = ring[ring_wrap(rb + s, R)];
                     su[s] += gk * r;
                     wa[s] += sg * r;
                 }
@@ -213,7 +192,7 @@ fdn_forward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, f
                 lv[s] = 0.f;
                 if (s < spt) {
                     const bool act = j0 + s < Sc;
-                    const float wn = fdn_w(xv[s], gk * ring[fdn_wrap(rb + s, R)], su[s], c2);
+                    const float wn = fdn_w(xv[s], gk * ring[ring_wrap(rb + s, R)], su[s], c2);
                     run = act ? na * wn + a * run : a * run;               // past the step's end: zero input, the same ratio
                     lv[s] = run;
                 }
@@ -221,9 +200,9 @@ fdn_forward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, f
             const float excl = fdn_wave_scan(run, as, t.wtot[par][k]);
 #pragma unroll
             for (int s = 0; s < FDN_SPT; ++s)
-                if (s < spt && j0 + s < Sc) ring[fdn_wrap(wb + s, R)] = __builtin_fmaf(pw[s], excl, lv[s]);
+                if (s < spt && j0 + s < Sc) ring[ring_wrap(wb + s, R)] = __builtin_fmaf(pw[s], excl, lv[s]);
         }
-        fdn_lds_barrier();
+        lds_barrier();
         // 3. the carry of the earlier waves and of the step before
         for (int k = 0; k < K; ++k) {
             const int R = t.R[k], wb = any ? t.pos[par][k] + j0 : 0;
@@ -232,7 +211,7 @@ fdn_forward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, f
 #pragma unroll
             for (int s = 0; s < FDN_SPT; ++s) {
                 if (s < spt && j0 + s < Sc) {
-                    const int iw = fdn_wrap(wb + s, R);
+                    const int iw = ring_wrap(wb + s, R);
                     const float v = __builtin_fmaf(pa[s], cw, ring[iw]);
                     ring[iw] = v;
                     if (j0 + s == Sc - 1) t.last[par][k] = v;
@@ -242,8 +221,8 @@ fdn_forward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, f
 #pragma unroll
         for (int s = 0; s < FDN_SPT; ++s)
             if (s < spt && j0 + s < Sc) stage[j0 + s] = yv[s];
-        if (tid < K) t.pos[par ^ 1][tid] = fdn_wrap(t.pos[par][tid] + S, t.R[tid]);
-        fdn_lds_barrier();
+        if (tid < K) t.pos[par ^ 1][tid] = ring_wrap(t.pos[par][tid] + S, t.R[tid]);
+        lds_barrier();
         // y and the v_k leave through LDS, a lane per consecutive sample; the next step writes `stage` and these ring words behind its
         // first barrier, which this thread reaches after these reads
         for (int j = tid; j < Sc; j += FDN_THREADS) st_stream(yr + n0 + j, stage[j]);
@@ -252,7 +231,7 @@ fdn_forward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, f
                 const int R = t.R[k], p0 = t.pos[par][k];
                 const float* ring = fdn_lds + t.off[k];
                 float* vr = vout + ((size_t)row * K + k) * N + n0;
-                for (int j = tid; j < Sc; j += FDN_THREADS) st_stream(vr + j, ring[fdn_wrap(p0 + j, R)]);
+                for (int j = tid; j < Sc; j += FDN_THREADS) st_stream(vr + j, ring[ring_wrap(p0 + j, R)]);
             }
         }
         par ^= 1;
@@ -268,10 +247,10 @@ fdn_backward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, 
     __shared__ FdnTab t;
     __shared__ double red[FDN_NW][FDN_PART];
     const int row = blockIdx.x, tid = threadIdx.x, lane = lane_id();
-    const int b = row / C, K = g.K, S = g.S, spt = fdn_spt(S), j0 = tid * spt;
+    const int b = row / C, K = g.K, S = g.S, spt = odd_spt<FDN_THREADS>(S), j0 = tid * spt;
     fdn_setup(t, fdn_lds, g, ctl, b, row % C, words);
     float* stage = fdn_lds + (words - S);
-    const float a = (float)fdn_pole((double)ctl[(size_t)b * 3 + 1], g.sr), na = 1.f - a, mix = ctl[(size_t)b * 3 + 2], dry = 1.f - mix;
+    const float a = (float)damping_pole((double)ctl[(size_t)b * 3 + 1], g.sr), na = 1.f - a, mix = ctl[(size_t)b * 3 + 2], dry = 1.f - mix;
     const float c2 = (float)(2.0 / (double)K), kinv = (float)(1.0 / sqrt((double)K));
     float as = 1.f;
     for (int s = 0; s < spt; ++s) as *= a;
@@ -333,7 +312,7 @@ fdn_backward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, 
                 lv[s] = 0.f;
                 if (s < spt) {
                     const bool act = j0 + s < Sc;
-                    const float in = ring[fdn_wrap(rb + s, R)];           // rho_k[n + m_k]
+                    const float in = ring[ring_wrap(rb + s, R)];           // rho_k[n + m_k]
                     run = act ? in + a * run : a * run;
                     lv[s] = run;
                 }
@@ -341,9 +320,9 @@ fdn_backward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, 
             const float excl = fdn_wave_scan(run, as, t.wtot[par][k]);
 #pragma unroll
             for (int s = 0; s < FDN_SPT; ++s)
-                if (s < spt && j0 + s < Sc) ring[fdn_wrap(wb + s, R)] = __builtin_fmaf(pw[s], excl, lv[s]);
+                if (s < spt && j0 + s < Sc) ring[ring_wrap(wb + s, R)] = __builtin_fmaf(pw[s], excl, lv[s]);
         }
-        fdn_lds_barrier();
+        lds_barrier();
         // B. lam_k complete, and sum_j om_j
         for (int k = 0; k < K; ++k) {
             const int R = t.R[k], wb = any ? t.pos[par][k] + j0 : 0;
@@ -352,7 +331,7 @@ fdn_backward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, 
 #pragma unroll
             for (int s = 0; s < FDN_SPT; ++s) {
                 if (s < spt && j0 + s < Sc) {
-                    const int iw = fdn_wrap(wb + s, R);
+                    const int iw = ring_wrap(wb + s, R);
                     const float lam = __builtin_fmaf(pa[s], cw, ring[iw]);
                     ring[iw] = lam;
                     if (j0 + s == Sc - 1) t.last[par][k] = lam;
@@ -373,7 +352,7 @@ fdn_backward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, 
 #pragma unroll
                 for (int s = 0; s < FDN_SPT; ++s) {
                     if (s < spt && j0 + s < Sc) {
-                        const int iw = fdn_wrap(wb + s, R);
+                        const int iw = ring_wrap(wb + s, R);
                         const float lam = ring[iw];
                         const float z = __builtin_fmaf(-c2, so[s], na * lam);
                         ring[iw] = __builtin_fmaf(gk, z, ck * gv[s]);
@@ -393,8 +372,8 @@ fdn_backward_kernel(const float* __restrict__ x, const float* __restrict__ ctl, 
 #pragma unroll
         for (int s = 0; s < FDN_SPT; ++s)
             if (s < spt && j0 + s < Sc) stage[j0 + s] = __builtin_fmaf(dry, gv[s], so[s]);
-        if (tid < K) t.pos[par ^ 1][tid] = fdn_wrap(t.pos[par][tid] + S, t.R[tid]);
-        fdn_lds_barrier();
+        if (tid < K) t.pos[par ^ 1][tid] = ring_wrap(t.pos[par][tid] + S, t.R[tid]);
+        lds_barrier();
         if (gxr)                                                           // gx leaves through LDS, as y does
             for (int j = tid; j < Sc; j += FDN_THREADS) st_stream(gxr + (N - 1 - m0 - j), stage[j]);
         par ^= 1;
@@ -441,7 +420,7 @@ __global__ void fdn_finalize_kernel(const float* __restrict__ partials, const fl
     }
     float* o = gctl + (size_t)b * 3;
     o[0] = (raw < 0.01 || raw > 100.0) ? 0.f : (float)gd;                  // a NaN is not a clamped value: it reaches the gradient
-    o[1] = (damping < 0.0 || damping > 1.7976931348623157e308) ? 0.f : (float)(-6.283185307179586 / g.sr * fdn_pole(damping, g.sr) * sa);
+    o[1] = (damping < 0.0 || damping > 1.7976931348623157e308) ? 0.f : (float)(-6.283185307179586 / g.sr * damping_pole(damping, g.sr) * sa);
     o[2] = (float)sm;
 }
 
@@ -452,10 +431,6 @@ __global__ void fdn_finalize_kernel(const float* __restrict__ partials, const fl
 using namespace dasp;
 
 namespace {
-inline int fdn_check() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DASP_OK : (int)e;
-}
 
 // The rings are more LDS than a kernel gets unasked (64 KiB): asked for once per device - by dasp_fdn_prepare() when the library is
 // loaded, so that no call has to (a call may be under stream capture) - and by the first call on any other device.
@@ -517,7 +492,7 @@ int dasp_fdn_forward(const float* x, const float* ctl, const int* delays, float*
     const size_t lds = (size_t)words * sizeof(float);
     if (v) hipLaunchKernelGGL(fdn_forward_kernel<true>, grid, block, lds, (hipStream_t)stream, x, ctl, y, v, N, C, words, g);
     else hipLaunchKernelGGL(fdn_forward_kernel<false>, grid, block, lds, (hipStream_t)stream, x, ctl, y, v, N, C, words, g);
-    return fdn_check();
+    return launch_status();
 }
 
 int dasp_fdn_backward(const float* x, const float* ctl, const int* delays, const float* v, const float* gy, float* gx, float* gctl, float* partials,
@@ -533,12 +508,12 @@ int dasp_fdn_backward(const float* x, const float* ctl, const int* delays, const
     const size_t lds = (size_t)words * sizeof(float);
     if (!v) {                                                              // gx alone: no saved v, no sums, no second launch
         hipLaunchKernelGGL(fdn_backward_kernel<false>, grid, block, lds, st, x, ctl, v, gy, gx, partials, N, C, words, g);
-        return fdn_check();
+        return launch_status();
     }
     hipLaunchKernelGGL(fdn_backward_kernel<true>, grid, block, lds, st, x, ctl, v, gy, gx, partials, N, C, words, g);
-    if ((s = fdn_check()) != DASP_OK) return s;
+    if ((s = launch_status()) != DASP_OK) return s;
     hipLaunchKernelGGL(fdn_finalize_kernel, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, (const float*)partials, ctl, gctl, B, C, g);
-    return fdn_check();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -47,7 +47,7 @@
 // (16,2,131072)); 1024 of 2 spills in the backward kernel.
 #include <atomic>
 
-#include "common.hpp"
+#include "row_helpers.hpp"
 
 namespace dasp {
 
@@ -440,10 +440,6 @@ limiter_backward_kernel(const float* __restrict__ x, const float* __restrict__ c
 using namespace dasp;
 
 namespace {
-inline int lim_check() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DASP_OK : (int)e;
-}
 inline long lim_ntile(long N, int L) { return (N + L + LIM_TILE - 1) / LIM_TILE; }
 
 int lim_prepare() {
@@ -492,7 +488,7 @@ int dasp_limiter_forward(const float* x, const float* ctl, float* y, float* gain
     else
         hipLaunchKernelGGL(limiter_forward_kernel<false>, grid, block, sizeof(LimLds), (hipStream_t)stream, x, ctl, y, gain, winner, N, nt, C, lookahead,
                            sample_rate, (float)eps);
-    return lim_check();
+    return launch_status();
 }
 
 int dasp_limiter_backward(const float* x, const float* ctl, const float* gain, const int* winner, const float* gy, float* gx, float* gctl,
@@ -502,10 +498,10 @@ int dasp_limiter_backward(const float* x, const float* ctl, const float* gain, c
     if (s != DASP_OK) return s;
     if ((s = lim_prepare()) != DASP_OK) return s;
     const hipStream_t st = (hipStream_t)stream;
-    if (zero_async(scratch, (size_t)B * N * 2 * sizeof(float), st) != hipSuccess) return lim_check();
+    if (zero_async(scratch, (size_t)B * N * 2 * sizeof(float), st) != hipSuccess) return launch_status();
     hipLaunchKernelGGL(limiter_backward_kernel, dim3((unsigned)B), dim3(LIM_THREADS), sizeof(LimLds), st, x, ctl, gain, winner, gy, gx, gctl,
                        reinterpret_cast<f2*>(scratch), N, (int)lim_ntile(N, lookahead), C, lookahead, sample_rate, (float)eps);
-    return lim_check();
+    return launch_status();
 }
 
 }  // extern "C"

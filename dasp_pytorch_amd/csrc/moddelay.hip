@@ -33,7 +33,7 @@
 //      on a word whenever the delay grows, p advancing by less than one per sample, so no schedule of the n is free of collisions.)
 //   A finalize kernel adds the partials of an item over its channels and tiles in float64, in a fixed order, and applies the chain rule
 //   through d: y and the control gradients are bit-identical run to run, and an item gives the same bits alone and inside a batch.
-#include "common.hpp"
+#include "row_helpers.hpp"
 
 namespace dasp {
 
@@ -46,7 +46,6 @@ constexpr int MD_PART = 4;                   // partials per voice
 struct MdCfg { double k, sr, dmax, spread; };                // k = sr / 1000 (samples per ms), dmax = k max_delay_ms
 struct MdVoice { double delay, depth, rate, phase; };
 struct MdPos { int i; float f; bool inside; };              // i relative to t0; inside: d was not clamped
-struct MdW { float a, b, c, d; };                            // weights of x[i-1], x[i], x[i+1], x[i+2]
 
 __device__ __forceinline__ MdVoice md_voice(const float* __restrict__ ctl, int b, int V, int v) {
     const float* q = ctl + ((size_t)b * V + v) * 4;
@@ -78,16 +77,6 @@ __device__ __forceinline__ MdPos md_pos(int nrel, double sn, const MdVoice& vc, 
     r.inside = !(raw < 0.0 || raw > g.dmax);               // a NaN is not a clamped sample: it reaches the gradients
     return r;
 }
-
-__device__ __forceinline__ MdW md_weights(float f) {
-    const float f2 = f * f;
-    return MdW{0.5f * f * ((2.f - f) * f - 1.f), 0.5f * ((3.f * f - 5.f) * f2 + 2.f), 0.5f * f * ((4.f - 3.f * f) * f + 1.f), 0.5f * f2 * (f - 1.f)};
-}
-__device__ __forceinline__ MdW md_dweights(float f) {
-    return MdW{0.5f * ((4.f - 3.f * f) * f - 1.f), 0.5f * f * (9.f * f - 10.f), 0.5f * ((8.f - 9.f * f) * f + 1.f), 0.5f * f * (3.f * f - 2.f)};
-}
-// all four products, always: a NaN or inf sample under a zero weight is a NaN
-__device__ __forceinline__ float md_dot(const MdW& w, const float* xs) { return w.a * xs[0] + w.b * xs[1] + w.c * xs[2] + w.d * xs[3]; }
 
 // word of x[i - 1] in the staged window that starts at t0 - H - 1; the bound holds by construction (0 <= d <= H) and is enforced all the same
 __device__ __forceinline__ int md_word(int i, int H, int T) { return min(max(i + H, 0), T + H - 1); }
@@ -128,7 +117,7 @@ moddelay_forward_kernel(const float* __restrict__ x, const float* __restrict__ c
 #pragma unroll
         for (int m = 0; m < TPT; ++m) {
             const MdPos p = md_pos(tid + MD_THREADS * m, s, vc, g);
-            wet[m] += md_dot(md_weights(p.f), xs + md_word(p.i, H, T));
+            wet[m] += cr_dot(cr_weights(p.f), xs + md_word(p.i, H, T));
             md_turn(s, c, ss, sc);
         }
     }
@@ -186,13 +175,13 @@ moddelay_backward_kernel(const float* __restrict__ x, const float* __restrict__ 
             const MdPos p = md_pos(nrel, s, vc, g);
             const float* xs = buf + md_word(p.i, H, T);
             const float gv = own[nrel];
-            const float t = (valid && p.inside) ? -gv * md_dot(md_dweights(p.f), xs) : 0.f;
+            const float t = (valid && p.inside) ? -gv * cr_dot(cr_dweights(p.f), xs) : 0.f;
             const float tc = t * (float)c;
             a0 += t;
             a1 = __builtin_fmaf(t, (float)s, a1);
             a2 += tc;
             a3 = __builtin_fmaf(tc, (float)nrel, a3);
-            accm += valid ? gv * md_dot(md_weights(p.f), xs) : 0.f;
+            accm += valid ? gv * cr_dot(cr_weights(p.f), xs) : 0.f;
             if (v == 0) accx += valid ? gv * buf[nrel + H + 1] : 0.f;
             md_turn(s, c, ss, sc);
         }
@@ -235,7 +224,7 @@ moddelay_backward_kernel(const float* __restrict__ x, const float* __restrict__ 
             const long n = t0 + nrel;
             if (n >= 0 && n < N) {
                 const MdPos p = md_pos(nrel, s, vc, g);
-                const MdW w = md_weights(p.f);
+                const CrW w = cr_weights(p.f);
                 const float gv = buf[nrel + MD_GPAD];
                 const int j = p.i - 1;
                 if ((unsigned)j < (unsigned)T) __hip_atomic_fetch_add(own + j, w.a * gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -291,10 +280,6 @@ __global__ void moddelay_finalize_kernel(const float* __restrict__ partials, con
 using namespace dasp;
 
 namespace {
-inline int md_check() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DASP_OK : (int)e;
-}
 inline bool md_h_ok(int H) { return H >= 1 && H <= MD_HMAX; }
 inline int md_tile(int H) { return H <= MD_HMAX / 2 ? 4096 : 2048; }          // 2 T + H + 6 floats of backward LDS: 48 KiB at both ends
 inline long md_ntile(long N, int H) { return (N + md_tile(H) - 1) / md_tile(H); }
@@ -316,17 +301,17 @@ int md_launch(const float* x, const float* ctl, const float* mix, const float* g
         const size_t lds = (size_t)(T + H + 3) * sizeof(float);
         if (T == 4096) hipLaunchKernelGGL(moddelay_forward_kernel<16>, grid, block, lds, st, x, ctl, mix, out, N, (int)nt, C, V, H, g);
         else hipLaunchKernelGGL(moddelay_forward_kernel<8>, grid, block, lds, st, x, ctl, mix, out, N, (int)nt, C, V, H, g);
-        return md_check();
+        return launch_status();
     }
     const size_t lds = (size_t)(2 * T + H + 2 * MD_GPAD) * sizeof(float);
     if (T == 4096) hipLaunchKernelGGL(moddelay_backward_kernel<16>, grid, block, lds, st, x, ctl, mix, gy, out, partials, N, (int)nt, C, V, H, g);
     else hipLaunchKernelGGL(moddelay_backward_kernel<8>, grid, block, lds, st, x, ctl, mix, gy, out, partials, N, (int)nt, C, V, H, g);
-    const int s = md_check();
+    const int s = launch_status();
     if (s != DASP_OK) return s;
     const long nfin = (long)B * (V + 1);
     hipLaunchKernelGGL(moddelay_finalize_kernel, dim3((unsigned)((nfin + 127) / 128)), dim3(128), 0, st, (const float*)partials, ctl, mix, gctl, gmix,
                        B, C, V, (int)nt, T, g);
-    return md_check();
+    return launch_status();
 }
 }  // namespace
 

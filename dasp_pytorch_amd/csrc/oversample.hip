@@ -19,7 +19,7 @@
 // The backward kernel writes one partial of sum s u per (row, tile) over the q the tile owns, [t0, t0 + T): every m is counted once; a
 // finalize kernel adds them in fp64. No atomics, no waiting between workgroups: results are bit-identical run to run, and a row gives the
 // same bits alone and inside a batch.
-#include "common.hpp"
+#include "row_helpers.hpp"
 
 namespace dasp {
 
@@ -182,10 +182,6 @@ __global__ void osdist_finalize_kernel(const float* __restrict__ partials, const
 using namespace dasp;
 
 namespace {
-inline int os_check() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DASP_OK : (int)e;
-}
 inline bool os_factor_ok(int L) { return L == 2 || L == 4 || L == 8; }
 inline int os_tile(int L) { return OS_SLOTS / L - 2 * OS_HMAX; }
 inline long os_ntile(long N, int L) { return (N + os_tile(L) - 1) / os_tile(L); }
@@ -210,11 +206,11 @@ int os_launch(const float* x, const float* drive_db, const float* taps, const fl
 #define DASP_OS_LAUNCH(LL) hipLaunchKernelGGL((osdist_kernel<LL, BWD>), grid, block, 0, st, x, drive_db, t, gy, out, partials, N, (int)nt, H)
     if (L == 2) DASP_OS_LAUNCH(2); else if (L == 4) DASP_OS_LAUNCH(4); else DASP_OS_LAUNCH(8);
 #undef DASP_OS_LAUNCH
-    int s = os_check();
+    int s = launch_status();
     if (s != DASP_OK || !BWD) return s;
     hipLaunchKernelGGL(osdist_finalize_kernel, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, st, (const float*)partials, drive_db, gdrive, rows,
                        (int)nt);
-    return os_check();
+    return launch_status();
 }
 }  // namespace
 

@@ -40,7 +40,7 @@
 // LDS: forward 18 KiB; backward (K + 4) rows of 8 KiB and 18 KiB of staging, 146 KiB at K = 12 - dynamic, the limit raised once per device.
 #include <atomic>
 
-#include "common.hpp"
+#include "row_helpers.hpp"
 
 namespace dasp {
 
@@ -88,21 +88,6 @@ __device__ __forceinline__ PhLfo ph_lfo(const PhItem& it, const PhCfg& g, long n
     return r;
 }
 
-__device__ __forceinline__ int ph_word(int i) { return i + i / PH_SPT; }
-
-// The barrier of the stages: what the waves exchange goes through LDS only, so a wave waits for its own LDS operations and no more
-// (__syncthreads() also waits for every global store issued so far and for the loads of the next tile).
-__device__ __forceinline__ void ph_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-// v of the lane DPP names, or 1 where there is none (lanes shifted in from outside a row, rows the mask leaves out)
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_or_one(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0x3f800000, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
-}
-
 // What the K scans of a tile share. q[j]: product of p over the thread's samples up to j. m[d]: product of p over the lanes that the
 // lane's partial result covers before scan step d. ep: product over the lanes before this one in its wave. wp: over the whole wave.
 struct PhShare { float q[PH_SPT], m[6], ep, wp; };
@@ -136,7 +121,7 @@ __device__ __forceinline__ float ph_scan(float run, const PhShare& sh, float car
     float excl = shift_up(agg, 1);
     if (lane == 0) excl = 0.f;
     if (lane == 63) { wt[2 * wv] = agg; wt[2 * wv + 1] = sh.wp; }
-    ph_lds_barrier();
+    lds_barrier();
     float cw = carry;                                    // the state before the wave's first sample
     for (int u = 0; u < wv; ++u) cw = __builtin_fmaf(wt[2 * u + 1], cw, wt[2 * u]);
     return __builtin_fmaf(sh.ep, cw, excl);
@@ -169,6 +154,7 @@ __device__ __forceinline__ float ph_stage(float (&cur)[PH_SPT], float (&d)[PH_SP
 }
 
 // x of a tile, a lane per consecutive sample, one tile ahead of its use; what lies past the row is zero. h: x before the tile (thread 0).
+// (The loop is stage_load's, written out: as a call to it the kernels compile to other code, see row_helpers.hpp's rule.)
 __device__ __forceinline__ void ph_load(float (&o)[PH_SPT], float& h, const float* __restrict__ p, long t0, long N, int tid) {
     const bool live = t0 >= 0 && t0 < N;
 #pragma unroll
@@ -179,10 +165,6 @@ __device__ __forceinline__ void ph_load(float (&o)[PH_SPT], float& h, const floa
     }
     const float v = p[live && t0 > 0 ? t0 - 1 : 0];
     h = live && t0 > 0 ? v : 0.f;
-}
-__device__ __forceinline__ void ph_put(float* st, const float (&v)[PH_SPT], int tid) {
-#pragma unroll
-    for (int m = 0; m < PH_SPT; ++m) st[ph_word(tid + PH_THREADS * m)] = v[m];
 }
 
 template <bool SAVE>
@@ -209,20 +191,20 @@ phaser_forward_kernel(const float* __restrict__ x, const float* __restrict__ ctl
     int par = 0, sc = 0;
     for (int ti = 0; ti < ntile; ++ti) {
         const long t0 = (long)ti * PH_TILE;
-        ph_put(xs, xn, tid);
+        stage_put<PH_SPT, PH_THREADS>(xs, xn, tid);
         if (tid == 0) halo = hn;
         ph_load(xn, hn, xr, t0 + PH_TILE, N, tid);
-        ph_lds_barrier();
+        lds_barrier();
 
         float cur[PH_SPT], a[PH_SPT], p[PH_SPT], none[PH_SPT];
         const int i0 = tid * PH_SPT;
 #pragma unroll
         for (int j = 0; j < PH_SPT; ++j) {
-            cur[j] = xs[ph_word(i0 + j)];
+            cur[j] = xs[stage_word<PH_SPT>(i0 + j)];
             a[j] = t0 + i0 + j < N ? ph_lfo<false>(it, g, t0 + i0 + j).a : 0.f;
             p[j] = -a[j];
         }
-        float cprev = tid ? xs[ph_word(i0 - 1)] : halo;
+        float cprev = tid ? xs[stage_word<PH_SPT>(i0 - 1)] : halo;
         PhShare sh;
         ph_share(sh, p);
         const bool more = ti + 1 < ntile;
@@ -234,10 +216,10 @@ phaser_forward_kernel(const float* __restrict__ x, const float* __restrict__ ctl
             }
         }
 #pragma unroll
-        for (int j = 0; j < PH_SPT; ++j) ys[ph_word(i0 + j)] = __builtin_fmaf(mix, cur[j], dry * xs[ph_word(i0 + j)]);
-        ph_lds_barrier();
+        for (int j = 0; j < PH_SPT; ++j) ys[stage_word<PH_SPT>(i0 + j)] = __builtin_fmaf(mix, cur[j], dry * xs[stage_word<PH_SPT>(i0 + j)]);
+        lds_barrier();
         const int Tc = (int)min((long)PH_TILE, N - t0);
-        for (int i = tid; i < Tc; i += PH_THREADS) st_stream(yr + t0 + i, ys[ph_word(i)]);
+        for (int i = tid; i < Tc; i += PH_THREADS) st_stream(yr + t0 + i, ys[stage_word<PH_SPT>(i)]);
         par ^= 1;
     }
 }
@@ -274,14 +256,14 @@ phaser_backward_kernel(const float* __restrict__ x, const float* __restrict__ ct
     for (int ti = ntile - 1; ti >= 0; --ti) {
         const long t0 = (long)ti * PH_TILE;
         float gv[PH_SPT];
-        ph_put(s1, xn, tid);
+        stage_put<PH_SPT, PH_THREADS>(s1, xn, tid);
         if (tid == 0) halo = hn;
         if (tid < K) cst[tid] = ti ? sr[(size_t)ti * K + tid] : 0.f;
 #pragma unroll
         for (int m = 0; m < PH_SPT; ++m) gv[m] = gn[m];
         ph_load(xn, hn, xr, t0 - PH_TILE, N, tid);
         ph_load(gn, unused, gr, t0 - PH_TILE, N, tid);
-        ph_lds_barrier();
+        lds_barrier();
 
         // ---- phase 1, forward time: thread tid has the samples 8 tid + j
         {
@@ -289,7 +271,7 @@ phaser_backward_kernel(const float* __restrict__ x, const float* __restrict__ ct
             const int i0 = tid * PH_SPT;
 #pragma unroll
             for (int j = 0; j < PH_SPT; ++j) {
-                x0[j] = cur[j] = s1[ph_word(i0 + j)];
+                x0[j] = cur[j] = s1[stage_word<PH_SPT>(i0 + j)];
                 PhLfo l{0.f, 0.f, 0.f, 0.f};
                 if (t0 + i0 + j < N) l = ph_lfo<true>(it, g, t0 + i0 + j);
                 a[j] = l.a;
@@ -297,7 +279,7 @@ phaser_backward_kernel(const float* __restrict__ x, const float* __restrict__ ct
                 const int wd = PH_THREADS * j + tid;
                 rowA[wd] = l.a; rowC[wd] = l.wc; rowD[wd] = l.wd; rowT[wd] = l.wt;
             }
-            float cprev = tid ? s1[ph_word(i0 - 1)] : halo;
+            float cprev = tid ? s1[stage_word<PH_SPT>(i0 - 1)] : halo;
             PhShare sh;
             ph_share(sh, p);
             for (int k = 0; k < K; ++k, sc ^= 1) {
@@ -306,10 +288,10 @@ phaser_backward_kernel(const float* __restrict__ x, const float* __restrict__ ct
                 for (int j = 0; j < PH_SPT; ++j) rowK[(size_t)k * PH_TILE + PH_THREADS * j + tid] = d[j];
             }
 #pragma unroll
-            for (int j = 0; j < PH_SPT; ++j) s2[ph_word(i0 + j)] = cur[j] - x0[j];
+            for (int j = 0; j < PH_SPT; ++j) s2[stage_word<PH_SPT>(i0 + j)] = cur[j] - x0[j];
         }
-        ph_put(s1, gv, tid);                             // every thread read its x before the barrier of the first stage
-        ph_lds_barrier();
+        stage_put<PH_SPT, PH_THREADS>(s1, gv, tid);                             // every thread read its x before the barrier of the first stage
+        lds_barrier();
 
         // ---- phase 2, reverse time: thread tid has the run of thread f = 255 - tid; m = 0 is its last sample, j = 7 - m
         {
@@ -319,8 +301,8 @@ phaser_backward_kernel(const float* __restrict__ x, const float* __restrict__ ct
 #pragma unroll
             for (int m = 0; m < PH_SPT; ++m) {
                 const int j = PH_SPT - 1 - m;
-                gq[m] = s1[ph_word(i0 + j)];
-                t_mix = __builtin_fmaf(gq[m], t0 + i0 + j < N ? s2[ph_word(i0 + j)] : 0.f, t_mix);
+                gq[m] = s1[stage_word<PH_SPT>(i0 + j)];
+                t_mix = __builtin_fmaf(gq[m], t0 + i0 + j < N ? s2[stage_word<PH_SPT>(i0 + j)] : 0.f, t_mix);
                 gs[m] = mix * gq[m];
                 a[m] = rowA[PH_THREADS * j + f];
                 ga[m] = 0.f;
@@ -351,7 +333,7 @@ phaser_backward_kernel(const float* __restrict__ x, const float* __restrict__ ct
             for (int m = 0; m < PH_SPT; ++m) {
                 const int j = PH_SPT - 1 - m, wd = PH_THREADS * j + f;
                 const bool valid = t0 + i0 + j < N;
-                s2[ph_word(i0 + j)] = __builtin_fmaf(dry, gq[m], gs[m]);
+                s2[stage_word<PH_SPT>(i0 + j)] = __builtin_fmaf(dry, gq[m], gs[m]);
                 const float wc = rowC[wd], wdp = rowD[wd], wth = rowT[wd];
                 const float tt = valid ? ga[m] * wth : 0.f;
                 t_c += valid ? ga[m] * wc : 0.f;
@@ -362,10 +344,10 @@ phaser_backward_kernel(const float* __restrict__ x, const float* __restrict__ ct
             s_center += (double)t_c; s_depth += (double)t_d; s_phase += (double)t_t; s_mix += (double)t_mix;
             s_rate += (double)t_r + (double)t0 * (double)t_t;
         }
-        ph_lds_barrier();
+        lds_barrier();
         if (gxr) {
             const int Tc = (int)min((long)PH_TILE, N - t0);
-            for (int i = tid; i < Tc; i += PH_THREADS) st_stream(gxr + t0 + i, s2[ph_word(i)]);
+            for (int i = tid; i < Tc; i += PH_THREADS) st_stream(gxr + t0 + i, s2[stage_word<PH_SPT>(i)]);
         }
         par ^= 1;
     }
@@ -411,10 +393,6 @@ __global__ void phaser_finalize_kernel(const float* __restrict__ partials, const
 using namespace dasp;
 
 namespace {
-inline int ph_check() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DASP_OK : (int)e;
-}
 inline bool ph_k_ok(int K) { return K >= 1 && K <= PH_KMAX; }
 inline long ph_ntile(long N) { return (N + PH_TILE - 1) / PH_TILE; }
 inline size_t ph_lds_bytes(int K) { return (size_t)(K + 4) * PH_TILE * sizeof(float); }
@@ -466,7 +444,7 @@ int dasp_phaser_forward(const float* x, const float* ctl, float* y, float* state
     const int nt = (int)ph_ntile(N);
     if (states) hipLaunchKernelGGL(phaser_forward_kernel<true>, grid, block, 0, (hipStream_t)stream, x, ctl, y, states, N, nt, C, stages, g);
     else hipLaunchKernelGGL(phaser_forward_kernel<false>, grid, block, 0, (hipStream_t)stream, x, ctl, y, states, N, nt, C, stages, g);
-    return ph_check();
+    return launch_status();
 }
 
 int dasp_phaser_backward(const float* x, const float* ctl, const float* states, const float* gy, float* gx, float* gctl, float* partials, int B,
@@ -479,9 +457,9 @@ int dasp_phaser_backward(const float* x, const float* ctl, const float* states, 
     const hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(phaser_backward_kernel, dim3((unsigned)((long)B * C)), dim3(PH_THREADS), ph_lds_bytes(stages), st, x, ctl, states, gy, gx,
                        partials, N, (int)ph_ntile(N), C, stages, g);
-    if ((s = ph_check()) != DASP_OK) return s;
+    if ((s = launch_status()) != DASP_OK) return s;
     hipLaunchKernelGGL(phaser_finalize_kernel, dim3((unsigned)((B + 127) / 128)), dim3(128), 0, st, (const float*)partials, ctl, gctl, B, C, g);
-    return ph_check();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -24,7 +24,7 @@
 // the outputs whose span covers it. No atomics, no scratch, nothing saved between the directions.
 #include <atomic>
 
-#include "common.hpp"
+#include "row_helpers.hpp"
 
 namespace dasp {
 
@@ -146,10 +146,6 @@ __global__ void __launch_bounds__(RS_THREADS) resample_fill_kernel(unsigned* __r
 using namespace dasp;
 
 namespace {
-inline int rs_check() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DASP_OK : (int)e;
-}
 inline size_t rs_lds_bytes(int A, int B, int P, int span, int F) { return ((size_t)rs_tab_words(A, P) + A + rs_window(F, B, span)) * sizeof(float); }
 
 // The table and the window together are more LDS than a kernel gets unasked (64 KiB): asked for once per device - by
@@ -209,7 +205,7 @@ int dasp_resample_table_store(void* dst, const void* host_words, long words, voi
         RsFill f = {};
         for (int i = 0; i < count; ++i) f.w[i] = src[at + i];
         hipLaunchKernelGGL(resample_fill_kernel, dim3(1), dim3(RS_THREADS), 0, (hipStream_t)stream, static_cast<unsigned*>(dst) + at, f, count);
-        const int s = rs_check();
+        const int s = launch_status();
         if (s != DASP_OK) return s;
     }
     return DASP_OK;
@@ -224,7 +220,7 @@ int dasp_resample_forward(const float* x, const void* table, float* y, long rows
     if (s != DASP_OK) return s;
     hipLaunchKernelGGL(resample_forward_kernel, dim3((unsigned)(rows * tiles)), dim3(RS_THREADS), rs_lds_bytes(new_, orig, taps, span, F),
                        (hipStream_t)stream, x, static_cast<const unsigned*>(table), y, N, M, orig, new_, taps, lo, span, F, tiles);
-    return rs_check();
+    return launch_status();
 }
 
 int dasp_resample_backward(const float* gy, const void* table, float* gx, long rows, long N, long M, int orig, int new_, int taps, int lo, int span,
@@ -236,7 +232,7 @@ int dasp_resample_backward(const float* gy, const void* table, float* gx, long r
     if (s != DASP_OK) return s;
     hipLaunchKernelGGL(resample_backward_kernel, dim3((unsigned)(rows * tiles)), dim3(RS_THREADS), rs_lds_bytes(orig, new_, taps, span, F),
                        (hipStream_t)stream, gy, static_cast<const unsigned*>(table), gx, N, M, orig, new_, taps, lo, span, F, tiles);
-    return rs_check();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -33,7 +33,7 @@
 // the walk carried along. A finalize kernel adds an item's channels in float64 and applies dG/dcutoff and dK/dq in float64, exactly
 // zero where the frame value was clamped. No atomics anywhere: every result is bit-identical run to run and for an item alone or in a
 // batch. Backward traffic: 12 B per sample. LDS: forward 20 KiB, backward 31 KiB.
-#include "common.hpp"
+#include "row_helpers.hpp"
 
 namespace dasp {
 
@@ -49,14 +49,6 @@ constexpr int TV_HOP_MIN = 8, TV_HOP_MAX = TV_TILE;
 // d2, dl, dx: w - x = m1 k v1 + d2 v2 + dl (a2 ic1 - a1 (1 + g k) v3) + dx x, the form without the cancellation of a pass band (tv_cfg)
 struct TvCfg { double wk, flo, fhi; float m1, m2, mx, d2, dl, dx, inv_hop; int hop, lg; };
 struct TvMap { float a, b, c, d, u, v; };             // z -> [[a, b], [c, d]] z + (u, v)
-
-__device__ __forceinline__ int tv_word(int i) { return i + i / TV_SPT; }
-
-__device__ __forceinline__ void tv_lds_barrier() {   // what the waves exchange goes through LDS only (csrc/phaser.hip)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 __device__ __forceinline__ double tv_clamp(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }   // a NaN stays
 
@@ -121,13 +113,9 @@ __device__ __forceinline__ TvMap tv_after(const TvMap& L, const TvMap& E) {     
     return r;
 }
 
-// v of the lane DPP names, or 1 where there is none (lanes shifted in from outside a row, rows the mask leaves out)
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ float tv_dpp_or_one(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0x3f800000, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
-}
 // the map of the lane DPP names, or the identity
 template <int CTRL, int ROW_MASK> __device__ __forceinline__ TvMap tv_dpp(const TvMap& m) {
-    return TvMap{tv_dpp_or_one<CTRL, ROW_MASK>(m.a), dpp_or_zero<CTRL, ROW_MASK>(m.b), dpp_or_zero<CTRL, ROW_MASK>(m.c), tv_dpp_or_one<CTRL, ROW_MASK>(m.d),
+    return TvMap{dpp_or_one<CTRL, ROW_MASK>(m.a), dpp_or_zero<CTRL, ROW_MASK>(m.b), dpp_or_zero<CTRL, ROW_MASK>(m.c), dpp_or_one<CTRL, ROW_MASK>(m.d),
                  dpp_or_zero<CTRL, ROW_MASK>(m.u), dpp_or_zero<CTRL, ROW_MASK>(m.v)};
 }
 
@@ -148,7 +136,7 @@ __device__ __forceinline__ void tv_scan(const TvMap& run, float c1, float c2, fl
         float* w = wt + 6 * wv;
         w[0] = agg.a; w[1] = agg.b; w[2] = agg.c; w[3] = agg.d; w[4] = agg.u; w[5] = agg.v;
     }
-    tv_lds_barrier();
+    lds_barrier();
     for (int u = 0; u < wv; ++u) {                      // the state before the wave's first sample
         const float* w = wt + 6 * u;
         const float n1 = __builtin_fmaf(w[0], c1, __builtin_fmaf(w[1], c2, w[4]));
@@ -170,21 +158,6 @@ __device__ __forceinline__ TvMap tv_run_map(const float (&x)[TV_SPT], const TvRu
         tv_step(z1, z2, x[j], c.a1[j], c.a2[j], c.a3[j], v1, v2);
     }
     return TvMap{e1, f1, e2, f2, z1, z2};
-}
-
-// x of a tile, a lane per consecutive sample, one tile ahead of its use; what lies past the row is zero.
-__device__ __forceinline__ void tv_load(float (&o)[TV_SPT], const float* __restrict__ p, long t0, long N, int tid) {
-    const bool live = t0 >= 0 && t0 < N;
-#pragma unroll
-    for (int m = 0; m < TV_SPT; ++m) {
-        const long n = t0 + tid + TV_THREADS * m;
-        const float v = p[live ? min(n, N - 1) : 0];
-        o[m] = live && n < N ? v : 0.f;
-    }
-}
-__device__ __forceinline__ void tv_put(float* st, const float (&v)[TV_SPT], int tid) {
-#pragma unroll
-    for (int m = 0; m < TV_SPT; ++m) st[tv_word(tid + TV_THREADS * m)] = v[m];
 }
 
 template <bool SAVE>
@@ -209,21 +182,21 @@ tvfilter_forward_kernel(const float* __restrict__ x, const float* __restrict__ c
         if (SAVE) sr[tid] = 0.f;                         // the state before the row
     }
     float xn[TV_SPT];
-    tv_load(xn, xr, 0, N, tid);
+    stage_load<TV_SPT, TV_THREADS>(xn, xr, 0, N, tid);
     int par = 0;
     for (int ti = 0; ti < ntile; ++ti) {
         const long t0 = (long)ti * TV_TILE;
-        tv_put(xs, xn, tid);
+        stage_put<TV_SPT, TV_THREADS>(xs, xn, tid);
         tv_frames(Gs, Ks, cr, qr, t0 >> g.lg, nint + 1, F, g, tid);
-        tv_load(xn, xr, t0 + TV_TILE, N, tid);
-        tv_lds_barrier();
+        stage_load<TV_SPT, TV_THREADS>(xn, xr, t0 + TV_TILE, N, tid);
+        lds_barrier();
 
         const int i0 = tid * TV_SPT;
         float xv[TV_SPT];
         TvRun c;
         tv_coef(c, Gs, Ks, i0, g);
 #pragma unroll
-        for (int j = 0; j < TV_SPT; ++j) xv[j] = xs[tv_word(i0 + j)];
+        for (int j = 0; j < TV_SPT; ++j) xv[j] = xs[stage_word<TV_SPT>(i0 + j)];
         float z1, z2;
         tv_scan(tv_run_map(xv, c), carry[par][0], carry[par][1], wt, z1, z2);
 #pragma unroll
@@ -231,16 +204,16 @@ tvfilter_forward_kernel(const float* __restrict__ x, const float* __restrict__ c
             float v1, v2;
             tv_step(z1, z2, xv[j], c.a1[j], c.a2[j], c.a3[j], v1, v2);
             const float w = __builtin_fmaf(g.m1 * c.k[j], v1, __builtin_fmaf(g.m2, v2, g.mx * xv[j]));
-            ys[tv_word(i0 + j)] = __builtin_fmaf(mix, w, dry * xv[j]);
+            ys[stage_word<TV_SPT>(i0 + j)] = __builtin_fmaf(mix, w, dry * xv[j]);
         }
         if (tid == TV_THREADS - 1) {
             carry[par ^ 1][0] = z1;
             carry[par ^ 1][1] = z2;
             if (SAVE && ti + 1 < ntile) { sr[(size_t)(ti + 1) * 2] = z1; sr[(size_t)(ti + 1) * 2 + 1] = z2; }
         }
-        tv_lds_barrier();
+        lds_barrier();
         const int Tc = (int)min((long)TV_TILE, N - t0);
-        for (int i = tid; i < Tc; i += TV_THREADS) st_stream(yr + t0 + i, ys[tv_word(i)]);
+        for (int i = tid; i < Tc; i += TV_THREADS) st_stream(yr + t0 + i, ys[stage_word<TV_SPT>(i)]);
         par ^= 1;
     }
 }
@@ -272,19 +245,19 @@ tvfilter_backward_kernel(const float* __restrict__ x, const float* __restrict__ 
 
     if (tid < 2) { clam[0][tid] = 0.f; edge[0][tid] = 0.0; }
     float xn[TV_SPT], gn[TV_SPT];
-    tv_load(xn, xr, (long)(ntile - 1) * TV_TILE, N, tid);
-    tv_load(gn, gr, (long)(ntile - 1) * TV_TILE, N, tid);
+    stage_load<TV_SPT, TV_THREADS>(xn, xr, (long)(ntile - 1) * TV_TILE, N, tid);
+    stage_load<TV_SPT, TV_THREADS>(gn, gr, (long)(ntile - 1) * TV_TILE, N, tid);
     double s_mix = 0.0;
     int par = 0;
     for (int ti = ntile - 1; ti >= 0; --ti) {
         const long t0 = (long)ti * TV_TILE, j0 = t0 >> g.lg;
-        tv_put(s1, xn, tid);
-        tv_put(s2, gn, tid);
+        stage_put<TV_SPT, TV_THREADS>(s1, xn, tid);
+        stage_put<TV_SPT, TV_THREADS>(s2, gn, tid);
         tv_frames(Gs, Ks, cr, qr, j0, nint + 1, F, g, tid);
         if (tid < 2) cst[tid] = ti ? sr[(size_t)ti * 2 + tid] : 0.f;
-        tv_load(xn, xr, t0 - TV_TILE, N, tid);
-        tv_load(gn, gr, t0 - TV_TILE, N, tid);
-        tv_lds_barrier();
+        stage_load<TV_SPT, TV_THREADS>(xn, xr, t0 - TV_TILE, N, tid);
+        stage_load<TV_SPT, TV_THREADS>(gn, gr, t0 - TV_TILE, N, tid);
+        lds_barrier();
 
         // ---- phase 1, forward time: the state before the run of every thread
         {
@@ -293,12 +266,12 @@ tvfilter_backward_kernel(const float* __restrict__ x, const float* __restrict__ 
             TvRun c;
             tv_coef(c, Gs, Ks, i0, g);
 #pragma unroll
-            for (int j = 0; j < TV_SPT; ++j) xv[j] = s1[tv_word(i0 + j)];
+            for (int j = 0; j < TV_SPT; ++j) xv[j] = s1[stage_word<TV_SPT>(i0 + j)];
             tv_scan(tv_run_map(xv, c), cst[0], cst[1], wt, z1, z2);
             zin[2 * tid] = z1;
             zin[2 * tid + 1] = z2;
         }
-        tv_lds_barrier();
+        lds_barrier();
 
         // ---- phase 2, reverse time: thread tid has the run of thread f = 255 - tid; m = 0 is its last sample, j = 7 - m
         float p_gl = 0.f, p_gr = 0.f, p_kl = 0.f, p_kr = 0.f, t_mix = 0.f;
@@ -311,8 +284,8 @@ tvfilter_backward_kernel(const float* __restrict__ x, const float* __restrict__ 
             float z1 = zin[2 * f], z2 = zin[2 * f + 1];
 #pragma unroll
             for (int j = 0; j < TV_SPT; ++j) {
-                xv[j] = s1[tv_word(i0 + j)];
-                gv[j] = s2[tv_word(i0 + j)];
+                xv[j] = s1[stage_word<TV_SPT>(i0 + j)];
+                gv[j] = s2[stage_word<TV_SPT>(i0 + j)];
                 zp1[j] = z1;
                 zp2[j] = z2;
                 float v2;
@@ -338,7 +311,7 @@ tvfilter_backward_kernel(const float* __restrict__ x, const float* __restrict__ 
                 const float gw = mix * gv[j];
                 float q1, q2, gv3, n1, n2;
                 tv_adj(l1, l2, gw, c.k[j], c.a1[j], c.a2[j], c.a3[j], g, q1, q2, gv3, n1, n2);
-                s2[tv_word(i0 + j)] = __builtin_fmaf(dry, gv[j], __builtin_fmaf(gw, g.mx, gv3));
+                s2[stage_word<TV_SPT>(i0 + j)] = __builtin_fmaf(dry, gv[j], __builtin_fmaf(gw, g.mx, gv3));
                 const float v3 = xv[j] - zp2[j];
                 const float ga3 = q2 * v3;
                 const float ga2 = __builtin_fmaf(c.g[j], ga3, __builtin_fmaf(q1, v3, q2 * zp1[j]));
@@ -372,7 +345,7 @@ tvfilter_backward_kernel(const float* __restrict__ x, const float* __restrict__ 
                 o[0] = d0; o[1] = d1; o[2] = d2; o[3] = d3;
             }
         }
-        tv_lds_barrier();
+        lds_barrier();
         // frame point i of the tile: the interval before it, then its own, then - on the tile's end - what the later tile carried
         for (int i = tid; i <= nint; i += TV_THREADS) {
             double sg = 0.0, sk = 0.0;
@@ -391,9 +364,9 @@ tvfilter_backward_kernel(const float* __restrict__ x, const float* __restrict__ 
         }
         if (gxr) {
             const int Tc = (int)min((long)TV_TILE, N - t0);
-            for (int i = tid; i < Tc; i += TV_THREADS) st_stream(gxr + t0 + i, s2[tv_word(i)]);
+            for (int i = tid; i < Tc; i += TV_THREADS) st_stream(gxr + t0 + i, s2[stage_word<TV_SPT>(i)]);
         }
-        tv_lds_barrier();                                // red, s1, s2 and zin are written again by the next tile
+        lds_barrier();                                // red, s1, s2 and zin are written again by the next tile
         par ^= 1;
     }
     s_mix = wave_sum(s_mix);
@@ -440,10 +413,6 @@ __global__ void tvfilter_finalize_kernel(const float* __restrict__ partials, con
 using namespace dasp;
 
 namespace {
-inline int tv_check() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? DASP_OK : (int)e;
-}
 inline long tv_ntile(long N) { return (N + TV_TILE - 1) / TV_TILE; }
 inline bool tv_hop_pow2(int hop) { return hop > 0 && (hop & (hop - 1)) == 0; }
 inline bool tv_hop_ok(int hop) { return tv_hop_pow2(hop) && hop >= TV_HOP_MIN && hop <= TV_HOP_MAX; }
@@ -492,7 +461,7 @@ int dasp_tvfilter_forward(const float* x, const float* cutoff_hz, const float* q
     const long F = tv_frames_of(N, hop);
     if (states) hipLaunchKernelGGL(tvfilter_forward_kernel<true>, grid, block, 0, (hipStream_t)stream, x, cutoff_hz, q, mix, y, states, N, nt, C, F, g);
     else hipLaunchKernelGGL(tvfilter_forward_kernel<false>, grid, block, 0, (hipStream_t)stream, x, cutoff_hz, q, mix, y, states, N, nt, C, F, g);
-    return tv_check();
+    return launch_status();
 }
 
 int dasp_tvfilter_backward(const float* x, const float* cutoff_hz, const float* q, const float* mix, const float* states, const float* gy, float* gx,
@@ -506,10 +475,10 @@ int dasp_tvfilter_backward(const float* x, const float* cutoff_hz, const float* 
     const long F = tv_frames_of(N, hop);
     hipLaunchKernelGGL(tvfilter_backward_kernel, dim3((unsigned)((long)B * C)), dim3(TV_THREADS), 0, st, x, cutoff_hz, q, mix, states, gy, gx, scratch, N,
                        (int)tv_ntile(N), C, F, g);
-    if ((s = tv_check()) != DASP_OK) return s;
+    if ((s = launch_status()) != DASP_OK) return s;
     hipLaunchKernelGGL(tvfilter_finalize_kernel, dim3((unsigned)(((long)B * F + 127) / 128)), dim3(128), 0, st, (const float*)scratch, cutoff_hz, q, mix,
                        gcutoff, gq, gmix, B, C, F, g);
-    return tv_check();
+    return launch_status();
 }
 
 }  // extern "C"

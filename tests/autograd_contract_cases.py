@@ -49,6 +49,13 @@ def as_np(v):
     return v.astype(np.float64)
 
 
+def peak_err(a, b):
+    """Largest difference relative to the peak of b: the measure of the fused effects' parity tests."""
+    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
+    assert a.shape == b.shape
+    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+
+
 def errors(kind, got, ref):
     """-> (error, scale) arrays: the bound asks error <= b * scale."""
     d = np.abs(got - ref)
@@ -538,6 +545,75 @@ def measured_bound(name, arrays, call, leaves, audio, reaches, ref, floors, **kw
     return spec
 
 
+def delay_filter_limiter_entries():
+    """feedback_delay, fdn_reverb, limiter, phaser, time_varying_filter and resample at (3, 2, 1501), every one against its float64
+    restatement at its parity test's bound: 4 x the error of the restatement in float32 arithmetic, never below the op's FLOOR (which
+    lives beside the restatement: tests/<op>_restated.py)."""
+    from tests import fdn_reverb_restated as FDN, feedback_delay_restated as FB, limiter_restated as LIM, phaser_restated as PH
+    from tests import resample_restated as RS, tvfilter_restated as TV
+    out = []
+    sr, N = 8000, 1501
+
+    def entry(name, R, salt, draw, call, restate, reaches, cite, ctl, names=None, forms=None, **kw):
+        """draw(u, g) -> the inputs, u(lo, hi, *shape) uniform from the generator g; restate(a, w, **arith) -> R.forward_backward's dict."""
+        names = dict(zip(names or R.NAMES, ("y0", "g_x") + tuple("g_" + k for k in ctl)))
+        floor = R.FLOOR if isinstance(R.FLOOR, dict) else dict.fromkeys(names, R.FLOOR)
+
+        def arrays(seed):
+            g = gen(seed, salt)
+            return draw(lambda lo, hi, *s: torch.rand(*s, generator=g) * (hi - lo) + lo, g)
+
+        def ref(a, gys):
+            w = torch.from_numpy(gys[0])
+            r64, r32 = restate(a, w), restate(a, w, arith=torch.float32)
+            bound = {names[k]: max(4.0 * peak_err(r32[k], r64[k]), floor[k]) for k in names}
+            return dict({names[k]: r64[k] for k in names}, _bound=bound)
+        out.append(measured_bound(name, arrays, call, ("x",) + tuple(ctl), ("x",), reaches, ref, {names[k]: floor[k] for k in names},
+                                  forms={k: "vector" for k in ctl} if forms is None else forms, lowp=("x",), cite=cite, **kw))
+
+    mdm = 50.0
+    entry("feedback_delay", FB, 149,
+          lambda u, g: dict(x=u(-1.0, 1.0, 3, 2, N), delay_ms=u(2.0, 45.0, 3), feedback=u(-0.9, 0.9, 3), damping_hz=u(300.0, 6000.0, 3), mix=u(0.2, 1.0, 3)),
+          lambda t: D().feedback_delay(t["x"], sr, *[t[k] for k in FB.CTL], max_delay_ms=mdm),
+          lambda a, w, **kw: FB.forward_backward(a["x"], sr, *[a[k] for k in FB.CTL], w, max_delay_ms=mdm, **kw),
+          ("FeedbackDelayFunction",), "tests/test_gpu_feedback_delay.py check_parity", FB.CTL)
+    lines = (53, 71, 97)
+    entry("fdn_reverb", FDN, 151,
+          lambda u, g: dict(x=u(-1.0, 1.0, 3, 2, N), decay_s=u(0.05, 1.0, 3), damping_hz=u(300.0, 3900.0, 3), mix=u(0.2, 1.0, 3)),
+          lambda t: D().fdn_reverb(t["x"], sr, *[t[k] for k in FDN.CTL], lines),
+          lambda a, w, **kw: FDN.forward_backward(a["x"], sr, *[a[k] for k in FDN.CTL], lines, w, **kw),
+          ("FdnReverbFunction",), "tests/test_gpu_fdn_reverb.py check_parity", FDN.CTL)
+    look = 40                                       # lookahead_ms = 5 at 8 kHz
+    entry("limiter", LIM, 167,
+          lambda u, g: dict(x=0.5 * torch.randn(3, 2, N, generator=g), threshold_db=u(-20.0, -8.0, 3), release_ms=u(5.0, 100.0, 3)),
+          lambda t: D().limiter(t["x"], sr, t["threshold_db"], t["release_ms"], lookahead_ms=5.0),
+          lambda a, w, **kw: LIM.forward_backward(a["x"], sr, a["threshold_db"], a["release_ms"], w, lookahead=look, **kw),
+          ("LimiterFunction",), "tests/test_gpu_limiter.py test_parity_with_the_float64_restatement", LIM.CTL)
+    stages = 4
+    entry("phaser", PH, 163,
+          lambda u, g: dict(x=u(-1.0, 1.0, 3, 2, N), rate_hz=u(0.5, 10.0, 3), center_hz=u(100.0, 800.0, 3), depth=u(0.5, 2.0, 3), phase=u(0.0, 1.0, 3),
+                            mix=u(0.2, 1.0, 3)),
+          lambda t: D().phaser(t["x"], sr, *[t[k] for k in PH.CTL], stages=stages),
+          lambda a, w, **kw: PH.forward_backward(a["x"], sr, *[a[k] for k in PH.CTL], w, stages=stages, **kw),
+          ("PhaserFunction",), "tests/test_gpu_phaser.py test_parity_with_the_float64_restatement", PH.CTL)
+    hop, mode = 64, "bandpass"
+    F = TV.control_frames(N, hop)
+    entry("time_varying_filter", TV, 167,
+          lambda u, g: dict(x=u(-1.0, 1.0, 3, 2, N), cutoff_hz=u(100.0, 3000.0, 3, F), q=u(0.5, 8.0, 3, F), mix=u(0.2, 1.0, 3)),
+          lambda t: D().time_varying_filter(t["x"], sr, *[t[k] for k in TV.CTL], hop=hop, mode=mode),
+          lambda a, w, **kw: TV.forward_backward(a["x"], sr, *[a[k] for k in TV.CTL], w, hop, mode, **kw),
+          ("TimeVaryingFilterFunction",), "tests/test_gpu_tvfilter.py test_parity_with_the_float64_restatement", TV.CTL,
+          forms={"cutoff_hz": "matrix", "q": "matrix", "mix": "vector"})
+    o, n, shape = 147, 160, (3, 2, N)
+    M = RS.out_len(o, n, N)
+    entry("resample", RS, 151,
+          lambda u, g: dict(x=torch.rand(*shape, generator=g) * 2 - 1),
+          lambda t: D().resample(t["x"], 44100, 48000),
+          lambda a, w, **kw: RS.forward_backward(a["x"], w, o, n, **kw),
+          ("ResampleFunction",), "tests/test_gpu_resample.py check_parity", (), names=("y", "gx"), outs=lambda a: [shape[:-1] + (M,)])
+    return out
+
+
 def level_entries():
     out = []
     for name in ("one_segment", "segmented"):
@@ -770,7 +846,7 @@ def registered_ops():
 @functools.lru_cache(maxsize=1)
 def table():
     E = (idc_entries() + peq_norm_entries() + dyn_matrix_entries() + reverb_matrix_entries() + chain_controls_entries() + mix_os_delay_entries()
-         + level_entries() + spectral_entries() + loss_entries() + biquad_entries() + [stack_columns_spec(DEV)])
+         + delay_filter_limiter_entries() + level_entries() + spectral_entries() + loss_entries() + biquad_entries() + [stack_columns_spec(DEV)])
     for e in E:
         e.functions = lambda names=e.reaches: [c for n, c in package_functions().items() if n in names]
     names = [e.name for e in E]

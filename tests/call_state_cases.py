@@ -160,7 +160,7 @@ def by_name():
     return {e.name: e for e in entries()}
 
 
-# ---- entries a check leaves out: by name, with the reason (at most 5 of the table's 106 per check) --------------------------------------------
+# ---- entries a check leaves out: by name, with the reason (at most 5 of the table's 112 per check) --------------------------------------------
 
 _SEEDS = "the entry's own call() begins with torch.manual_seed(4242), which reseeds the CPU and every device generator: the test's doing, " \
          "not the library's - reverb_default_noise[...] is the same call without it"

@@ -16,6 +16,9 @@ import numpy as np
 import torch
 
 NAMES = ("y", "gx", "gdecay", "gdamping", "gmix")
+CTL = ("decay_s", "damping_hz", "mix")
+# the least the kernel's parity bound is, whatever the float32 restatement's own error: the floors of the other fused effects
+FLOOR = dict(y=2e-6, gx=2e-6, gdecay=1e-5, gdamping=1e-5, gmix=1e-5)
 
 
 def gains(sr, decay_s, delays):

@@ -88,6 +88,9 @@ def forward(x, sr, delay_ms, feedback, damping_hz, mix, max_delay_ms=500.0, arit
 
 
 NAMES = ("y", "gx", "gdelay", "gfeedback", "gdamping", "gmix")
+CTL = ("delay_ms", "feedback", "damping_hz", "mix")
+# the least the kernel's parity bound is, whatever the float32 restatement's own error: the floors of the other fused effects
+FLOOR = dict(y=2e-6, gx=2e-6, gdelay=1e-5, gfeedback=1e-5, gdamping=1e-5, gmix=1e-5)
 
 
 def forward_backward(x, sr, delay_ms, feedback, damping_hz, mix, gy, max_delay_ms=500.0, arith=torch.float64, block=512):

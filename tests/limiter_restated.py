@@ -16,6 +16,7 @@ LN9 = math.log(9.0)
 NAMES = ("y", "gx", "gthr", "grel")
 GRADS = ("gthr", "grel")
 CTL = ("threshold_db", "release_ms")
+FLOOR = dict(y=2e-6, gx=2e-6, gthr=1e-5, grel=1e-5)          # the least the kernel's parity bound is: the floors of the other fused effects
 THR_RANGE, REL_RANGE = (-120.0, 40.0), (0.1, 10000.0)
 
 

@@ -15,6 +15,8 @@ import torch
 CTL = ("rate_hz", "center_hz", "depth", "phase", "mix")
 GRADS = ("grate", "gcenter", "gdepth", "gphase", "gmix")
 NAMES = ("y", "gx") + GRADS
+# the least the kernel's parity bound is, whatever the float32 restatement's own error: the floors of the other fused effects
+FLOOR = dict(y=2e-6, gx=2e-6, grate=1e-5, gcenter=1e-5, gdepth=1e-5, gphase=1e-5, gmix=1e-5)
 
 
 def clamp_bounds(sr):

@@ -11,6 +11,7 @@ import math
 import numpy as np
 import torch
 
+FLOOR = 2e-6            # the least the kernel's parity bound is, for y and grad x alike
 KAISER_BETA = 14.769656459379492
 KAISER_FAST = dict(lowpass_filter_width=16, rolloff=0.85, resampling_method="sinc_interp_kaiser", beta=8.555504641634386)
 

@@ -158,7 +158,7 @@ def test_every_added_reference_evaluates_on_the_entry_shape(name):
 
 
 def test_the_contract_table_is_unchanged_by_the_added_entries():
-    assert len(T.table()) == 106 and len(C.entries()) == 106 + 9
+    assert len(T.table()) == 112 and len(C.entries()) == 112 + 9
     reached = {r for e in T.table() for r in e.reaches}
     assert set(T.package_functions()) <= reached and set(T.registered_ops()) <= reached
 

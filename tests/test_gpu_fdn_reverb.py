@@ -1,6 +1,6 @@
 """GPU tests of fdn_reverb (csrc/fdn.hip): parity of y, grad x and the three control gradients with the float64 restatement
-(tests/fdn_reverb_restated.py), exact identities, the adjoint, bit-for-bit reproducibility, what happens off the nominal domain, the
-autograd and call-state contracts (the helpers of tests/autograd_contract_checks.py and tests/call_state_checks.py) and the module.
+(tests/fdn_reverb_restated.py), exact identities, the adjoint, bit-for-bit reproducibility, what happens off the nominal domain, the refused
+double backward and the module. The autograd and call-state contracts run on the op's entry in tests/autograd_contract_cases.py.
 
 Parity bounds, the convention of the fused effects. The yardstick is the restatement with float64 g and a and float32 arithmetic on the
 same inputs on the CPU: e32 = its error against float64 throughout, relative to the peak of the float64 result. The kernel's scans take
@@ -16,13 +16,13 @@ import pytest
 import torch
 
 from tests import fdn_reverb_restated as R
+from tests.autograd_contract_cases import peak_err
 from tests.util import record
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-CTL = ("decay_s", "damping_hz", "mix")
+CTL, FLOOR = R.CTL, R.FLOOR
 GRADS = ("gdecay", "gdamping", "gmix")
-FLOOR = dict(y=2e-6, gx=2e-6, gdecay=1e-5, gdamping=1e-5, gmix=1e-5)
 DECAY = (0.005, 0.3, 3.0, 30.0, 500.0)                    # the first and the last are clamped
 DAMPING = (float("inf"), 8000.0, 300.0, -5.0)
 INF = float("inf")
@@ -79,12 +79,6 @@ def run_t(D, a, sr, delays=LINES, decorrelate=True, need_gx=True, need_ctl=True)
 
 def restated(a, sr, delays=LINES, decorrelate=True, **kw):
     return R.forward_backward(a["x"], sr, *[a[k] for k in CTL], delays, a["w"], decorrelate, **{"block": BLOCK, **kw})
-
-
-def peak_err(a, b):
-    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
-    assert a.shape == b.shape
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
 def check_parity(D, name, a, sr, delays, decorrelate=True):
@@ -461,67 +455,7 @@ def test_too_many_samples_of_delay_are_refused_on_the_host(D):
     assert torch.equal(y, x) and lib().dasp_device_error() == 0
 
 
-# ---- 6. the autograd and call-state contracts ---------------------------------------------------------------------------------------------
-def _spec():
-    """The op's entry for the contract batteries, in the form of the entries of tests/autograd_contract_cases.py (that table is closed:
-    tests/test_call_state_cpu.py pins its size). What is watched is FdnReverbKernels, the class that holds the forward / backward pair
-    that FdnReverbFunction binds to autograd."""
-    from dasp_pytorch_amd._ctypes_ops import FdnReverbKernels
-    from tests import autograd_contract_cases as T
-    sr, N, lines = 8000, 1501, (53, 71, 97)
-
-    def arrays(seed):
-        g = T.gen(seed, 151)
-        u = lambda lo, hi, *s: torch.rand(*s, generator=g) * (hi - lo) + lo
-        return dict(x=u(-1.0, 1.0, 3, 2, N), decay_s=u(0.05, 1.0, 3), damping_hz=u(300.0, 3900.0, 3), mix=u(0.2, 1.0, 3))
-
-    def call(t):
-        import dasp_pytorch_amd
-        return dasp_pytorch_amd.fdn_reverb(t["x"], sr, *[t[k] for k in CTL], lines)
-
-    def ref(a, gys):
-        w = torch.from_numpy(gys[0])
-        r64 = R.forward_backward(a["x"], sr, *[a[k] for k in CTL], lines, w)
-        r32 = R.forward_backward(a["x"], sr, *[a[k] for k in CTL], lines, w, arith=torch.float32)
-        names = dict(y="y0", gx="g_x", gdecay="g_decay_s", gdamping="g_damping_hz", gmix="g_mix")
-        bound = {names[k]: max(4.0 * peak_err(r32[k], r64[k]), FLOOR[k]) for k in names}
-        return dict({names[k]: r64[k] for k in names}, _bound=bound)
-    floors = dict(y0=2e-6, g_x=2e-6, **{"g_" + k: 1e-5 for k in CTL})
-    spec = T.measured_bound("fdn_reverb", arrays, call, ("x",) + CTL, ("x",), ("FdnReverbKernels",), ref, floors,
-                            forms={k: "vector" for k in CTL}, lowp=("x",), cite="tests/test_gpu_fdn_reverb.py check_parity")
-    spec.functions = lambda: [FdnReverbKernels]
-    return spec
-
-
-def _contract(checks, check):
-    spec, rec = _spec(), []
-    try:
-        find = checks[check](spec, rec)
-    except RuntimeError as e:
-        if "illegal memory access" in str(e) or "hipError" in str(e) or "HIP error" in str(e):
-            pytest.exit(f"GPU fault in fdn_reverb {check}: {e}", returncode=3)        # nothing more runs on a device that has faulted
-        raise
-    torch.cuda.synchronize()
-    assert lib().dasp_device_error() == 0
-    assert not find, "\n".join(find)
-
-
-@pytest.mark.parametrize("check", ["C1_subsets", "C2_repeat", "C3_interleave", "C4_upstream_forms", "C5_leaf_forms", "C6_mutation", "C7_streams"])
-def test_autograd_contract(D, check):
-    """needs_input_grad subsets (x alone: no saved line signals; x without a gradient: gx = NULL), repeated and interleaved backward
-    passes, the forms of upstream gradients and leaves, callers' tensors overwritten between the passes, streams."""
-    from tests import autograd_contract_checks as K
-    _contract(K.CHECKS, check)
-
-
-@pytest.mark.parametrize("check", ["S1_arguments", "S4_memory"])
-def test_call_state(D, check):
-    """Arguments keep their bits and versions (offset and sliced views inside NaN-filled allocations included); five steps after warm-up
-    allocate nothing that stays."""
-    from tests import call_state_checks as S
-    _contract(S.CHECKS, check)
-
-
+# ---- 6. double backward ------------------------------------------------------------------------------------------------------------------
 def test_double_backward_is_refused(D):
     a = plain(2, 1, 600)
     x = a["x"].to(DEV).requires_grad_(True)

@@ -1,7 +1,8 @@
 """GPU tests of limiter (csrc/limiter.hip): parity of y, grad x, both control gradients and the saved winners with the float64
 restatement (tests/limiter_restated.py) on the cases of tests/limiter_cases.py, the ceiling, exact identities, closed forms of one
 impulse, ties, the link of the channels, clamped controls, the adjoint, bit-for-bit reproducibility, what happens off the nominal
-domain, what the forward pass leaves behind, the autograd and call-state contracts and the module.
+domain, what the forward pass leaves behind, the refused
+double backward and the module. The autograd and call-state contracts run on the op's entry in tests/autograd_contract_cases.py.
 
 Parity bounds, the house rule of the phaser and the swept filter: the yardstick is the restatement in float32 arithmetic on the same
 inputs, e32 = its error against float64 relative to the peak of the float64 result, per case over its items; the kernel gets 4 x e32
@@ -18,12 +19,13 @@ import torch
 
 from tests import limiter_cases as K
 from tests import limiter_restated as R
+from tests.autograd_contract_cases import peak_err
 from tests.util import record
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 CTL, GRADS, NAMES = R.CTL, R.GRADS, R.NAMES
-FLOOR = dict(y=2e-6, gx=2e-6, gthr=1e-5, grel=1e-5)
+FLOOR = R.FLOOR
 T = K.TILE
 
 
@@ -65,12 +67,6 @@ def plain(B, C, N, seed=0, sr=44100):
     u = lambda lo, hi: torch.rand(B, generator=g) * (hi - lo) + lo
     return dict(x=0.35 * torch.randn(B, C, N, generator=g) * env, w=torch.randn(B, C, N, generator=g), threshold_db=u(-20.0, -8.0),
                 release_ms=torch.exp(u(np.log(30.0), np.log(4000.0))) / sr * 1000.0)
-
-
-def peak_err(a, b):
-    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
-    assert a.shape == b.shape
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
 def ceiling(thr):
@@ -488,63 +484,7 @@ def test_forward_saves_eight_bytes_per_item_sample_and_nothing_without_a_gradien
     assert not saved
 
 
-# ---- 11. the autograd and call-state contracts -----------------------------------------------------------------------------------------------
-def _spec():
-    """The op's entry for the contract batteries, in the form of the entries of tests/autograd_contract_cases.py (that table is closed:
-    tests/test_call_state_cpu.py pins its size). What is watched is LimiterKernels, the class that holds the forward / backward pair
-    that LimiterFunction binds to autograd."""
-    from dasp_pytorch_amd._ctypes_ops import LimiterKernels
-    from tests import autograd_contract_cases as A
-    sr, L, N = 8000, 40, 1501
-
-    def arrays(seed):
-        g = A.gen(seed, 167)
-        u = lambda lo, hi, *s: torch.rand(*s, generator=g) * (hi - lo) + lo
-        return dict(x=0.5 * torch.randn(3, 2, N, generator=g), threshold_db=u(-20.0, -8.0, 3), release_ms=u(5.0, 100.0, 3))
-
-    def call(t):
-        import dasp_pytorch_amd
-        return dasp_pytorch_amd.limiter(t["x"], sr, t["threshold_db"], t["release_ms"], lookahead_ms=5.0)
-
-    def ref(a, gys):
-        w = torch.from_numpy(gys[0])
-        r64 = R.forward_backward(a["x"], sr, a["threshold_db"], a["release_ms"], w, lookahead=L)
-        r32 = R.forward_backward(a["x"], sr, a["threshold_db"], a["release_ms"], w, lookahead=L, arith=torch.float32)
-        names = dict(y="y0", gx="g_x", gthr="g_threshold_db", grel="g_release_ms")
-        bound = {names[k]: max(4.0 * peak_err(r32[k], r64[k]), FLOOR[k]) for k in names}
-        return dict({names[k]: r64[k] for k in names}, _bound=bound)
-    floors = dict(y0=2e-6, g_x=2e-6, **{"g_" + k: 1e-5 for k in CTL})
-    spec = A.measured_bound("limiter", arrays, call, ("x",) + CTL, ("x",), ("LimiterKernels",), ref, floors,
-                            forms={k: "vector" for k in CTL}, lowp=("x",), cite="tests/test_gpu_limiter.py test_parity_with_the_float64_restatement")
-    spec.functions = lambda: [LimiterKernels]
-    return spec
-
-
-def _contract(checks, check):
-    spec, rec = _spec(), []
-    try:
-        find = checks[check](spec, rec)
-    except RuntimeError as e:
-        if "illegal memory access" in str(e) or "hipError" in str(e) or "HIP error" in str(e):
-            pytest.exit(f"GPU fault in limiter {check}: {e}", returncode=3)        # nothing more runs on a device that has faulted
-        raise
-    torch.cuda.synchronize()
-    assert lib().dasp_device_error() == 0
-    assert not find, "\n".join(find)
-
-
-@pytest.mark.parametrize("check", ["C1_subsets", "C2_repeat", "C3_interleave", "C4_upstream_forms", "C5_leaf_forms", "C6_mutation", "C7_streams"])
-def test_autograd_contract(D, check):
-    from tests import autograd_contract_checks as C
-    _contract(C.CHECKS, check)
-
-
-@pytest.mark.parametrize("check", ["S1_arguments", "S4_memory"])
-def test_call_state(D, check):
-    from tests import call_state_checks as S
-    _contract(S.CHECKS, check)
-
-
+# ---- 11. double backward -----------------------------------------------------------------------------------------------------------------
 def test_double_backward_is_refused(D):
     a = plain(2, 1, 600)
     x = a["x"].to(DEV).requires_grad_(True)

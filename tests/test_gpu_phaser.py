@@ -1,7 +1,7 @@
 """GPU tests of phaser (csrc/phaser.hip): parity of y, grad x and the five control gradients with the float64 restatement
 (tests/phaser_restated.py), exact identities, the adjoint, bit-for-bit reproducibility, what happens off the nominal domain, what the
-forward pass leaves behind, the autograd and call-state contracts (the helpers of tests/autograd_contract_checks.py and
-tests/call_state_checks.py) and the module.
+forward pass leaves behind, the refused
+double backward and the module. The autograd and call-state contracts run on the op's entry in tests/autograd_contract_cases.py.
 
 Parity bounds, as for feedback_delay. The yardstick is the restatement with a float64 phase and float32 arithmetic on the same inputs on
 the CPU: e32 = its error against float64 throughout, relative to the peak of the float64 result. The kernel's scan orders its sums
@@ -20,13 +20,14 @@ import pytest
 import torch
 
 from tests import phaser_restated as R
+from tests.autograd_contract_cases import peak_err
 from tests.util import record
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 CTL = R.CTL
 GRADS = R.GRADS
-FLOOR = dict(y=2e-6, gx=2e-6, grate=1e-5, gcenter=1e-5, gdepth=1e-5, gphase=1e-5, gmix=1e-5)
+FLOOR = R.FLOOR
 LANE, WAVE = 8, 512                        # samples of a lane's run and of a wave's 64 runs (csrc/phaser.hip PH_SPT)
 SETS = 4                                   # control sets per length
 
@@ -85,12 +86,6 @@ def run_t(D, a, sr, K, need_gx=True, **kw):
     grads = torch.autograd.grad((y * a["w"].to(DEV)).sum(), ([x] if need_gx else []) + ctl)
     torch.cuda.synchronize()
     return dict(zip(("y",) + (("gx",) if need_gx else ()) + GRADS, (y.detach(),) + grads))
-
-
-def peak_err(a, b):
-    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
-    assert a.shape == b.shape
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
 @functools.lru_cache(maxsize=None)
@@ -435,68 +430,7 @@ def test_forward_saves_the_tile_states_and_nothing_of_the_signals_length(D, K):
     assert not saved
 
 
-# ---- 7. the autograd and call-state contracts ---------------------------------------------------------------------------------------------
-def _spec():
-    """The op's entry for the contract batteries, in the form of the entries of tests/autograd_contract_cases.py (that table is closed:
-    tests/test_call_state_cpu.py pins its size). What is watched is PhaserKernels, the class that holds the forward / backward pair that
-    PhaserFunction binds to autograd."""
-    from dasp_pytorch_amd._ctypes_ops import PhaserKernels
-    from tests import autograd_contract_cases as T
-    sr, K, N = 8000, 4, 1501
-
-    def arrays(seed):
-        g = T.gen(seed, 163)
-        u = lambda lo, hi, *s: torch.rand(*s, generator=g) * (hi - lo) + lo
-        return dict(x=u(-1.0, 1.0, 3, 2, N), rate_hz=u(0.5, 10.0, 3), center_hz=u(100.0, 800.0, 3), depth=u(0.5, 2.0, 3), phase=u(0.0, 1.0, 3),
-                    mix=u(0.2, 1.0, 3))
-
-    def call(t):
-        import dasp_pytorch_amd
-        return dasp_pytorch_amd.phaser(t["x"], sr, *[t[k] for k in CTL], stages=K)
-
-    def ref(a, gys):
-        w = torch.from_numpy(gys[0])
-        r64 = R.forward_backward(a["x"], sr, *[a[k] for k in CTL], w, stages=K)
-        r32 = R.forward_backward(a["x"], sr, *[a[k] for k in CTL], w, stages=K, arith=torch.float32)
-        names = dict(y="y0", gx="g_x", grate="g_rate_hz", gcenter="g_center_hz", gdepth="g_depth", gphase="g_phase", gmix="g_mix")
-        bound = {names[k]: max(4.0 * peak_err(r32[k], r64[k]), FLOOR[k]) for k in names}
-        return dict({names[k]: r64[k] for k in names}, _bound=bound)
-    floors = dict(y0=2e-6, g_x=2e-6, **{"g_" + k: 1e-5 for k in CTL})
-    spec = T.measured_bound("phaser", arrays, call, ("x",) + CTL, ("x",), ("PhaserKernels",), ref, floors,
-                            forms={k: "vector" for k in CTL}, lowp=("x",), cite="tests/test_gpu_phaser.py test_parity_with_the_float64_restatement")
-    spec.functions = lambda: [PhaserKernels]
-    return spec
-
-
-def _contract(checks, check):
-    spec, rec = _spec(), []
-    try:
-        find = checks[check](spec, rec)
-    except RuntimeError as e:
-        if "illegal memory access" in str(e) or "hipError" in str(e) or "HIP error" in str(e):
-            pytest.exit(f"GPU fault in phaser {check}: {e}", returncode=3)        # nothing more runs on a device that has faulted
-        raise
-    torch.cuda.synchronize()
-    assert lib().dasp_device_error() == 0
-    assert not find, "\n".join(find)
-
-
-@pytest.mark.parametrize("check", ["C1_subsets", "C2_repeat", "C3_interleave", "C4_upstream_forms", "C5_leaf_forms", "C6_mutation", "C7_streams"])
-def test_autograd_contract(D, check):
-    """needs_input_grad subsets (x without a gradient included: gx = NULL), repeated and interleaved backward passes, the forms of
-    upstream gradients and leaves, callers' tensors overwritten between the passes, streams."""
-    from tests import autograd_contract_checks as K
-    _contract(K.CHECKS, check)
-
-
-@pytest.mark.parametrize("check", ["S1_arguments", "S4_memory"])
-def test_call_state(D, check):
-    """Arguments keep their bits and versions (offset and sliced views inside NaN-filled allocations included); five steps after warm-up
-    allocate nothing that stays."""
-    from tests import call_state_checks as S
-    _contract(S.CHECKS, check)
-
-
+# ---- 7. double backward ------------------------------------------------------------------------------------------------------------------
 def test_double_backward_is_refused(D):
     a = plain(2, 1, 600)
     x = a["x"].to(DEV).requires_grad_(True)

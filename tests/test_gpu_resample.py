@@ -1,6 +1,6 @@
 """GPU tests of resample (csrc/resample.hip): parity of y and grad x with the float64 restatement (tests/resample_restated.py), exact
-identities, the adjoint, bit-for-bit reproducibility, what happens off the nominal domain, host refusals, the autograd and call-state
-contracts (the helpers of tests/autograd_contract_checks.py and tests/call_state_checks.py) and the module.
+identities, the adjoint, bit-for-bit reproducibility, what happens off the nominal domain, host refusals, the refused
+double backward and the module. The autograd and call-state contracts run on the op's entry in tests/autograd_contract_cases.py.
 
 Parity bounds. The yardstick is the restatement with the same float32 taps and float32 arithmetic on the same inputs on the CPU:
 e32 = its error against float64 arithmetic, relative to the peak of the float64 result. The kernel sums an output's products in another
@@ -16,11 +16,12 @@ import pytest
 import torch
 
 from tests import resample_restated as R
+from tests.autograd_contract_cases import peak_err
 from tests.util import record
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-FLOOR = 2e-6
+FLOOR = R.FLOOR
 NAMES = ("y", "gx")
 RATIOS = [(147, 160), (160, 147), (441, 160), (80, 441), (640, 147), (2, 1), (1, 2), (3, 2), (2, 3)]
 HANN = dict(resampling_method="sinc_interp_hann")
@@ -77,12 +78,6 @@ def run_t(D, x, w, o, n, **kw):
     (gx,) = torch.autograd.grad((y * w.to(DEV)).sum(), xt)
     torch.cuda.synchronize()
     return dict(y=y.detach(), gx=gx)
-
-
-def peak_err(a, b):
-    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
-    assert a.shape == b.shape
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
 def check_parity(D, name, x, w, o, n, kw):
@@ -389,62 +384,7 @@ def test_double_backward_is_refused(D):
         gx.sum().backward()
 
 
-# ---- 7. the autograd and call-state contracts, the module ---------------------------------------------------------------------------------
-def _spec():
-    """The op's entry for the contract batteries, in the form of the entries of tests/autograd_contract_cases.py (that table is closed:
-    tests/test_call_state_cpu.py pins its size). What is watched is ResampleKernels, the class that holds the forward / backward pair
-    that ResampleFunction binds to autograd."""
-    from dasp_pytorch_amd._ctypes_ops import ResampleKernels
-    from tests import autograd_contract_cases as T
-    o, n, shape = 147, 160, (3, 2, 1501)
-    M = R.out_len(o, n, shape[-1])
-
-    def arrays(seed):
-        g = T.gen(seed, 151)
-        return dict(x=torch.rand(*shape, generator=g) * 2 - 1)
-
-    def call(t):
-        import dasp_pytorch_amd
-        return dasp_pytorch_amd.resample(t["x"], 44100, 48000)
-
-    def ref(a, gys):
-        w = torch.from_numpy(gys[0])
-        r64 = R.forward_backward(a["x"], w, o, n)
-        r32 = R.forward_backward(a["x"], w, o, n, arith=torch.float32)
-        names = dict(y="y0", gx="g_x")
-        bound = {names[k]: max(4.0 * peak_err(r32[k], r64[k]), FLOOR) for k in names}
-        return dict({names[k]: r64[k] for k in names}, _bound=bound)
-    spec = T.measured_bound("resample", arrays, call, ("x",), ("x",), ("ResampleKernels",), ref, dict(y0=FLOOR, g_x=FLOOR), lowp=("x",),
-                            outs=lambda a: [shape[:-1] + (M,)], cite="tests/test_gpu_resample.py check_parity")
-    spec.functions = lambda: [ResampleKernels]
-    return spec
-
-
-def _contract(checks, check):
-    spec, rec = _spec(), []
-    try:
-        find = checks[check](spec, rec)
-    except RuntimeError as e:
-        if "illegal memory access" in str(e) or "hipError" in str(e) or "HIP error" in str(e):
-            pytest.exit(f"GPU fault in resample {check}: {e}", returncode=3)              # nothing more runs on a device that has faulted
-        raise
-    torch.cuda.synchronize()
-    assert lib().dasp_device_error() == 0
-    assert not find, "\n".join(find)
-
-
-@pytest.mark.parametrize("check", ["C1_subsets", "C2_repeat", "C3_interleave", "C4_upstream_forms", "C5_leaf_forms", "C6_mutation", "C7_streams"])
-def test_autograd_contract(D, check):
-    from tests import autograd_contract_checks as K
-    _contract(K.CHECKS, check)
-
-
-@pytest.mark.parametrize("check", ["S1_arguments", "S4_memory"])
-def test_call_state(D, check):
-    from tests import call_state_checks as S
-    _contract(S.CHECKS, check)
-
-
+# ---- 7. double backward, the module ------------------------------------------------------------------------------------------------------
 def test_module_equals_functional(D):
     x = draw((3, 2, 3000), 147, 160)[0].to(DEV)
     m = D.Resample(44100, 48000, resampling_method="sinc_interp_kaiser", lowpass_filter_width=8, rolloff=0.9, beta=10.0)

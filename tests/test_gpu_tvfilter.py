@@ -1,7 +1,8 @@
 """GPU tests of time_varying_filter (csrc/tvfilter.hip): parity of y, grad x and the three control gradients with the float64 restatement
 (tests/tvfilter_restated.py), the static case against the RBJ biquads, exact identities, clamped frame values, the last frame point, a
 frame point on a tile boundary, the adjoint, bit-for-bit reproducibility, NaN frame values, views and guard words, the errors of the C
-ABI, the autograd and call-state contracts (the helpers of tests/autograd_contract_checks.py and tests/call_state_checks.py) and the module.
+ABI, the refused
+double backward and the module. The autograd and call-state contracts run on the op's entry in tests/autograd_contract_cases.py.
 
 Parity bounds, as for phaser. The yardstick is the restatement with float64 frame points and float32 arithmetic on the same inputs on the
 CPU: e32 = its error against float64 throughout, relative to the peak of the float64 result. The kernel's scan orders its products
@@ -27,13 +28,14 @@ import scipy.signal
 import torch
 
 from tests import tvfilter_restated as R
+from tests.autograd_contract_cases import peak_err
 from tests.util import record
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 CTL = R.CTL
 GRADS = R.GRADS
-FLOOR = dict(y=2e-6, gx=2e-6, gcutoff=1e-5, gq=1e-5, gmix=1e-5)
+FLOOR = R.FLOOR
 LANE, WAVE, TILE = 8, 512, 2048            # samples of a lane's run, of a wave's 64 runs and of a tile (csrc/tvfilter.hip TV_SPT, TV_TILE)
 LENGTHS = (1, 7, 8, 9, WAVE - 1, WAVE, WAVE + 1, TILE - 1, TILE, TILE + 1, 2 * TILE + 1, 3 * TILE + 5)
 SETS = 3                                   # control sets per length: two draws of the main sweep, the hard set
@@ -72,12 +74,6 @@ def run_t(D, a, sr, hop=64, mode="lowpass", need_gx=True):
     grads = torch.autograd.grad((y * a["w"].to(DEV)).sum(), ([x] if need_gx else []) + ctl)
     torch.cuda.synchronize()
     return dict(zip(("y",) + (("gx",) if need_gx else ()) + GRADS, (y.detach(),) + grads))
-
-
-def peak_err(a, b):
-    a, b = np.asarray(a, np.float64).reshape(-1), np.asarray(b, np.float64).reshape(-1)
-    assert a.shape == b.shape
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
 def restated(a, sr, hop, mode, **kw):
@@ -519,69 +515,7 @@ def test_forward_saves_the_tile_states_and_nothing_of_the_signals_length(D):
     assert not saved
 
 
-# ---- 9. the autograd and call-state contracts ---------------------------------------------------------------------------------------------
-def _spec():
-    """The op's entry for the contract batteries, in the form of the entries of tests/autograd_contract_cases.py (that table is closed:
-    tests/test_call_state_cpu.py pins its size). What is watched is TimeVaryingFilterKernels, the class that holds the forward / backward
-    pair that TimeVaryingFilterFunction binds to autograd."""
-    from dasp_pytorch_amd._ctypes_ops import TimeVaryingFilterKernels
-    from tests import autograd_contract_cases as T
-    sr, hop, mode, N = 8000, 64, "bandpass", 1501
-    F = R.control_frames(N, hop)
-
-    def arrays(seed):
-        g = T.gen(seed, 167)
-        u = lambda lo, hi, *s: torch.rand(*s, generator=g) * (hi - lo) + lo
-        return dict(x=u(-1.0, 1.0, 3, 2, N), cutoff_hz=u(100.0, 3000.0, 3, F), q=u(0.5, 8.0, 3, F), mix=u(0.2, 1.0, 3))
-
-    def call(t):
-        import dasp_pytorch_amd
-        return dasp_pytorch_amd.time_varying_filter(t["x"], sr, *[t[k] for k in CTL], hop=hop, mode=mode)
-
-    def ref(a, gys):
-        w = torch.from_numpy(gys[0])
-        r64 = R.forward_backward(a["x"], sr, *[a[k] for k in CTL], w, hop, mode)
-        r32 = R.forward_backward(a["x"], sr, *[a[k] for k in CTL], w, hop, mode, arith=torch.float32)
-        names = dict(y="y0", gx="g_x", gcutoff="g_cutoff_hz", gq="g_q", gmix="g_mix")
-        bound = {names[k]: max(4.0 * peak_err(r32[k], r64[k]), FLOOR[k]) for k in names}
-        return dict({names[k]: r64[k] for k in names}, _bound=bound)
-    floors = dict(y0=2e-6, g_x=2e-6, **{"g_" + k: 1e-5 for k in CTL})
-    spec = T.measured_bound("time_varying_filter", arrays, call, ("x",) + CTL, ("x",), ("TimeVaryingFilterKernels",), ref, floors,
-                            forms={"cutoff_hz": "matrix", "q": "matrix", "mix": "vector"}, lowp=("x",),
-                            cite="tests/test_gpu_tvfilter.py test_parity_with_the_float64_restatement")
-    spec.functions = lambda: [TimeVaryingFilterKernels]
-    return spec
-
-
-def _contract(checks, check):
-    spec, rec = _spec(), []
-    try:
-        find = checks[check](spec, rec)
-    except RuntimeError as e:
-        if "illegal memory access" in str(e) or "hipError" in str(e) or "HIP error" in str(e):
-            pytest.exit(f"GPU fault in time_varying_filter {check}: {e}", returncode=3)        # nothing more runs on a device that has faulted
-        raise
-    torch.cuda.synchronize()
-    assert lib().dasp_device_error() == 0
-    assert not find, "\n".join(find)
-
-
-@pytest.mark.parametrize("check", ["C1_subsets", "C2_repeat", "C3_interleave", "C4_upstream_forms", "C5_leaf_forms", "C6_mutation", "C7_streams"])
-def test_autograd_contract(D, check):
-    """needs_input_grad subsets (x without a gradient included: gx = NULL), repeated and interleaved backward passes, the forms of
-    upstream gradients and leaves, callers' tensors overwritten between the passes, streams."""
-    from tests import autograd_contract_checks as K
-    _contract(K.CHECKS, check)
-
-
-@pytest.mark.parametrize("check", ["S1_arguments", "S2_rng", "S4_memory"])
-def test_call_state(D, check):
-    """Arguments keep their bits and versions (offset and sliced views inside NaN-filled allocations included); no random stream moves;
-    five steps after warm-up allocate nothing that stays."""
-    from tests import call_state_checks as S
-    _contract(S.CHECKS, check)
-
-
+# ---- 9. double backward ------------------------------------------------------------------------------------------------------------------
 def test_double_backward_is_refused(D):
     a = plain(2, 1, 600)
     x = a["x"].to(DEV).requires_grad_(True)

@@ -19,6 +19,8 @@ MODES = ("lowpass", "bandpass", "highpass", "notch")
 CTL = ("cutoff_hz", "q", "mix")
 GRADS = ("gcutoff", "gq", "gmix")
 NAMES = ("y", "gx") + GRADS
+# the least the kernel's parity bound is, whatever the float32 restatement's own error: the floors of the other fused effects
+FLOOR = dict(y=2e-6, gx=2e-6, gcutoff=1e-5, gq=1e-5, gmix=1e-5)
 Q_LO, Q_HI = 0.1, 100.0
 
 
