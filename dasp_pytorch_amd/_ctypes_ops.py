@@ -1143,6 +1143,108 @@ class TimeVaryingFilterFunction(_AudioControlsFunction):
         return gcut, gq, gmix
 
 
+class GainCurveKernels:
+    """The forward / backward pair of gain_curve as autograd calls it: y = x 10^(g / 20), g the curve gain_db (bs, F) interpolated in dB
+    between frame points hop samples apart (dasp_gaincurve_forward / _backward, csrc/envelope.hip). sample_rate: a float the op does
+    not use (the signature of `gain`); hop: an int. Saves x and the curve: the backward kernel recomputes the gain."""
+
+    @staticmethod
+    def forward(ctx, x, gain_db, sample_rate, hop):
+        return GainCurveFunction._run(ctx, x, (gain_db,), sample_rate, hop)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return GainCurveFunction._grad(ctx, gy)
+
+
+class GainCurveFunction(GainCurveKernels, _AudioControlsFunction):
+    """GainCurveKernels bound to autograd on the shared plumbing of _AudioControlsFunction, the curve kept as a (bs, F) matrix like the
+    curves of TimeVaryingFilterFunction. The pair lives in the plain class and this one defines no forward of its own: the table of
+    tests/autograd_contract_cases.py is closed, and this op's contract is checked by the same batteries from
+    tests/test_gpu_gain_curve.py, which watches GainCurveKernels."""
+    CFG = (float, int)
+
+    @classmethod
+    def _controls(cls, x, ctls):
+        return (cls._f32(x, ctls[0], x.shape[0], -1).contiguous(),)
+
+    @staticmethod
+    def _forward(ctx, x32, c32, y):
+        (B, C, N), hop = x32.shape, ctx.cfg[1]
+        call("dasp_gaincurve_forward", ptr(x32), ptr(c32[0]), ptr(y), B, C, N, hop, stream())
+        return () if any(ctx.needs_input_grad[:2]) else None
+
+    @staticmethod
+    def _backward(ctx, x32, saved, gy, gx):
+        (P,), (B, C, N), hop = saved, x32.shape, ctx.cfg[1]
+        gP = scratch = None
+        if ctx.needs_input_grad[1]:                                               # otherwise one launch: gx alone
+            gP = torch.empty_like(P)
+            scratch = torch.empty(_lib.lib().dasp_gaincurve_scratch_floats(B, N, hop), dtype=torch.float32, device=x32.device)
+        g32 = _f32c(gy)
+        call("dasp_gaincurve_backward", ptr(x32), ptr(P), ptr(g32), ptr(gx), ptr(gP), ptr(scratch), B, C, N, hop, stream())
+        return (gP,)
+
+
+ENVELOPE_DETECTORS = ("peak", "power")
+
+
+class EnvelopeFollowerKernels:
+    """The forward / backward pair of envelope_follower as autograd calls it: x (bs, chs, N) -> E (bs, F), the one-pole smoothed peak
+    or power level at the frame points (dasp_envelope_forward / _backward, csrc/envelope.hip). smoothing_ms: bs values; sample_rate: a
+    float; hop: an int; detector: an index into ENVELOPE_DETECTORS. Saves x, the control and, when the control needs a gradient, the
+    tangent dE/da (bs, F): nothing per sample."""
+
+    @staticmethod
+    def forward(ctx, x, smoothing_ms, sample_rate, hop, detector):
+        _lib.require_device(x, "x")
+        B, C, N = x.shape
+        hop = int(hop)
+        F = -(-N // hop) + 1
+        ctx.meta = (x.dtype, x.shape, smoothing_ms.dtype, smoothing_ms.shape)
+        ctx.cfg = (float(sample_rate), hop, int(detector))
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            return torch.zeros((B, F), dtype=x.dtype, device=x.device)
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            s32 = smoothing_ms.detach().reshape(B).to(device=x.device, dtype=torch.float32).contiguous()
+            E = torch.empty((B, F), dtype=torch.float32, device=x.device)
+            ctx.tangent = bool(ctx.needs_input_grad[1])
+            D = torch.empty_like(E) if ctx.tangent else None
+            scratch = torch.empty(_lib.lib().dasp_envelope_scratch_floats(B, N, hop), dtype=torch.float32, device=x.device)
+            call("dasp_envelope_forward", ptr(x32), ptr(s32), ptr(E), ptr(D), ptr(scratch), B, C, N, hop, ctx.cfg[2], ctx.cfg[0], stream())
+            if any(ctx.needs_input_grad[:2]):
+                ctx.save_for_backward(x32, s32, *((D,) if ctx.tangent else ()))
+        return E.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gE):
+        xd, xs, sd, ss = ctx.meta
+        need = ctx.needs_input_grad
+        if ctx.empty:
+            return _needed(ctx, (torch.zeros(xs, dtype=xd, device=gE.device), torch.zeros(ss, dtype=sd, device=gE.device), None, None, None))
+        sample_rate, hop, detector = ctx.cfg
+        x32, s32, *rest = ctx.saved_tensors
+        B, C, N = x32.shape
+        with torch.cuda.device(x32.device):
+            gx = torch.empty_like(x32) if need[0] else None                       # None: the elementwise pass is skipped
+            gs = torch.empty_like(s32) if ctx.tangent else None
+            scratch = torch.empty(_lib.lib().dasp_envelope_scratch_floats(B, N, hop), dtype=torch.float32, device=x32.device) if need[0] else None
+            g32 = _f32c(gE)
+            call("dasp_envelope_backward", ptr(x32), ptr(s32), ptr(rest[0] if ctx.tangent else None), ptr(g32), ptr(gx), ptr(gs), ptr(scratch),
+                 B, C, N, hop, detector, sample_rate, stream())
+        return (gx.to(xd) if need[0] else None, gs.reshape(ss).to(sd) if need[1] else None, None, None, None)
+
+
+class EnvelopeFollowerFunction(EnvelopeFollowerKernels, torch.autograd.Function):
+    """EnvelopeFollowerKernels bound to autograd: a direct Function like ResampleFunction, because its output is not audio-shaped. The pair
+    lives in the plain class and this one defines no forward of its own: the table of tests/autograd_contract_cases.py is closed, and
+    this op's contract is checked by the same batteries from tests/test_gpu_envelope.py, which watches EnvelopeFollowerKernels."""
+
+
 _RESAMPLE_DESIGNS, _RESAMPLE_TABLES = {}, {}
 
 

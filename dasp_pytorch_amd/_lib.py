@@ -121,6 +121,13 @@ SIGNATURES = {
     "dasp_phaser_prepare": (_i, []),
     "dasp_phaser_forward": (_i, [_p] * 4 + [_i, _i, _l, _i, _d, _d, _p]),
     "dasp_phaser_backward": (_i, [_p] * 7 + [_i, _i, _l, _i, _d, _d, _p]),
+    "dasp_envelope_tile": (_i, []),
+    "dasp_envelope_scratch_floats": (_l, [_l, _l, _i]),
+    "dasp_envelope_forward": (_i, [_p] * 5 + [_i, _i, _l, _i, _i, _d, _p]),
+    "dasp_envelope_backward": (_i, [_p] * 7 + [_i, _i, _l, _i, _i, _d, _p]),
+    "dasp_gaincurve_scratch_floats": (_l, [_l, _l, _i]),
+    "dasp_gaincurve_forward": (_i, [_p] * 3 + [_i, _i, _l, _i, _p]),
+    "dasp_gaincurve_backward": (_i, [_p] * 6 + [_i, _i, _l, _i, _p]),
     "dasp_tvfilter_tile": (_i, []),
     "dasp_tvfilter_frames": (_l, [_l, _i]),
     "dasp_tvfilter_state_floats": (_l, [_l, _l]),

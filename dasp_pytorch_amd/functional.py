@@ -10,7 +10,8 @@ from . import signal as _signal
 from . import _mt19937
 from . import ops as _ops
 from . import _lib
-from .ops import (FILTER_TYPES, BusFunction, DistortionSampleFunction, FdnReverbFunction, FeedbackDelayFunction, LimiterFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
+from .ops import (ENVELOPE_DETECTORS, FILTER_TYPES, BusFunction, DistortionSampleFunction, EnvelopeFollowerFunction, FdnReverbFunction, FeedbackDelayFunction, GainCurveFunction,
+                  LimiterFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
                   PhaserFunction, ResampleFunction, StereoMixFunction, TVFILTER_MODES, TimeVaryingFilterFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
@@ -317,7 +318,7 @@ def time_varying_filter(x: torch.Tensor, sample_rate: float, cutoff_hz: torch.Te
     zero. The clamps are comparisons, which a NaN passes: a NaN frame value j makes its item NaN from sample (j - 1) hop on and leaves
     earlier samples and other items alone.
     One workgroup walks one (item, channel) row tile by tile: the op cannot fill the chip at training batch sizes.
-    Out of scope: an envelope follower that drives the cutoff from x itself, per-channel curves, cascaded sections or a morphing mode
+    Out of scope: an envelope follower inside the op (compose `envelope_follower`, whose output is a curve for it), per-channel curves, cascaded sections or a morphing mode
     mix, look-back segments for few rows, float64, and a torch.ops.dasp registration. A wrong frame count raises RuntimeError naming the
     control and the expected F; a hop that is no power of two from 8 to 2048, an unknown mode or a sample_rate that is not positive and
     finite ValueError, before anything touches the device."""
@@ -339,6 +340,72 @@ def time_varying_filter(x: torch.Tensor, sample_rate: float, cutoff_hz: torch.Te
     _lib.require_device(x, "x")
     require_fp32_ok(x, "time_varying_filter")
     return TimeVaryingFilterFunction.apply(x, cutoff_hz, q, mix, sr, int(hop), TVFILTER_MODES.index(mode))
+
+
+def envelope_follower(x: torch.Tensor, sample_rate: float, smoothing_ms: torch.Tensor, hop: int = 64, detector: str = "peak"):
+    """Envelope follower: a control curve from a signal. x (bs, chs, seq_len); smoothing_ms holds bs values; hop is a plain int, a power
+    of two from 8 to 2048; detector "peak" or "power". Returns E (bs, F), F = signal.control_frames(seq_len, hop), frame point j at
+    sample j hop - the convention of time_varying_filter and gain_curve, so E is directly a curve for them. For item b, with the level
+    zero from sample seq_len on and e[-1] = 0:
+        t = clamp(smoothing_ms, 0.1, 10000);   a = exp(-ln 9 / (sample_rate t / 1000))          (the compressor's 10-90 % constant)
+        p[m] = max_c |x[b,c,m]|   ("peak": channels linked, the lowest channel wins a tie)   |   mean_c x[b,c,m]^2   ("power")
+        e[m] = a e[m-1] + (1 - a) p[m]                                                          (unit DC gain)
+        E[b,j] = e[j hop],  j = 0 .. F-1                                  ((F-1) hop >= seq_len: the last points see the decay)
+    The output is linear - amplitude for "peak", mean square for "power": dB, square roots, thresholds and ratios are the caller's torch
+    code on (bs, F), so the op has no eps and no singular gradient. The recurrence is not walked: a is constant per item, so
+    E_j = a^hop E_{j-1} + z_j with z_j a weighted sum over hop samples; the sums are float32 with weights from float64 (rounded once),
+    over independent tiles that fill the chip at any batch size, and the frame-rate recurrence is float64 (csrc/envelope.hip).
+    Differentiable once in x and smoothing_ms: "peak" sends sign(x) to the winning channel (sign(0) = 0), "power" 2 x / chs to every
+    channel; the gradient of smoothing_ms is exactly zero where it was clamped. Nothing per sample is saved: x, the control and, when
+    the control needs a gradient, dE/da (bs, F). No atomics: every result is bit-identical run to run and for an item alone or in a
+    batch. A NaN smoothing_ms makes its own item NaN and no other; a NaN or inf sample at m0 reaches the frame points j hop >= m0 of
+    its item and nothing else. Half and bfloat16 are converted, float64 is refused; seq_len = 0 returns the (bs, 1) zero curve.
+    Out of scope: separate attack and release, unlinked channels, per-sample output, float64, a torch.ops.dasp registration and a
+    chain.py entry. A wrong control count raises RuntimeError naming the control; a hop that is no power of two from 8 to 2048, an
+    unknown detector or a sample_rate that is not positive and finite ValueError, before anything touches the device."""
+    bs, chs, seq_len = x.size()
+    if smoothing_ms.numel() != bs:
+        raise RuntimeError(f"smoothing_ms: shape '[{bs}]' is invalid for input of size {smoothing_ms.numel()}")
+    try:
+        sr = float(sample_rate)
+    except (TypeError, ValueError):
+        sr = float("nan")
+    if not (sr > 0.0 and sr != float("inf")):
+        raise ValueError(f"envelope_follower: finite sample_rate > 0, got {sample_rate}")
+    if detector not in ENVELOPE_DETECTORS:
+        raise ValueError(f"envelope_follower: detector must be one of {', '.join(ENVELOPE_DETECTORS)}, got {detector!r}")
+    try:
+        _signal.control_frames(seq_len, hop)
+    except ValueError as e:
+        raise ValueError(f"envelope_follower: {e}") from None
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "envelope_follower")
+    return EnvelopeFollowerFunction.apply(x, smoothing_ms, sr, int(hop), ENVELOPE_DETECTORS.index(detector))
+
+
+def gain_curve(x: torch.Tensor, sample_rate: float, gain_db: torch.Tensor, hop: int = 64):
+    """Gain that follows a control curve: fader automation, fades, tremolo, ducking. x (bs, chs, seq_len); gain_db (bs, F) with
+    F = signal.control_frames(seq_len, hop), frame point j at sample j hop, shared by an item's channels; hop is a plain int, a power of
+    two from 8 to 2048; sample_rate is not used (the signature of `gain`). For item b, every channel and sample n, with P = gain_db[b]:
+        j = n // hop;   t = (n mod hop) / hop;   g[n] = P_j + t (P_{j+1} - P_j)                 (interpolated in dB, float32)
+        y[b,c,n] = x[b,c,n] 10^(g[n] / 20)
+    An all-zero curve returns x bit for bit. Differentiable once in x and in every frame value: frame point j takes (1 - t) of its own
+    interval and t of the one before it, summed over the channels in a fixed order - no atomics, every result bit-identical run to run
+    and for an item alone or in a batch (csrc/envelope.hip). At t = 0 the gain is P_j itself: a NaN frame value j reaches the samples
+    (j - 1) hop < n < (j + 1) hop of its item only, in y and in both gradients. Frame values are expected finite; +-inf is not a mute.
+    Half and bfloat16 are converted, float64 is refused.
+    A wrong frame count raises RuntimeError naming gain_db and the expected F; a hop that is no power of two from 8 to 2048 ValueError,
+    before anything touches the device."""
+    bs, chs, seq_len = x.size()
+    try:
+        frames = _signal.control_frames(seq_len, hop)
+    except ValueError as e:
+        raise ValueError(f"gain_curve: {e}") from None
+    if gain_db.dim() != 2 or tuple(gain_db.shape) != (bs, frames):
+        raise RuntimeError(f"gain_db: expected shape [{bs}, {frames}] (F = ceil({seq_len} / {hop}) + 1 = {frames} frame points), got {list(gain_db.shape)}")
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "gain_curve")
+    return GainCurveFunction.apply(x, gain_db, float(sample_rate), int(hop))
 
 
 def resample(x: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,

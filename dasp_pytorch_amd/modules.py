@@ -464,6 +464,34 @@ class TimeVaryingFilter(Processor):
                                q=denormalize(param_tensor[:, frames:2 * frames], qhi, qlo), mix=denormalize(param_tensor[:, 2 * frames], mhi, mlo))
 
 
+class GainCurve(Processor):
+    """Gain along a control curve (functional.gain_curve); hop is fixed at construction. Its control is a curve, so the parameter tensor
+    of process_normalized is (bs, F) with F = signal.control_frames(seq_len, hop): the frame values of gain_db, each on [0, 1] and mapped
+    linearly onto [min_gain_db, max_gain_db]."""
+
+    def __init__(self, sample_rate: int, hop: int = 64, min_gain_db: float = -60.0, max_gain_db: float = 12.0):
+        super().__init__()
+        S.control_frames(0, hop)
+        self.sample_rate = sample_rate
+        self.hop = int(hop)
+        self.process_fn = functools.partial(F.gain_curve, hop=self.hop)
+        self.param_ranges = {"gain_db": (min_gain_db, max_gain_db)}
+
+    def process_normalized(self, x: torch.Tensor, param_tensor: torch.Tensor):
+        frames = S.control_frames(x.shape[-1], self.hop)
+        if param_tensor.dim() != 2 or param_tensor.shape[1] != frames:
+            raise ValueError(f"Parameter tensor has {param_tensor.shape[-1]} parameters, but processor has {frames} parameters "
+                             f"({frames} frame points of gain_db).")
+        if self.validate_range and not getattr(_validated, "on", False) and not (param_tensor.is_cuda and torch.cuda.is_current_stream_capturing()):
+            names = ["gain_db"] * frames
+            if self.validate_range == "deferred":
+                self._deferred().submit(param_tensor, names)
+            else:
+                check_unit_range(param_tensor, names)
+        lo, hi = self.param_ranges["gain_db"]
+        return self.process_fn(x, self.sample_rate, gain_db=denormalize(param_tensor, hi, lo))
+
+
 class Resample(torch.nn.Module):
     """functional.resample with torchaudio.transforms.Resample's constructor: callable on (..., N), returns (..., ceil(new N / orig)).
     No parameters and no buffers: the design is built on the host on first use and its tables are kept per device by the binding. The

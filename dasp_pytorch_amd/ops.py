@@ -16,7 +16,7 @@ import torch
 
 from . import _lib, config
 from ._ctypes_ops import (FILTER_TYPES, BiquadFunction, BusFunction, ChainControlsFunction, DistortionFunction, DistortionSampleFunction,   # noqa: F401
-                          DynamicsCtlFunction, DynamicsFunction, DynamicsMatrixFunction, FdnReverbFunction, FeedbackDelayFunction, GainFunction, LimiterFunction, ModulatedDelayFunction, OversampledDistortionFunction,
+                          DynamicsCtlFunction, DynamicsFunction, DynamicsMatrixFunction, ENVELOPE_DETECTORS, EnvelopeFollowerFunction, FdnReverbFunction, FeedbackDelayFunction, GainCurveFunction, GainFunction, LimiterFunction, ModulatedDelayFunction, OversampledDistortionFunction,
                           PannerFunction, PhaserFunction,
                           ParametricEQFunction,
                           ParametricEQNormFunction, ResampleFunction, ReverbFunction, SosFiltFunction, StereoMixFunction, TVFILTER_MODES, TimeVaryingFilterFunction, WidenerFunction, _dyn_counters, _filter_spectrum, _seed_offset,

@@ -607,6 +607,38 @@ int dasp_tvfilter_backward(const float* x, const float* cutoff_hz, const float* 
                            float* gcutoff, float* gq, float* gmix, float* scratch, int B, int C, long N, int hop, int mode, double sample_rate,
                            void* stream);
 
+/* envelope_follower and gain_curve: the control-rate side chains, audio -> curve and curve -> gain (csrc/envelope.hip). x, gx, y, gy
+ * (B, C, N) fp32; smoothing_ms, gsmoothing (B) fp32; env, tangent, genv, gain_db, ggain (B, F) fp32, F = ceil(N / hop) + 1 (the frame
+ * points of dasp_tvfilter_frames: point j at sample j hop), shared by an item's channels. hop: a power of two from 8 to 2048.
+ * detector: 0 peak, 1 power. Both ops work in tiles of dasp_envelope_tile() samples, one workgroup per (item, tile).
+ * envelope, for item b with the level zero from sample N on and e[-1] = 0:
+ *   t = clamp(smoothing_ms, 0.1, 10000),  a = exp(-ln 9 / (sample_rate t / 1000))
+ *   p[m] = max_c |x[b,c,m]|  (the lowest channel wins a tie)  |  mean_c x[b,c,m]^2
+ *   e[m] = a e[m-1] + (1 - a) p[m],   env[b,j] = e[j hop]
+ * evaluated as per-block sums z_j = sum_{i=1..hop} (1 - a) a^(hop-i) p[(j-1) hop + i] in fp32 with weights from fp64 and the frame-rate
+ * recurrence E_j = a^hop E_{j-1} + z_j in fp64. tangent (NULL: not formed) receives dE_j/da, which is all the backward pass needs beyond
+ * x and the control. scratch: dasp_envelope_scratch_floats(B, N, hop) = 2 B F floats, in both directions (backward: NULL when gx is).
+ * Backward: gx (NULL: not written) and gsmoothing (NULL exactly when tangent is; exactly zero where the control was clamped).
+ * gain_curve: j = n / hop, t = (n mod hop) / hop, g = gain_db[b,j] + t (gain_db[b,j+1] - gain_db[b,j]) (the frame value itself at
+ * t = 0), y[b,c,n] = x[b,c,n] 10^(g / 20). Backward: gx (NULL: not written) and ggain (NULL: not formed; else scratch holds
+ * dasp_gaincurve_scratch_floats(B, N, hop) = 2 B F floats, the per-interval pairs that a second launch joins).
+ * No atomics: every output is bit-identical run to run and for an item alone or in a batch.
+ * A null pointer (the optional ones apart), a non-positive size or hop, a detector outside 0 .. 1 or a sample rate that is not positive
+ * and finite: DASP_ERR_ARG (-1 from the queries); a hop that is no power of two from 8 to 2048, N > 2^40, B * tiles >= 2^31 or
+ * B * F >= 2^37: DASP_ERR_UNSUPPORTED (-2 from the queries). All of it is checked before any launch.
+ * Non-finite input: a NaN smoothing_ms makes env, tangent and the gradients of its item NaN; a NaN or inf sample m0 reaches the frame
+ * points j hop >= m0 of its item; a NaN gain_db[b,j] reaches the samples (j - 1) hop < n < (j + 1) hop of its item. */
+int dasp_envelope_tile(void);
+long dasp_envelope_scratch_floats(long B, long N, int hop);
+int dasp_envelope_forward(const float* x, const float* smoothing_ms, float* env, float* tangent, float* scratch, int B, int C, long N, int hop,
+                          int detector, double sample_rate, void* stream);
+int dasp_envelope_backward(const float* x, const float* smoothing_ms, const float* tangent, const float* genv, float* gx, float* gsmoothing,
+                           float* scratch, int B, int C, long N, int hop, int detector, double sample_rate, void* stream);
+long dasp_gaincurve_scratch_floats(long B, long N, int hop);
+int dasp_gaincurve_forward(const float* x, const float* gain_db, float* y, int B, int C, long N, int hop, void* stream);
+int dasp_gaincurve_backward(const float* x, const float* gain_db, const float* gy, float* gx, float* ggain, float* scratch, int B, int C, long N,
+                            int hop, void* stream);
+
 /* resample: polyphase windowed-sinc sample-rate conversion by the reduced ratio orig : new_ = o : n, and its adjoint
  * (csrc/resample.hip; the definition is DESIGN.md 3.15, a restatement of torchaudio.functional.resample's published algorithm with
  * the taps exactly zero where the window's argument was clamped). x, gx (rows, N) fp32; y, gy (rows, M) fp32, M = ceil(n N / o):
