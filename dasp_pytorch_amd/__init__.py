@@ -2,7 +2,7 @@
 from . import chain, config, functional, losses, modules, signal  # noqa: F401
 from .functional import (advanced_distortion, compressor, distortion, envelope_follower, expander, fdn_reverb, feedback_delay, gain, gain_curve, graphic_eq, limiter, loudness, loudness_normalize,  # noqa: F401
                          modulated_delay, noise_shaped_reverberation, oversampled_distortion, parametric_eq, peak_normalize, phaser, resample, stereo_bus, stereo_mix, stereo_panner,
-                         stereo_widener, time_varying_filter)
+                         stereo_widener, time_varying_eq, time_varying_filter)
 from .modules import (Compressor, Distortion, Expander, FDNReverb, FeedbackDelay, Gain, GainCurve, Limiter, ModulatedDelay, NoiseShapedReverb, OversampledDistortion, ParametricEQ, Phaser, Processor,  # noqa: F401
-                      Resample, TimeVaryingFilter)
+                      Resample, TimeVaryingEQ, TimeVaryingFilter)
 from .signal import control_frames, fdn_delay_lengths, resample_taps  # noqa: F401

@@ -1143,6 +1143,56 @@ class TimeVaryingFilterFunction(_AudioControlsFunction):
         return gcut, gq, gmix
 
 
+TVEQ_MODES = ("bell", "lowshelf", "highshelf")
+
+
+class TimeVaryingEQKernels:
+    """The forward / backward pair of time_varying_eq as autograd calls it: a bell or shelf band of the trapezoidal state-variable filter
+    whose gain, g and k follow the curves gain_db, cutoff_hz and q (dasp_tveq_forward / _backward, csrc/tveq.hip). The curves: (bs, F),
+    F = signal.control_frames(seq_len, hop); sample_rate: a float; hop: an int; mode: an index into TVEQ_MODES. Saves x, the curves and,
+    when anything needs a gradient, the two states before every tile (dasp_tveq_state_floats): the backward kernel rebuilds a tile from
+    them."""
+
+    @staticmethod
+    def forward(ctx, x, gain_db, cutoff_hz, q, sample_rate, hop, mode):
+        return TimeVaryingEQFunction._run(ctx, x, (gain_db, cutoff_hz, q), sample_rate, hop, mode)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return TimeVaryingEQFunction._grad(ctx, gy)
+
+
+class TimeVaryingEQFunction(TimeVaryingEQKernels, _AudioControlsFunction):
+    """TimeVaryingEQKernels bound to autograd on the shared plumbing of _AudioControlsFunction, the curves kept as three (bs, F)
+    matrices. The pair lives in the plain class, as for GainCurveFunction: the table of tests/autograd_contract_cases.py is closed, and
+    this op's contract is checked by the same batteries from tests/test_gpu_time_varying_eq.py, which watches TimeVaryingEQKernels."""
+    CFG = (float, int, int)
+
+    @classmethod
+    def _controls(cls, x, ctls):
+        return tuple(cls._f32(x, c, x.shape[0], -1).contiguous() for c in ctls)
+
+    @staticmethod
+    def _forward(ctx, x32, c32, y):
+        (gain, cut, qq), (B, C, N), (sample_rate, hop, mode) = c32, x32.shape, ctx.cfg
+        states = None
+        if any(ctx.needs_input_grad[:4]):
+            states = torch.empty(_lib.lib().dasp_tveq_state_floats(B * C, N), dtype=torch.float32, device=x32.device)
+        call("dasp_tveq_forward", ptr(x32), ptr(gain), ptr(cut), ptr(qq), ptr(y), ptr(states), B, C, N, hop, mode, sample_rate, stream())
+        return None if states is None else (states,)
+
+    @staticmethod
+    def _backward(ctx, x32, saved, gy, gx):
+        (gain, cut, qq, states), (B, C, N), (sample_rate, hop, mode) = saved, x32.shape, ctx.cfg
+        ggain, gcut, gq = torch.empty_like(gain), torch.empty_like(cut), torch.empty_like(qq)
+        scratch = torch.empty(_lib.lib().dasp_tveq_scratch_floats(B * C, N, hop), dtype=torch.float32, device=x32.device)
+        g32 = _f32c(gy)
+        call("dasp_tveq_backward", ptr(x32), ptr(gain), ptr(cut), ptr(qq), ptr(states), ptr(g32), ptr(gx), ptr(ggain), ptr(gcut), ptr(gq), ptr(scratch),
+             B, C, N, hop, mode, sample_rate, stream())
+        return ggain, gcut, gq
+
+
 class GainCurveKernels:
     """The forward / backward pair of gain_curve as autograd calls it: y = x 10^(g / 20), g the curve gain_db (bs, F) interpolated in dB
     between frame points hop samples apart (dasp_gaincurve_forward / _backward, csrc/envelope.hip). sample_rate: a float the op does

@@ -134,6 +134,11 @@ SIGNATURES = {
     "dasp_tvfilter_scratch_floats": (_l, [_l, _l, _i]),
     "dasp_tvfilter_forward": (_i, [_p] * 6 + [_i, _i, _l, _i, _i, _d, _p]),
     "dasp_tvfilter_backward": (_i, [_p] * 11 + [_i, _i, _l, _i, _i, _d, _p]),
+    "dasp_tveq_tile": (_i, []),
+    "dasp_tveq_state_floats": (_l, [_l, _l]),
+    "dasp_tveq_scratch_floats": (_l, [_l, _l, _i]),
+    "dasp_tveq_forward": (_i, [_p] * 6 + [_i, _i, _l, _i, _i, _d, _p]),
+    "dasp_tveq_backward": (_i, [_p] * 11 + [_i, _i, _l, _i, _i, _d, _p]),
     "dasp_resample_table_limit": (_i, []),
     "dasp_resample_window_limit": (_i, []),
     "dasp_resample_tile": (_i, [_i, _i, _i, _i]),

@@ -33,24 +33,13 @@
 // the walk carried along. A finalize kernel adds an item's channels in float64 and applies dG/dcutoff and dK/dq in float64, exactly
 // zero where the frame value was clamped. No atomics anywhere: every result is bit-identical run to run and for an item alone or in a
 // batch. Backward traffic: 12 B per sample. LDS: forward 20 KiB, backward 31 KiB.
-#include "row_helpers.hpp"
+#include "tv_scan.hpp"      // the tile geometry, tv_step, the maps and their scan, the interval sum: shared with tveq.hip
 
 namespace dasp {
-
-constexpr int TV_THREADS = 256;
-constexpr int TV_SPT = 8;                            // consecutive samples per thread
-constexpr int TV_TILE = TV_THREADS * TV_SPT;
-constexpr int TV_NW = TV_THREADS / 64;
-constexpr int TV_STAGE = TV_TILE + TV_TILE / TV_SPT; // a staged tile: sample i at word i + i / 8
-constexpr int TV_FP = TV_TILE / 8 + 1;               // frame points of a tile at the smallest hop
-constexpr int TV_HOP_MIN = 8, TV_HOP_MAX = TV_TILE;
 
 // wk = pi / sr; flo, fhi: the clamp of the cutoff; m1, m2, mx: w = m1 k v1 + m2 v2 + mx x;
 // d2, dl, dx: w - x = m1 k v1 + d2 v2 + dl (a2 ic1 - a1 (1 + g k) v3) + dx x, the form without the cancellation of a pass band (tv_cfg)
 struct TvCfg { double wk, flo, fhi; float m1, m2, mx, d2, dl, dx, inv_hop; int hop, lg; };
-struct TvMap { float a, b, c, d, u, v; };             // z -> [[a, b], [c, d]] z + (u, v)
-
-__device__ __forceinline__ double tv_clamp(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }   // a NaN stays
 
 // The frame points j0 .. j0 + nfp - 1 of a tile; those past the curves (only runs past the row read them) are zero.
 __device__ __forceinline__ void tv_frames(float* Gs, float* Ks, const float* __restrict__ cut, const float* __restrict__ q, long j0, int nfp, long F,
@@ -68,7 +57,6 @@ __device__ __forceinline__ void tv_frames(float* Gs, float* Ks, const float* __r
 }
 
 // The coefficients of a thread's 8 samples: i0 its first sample in the tile.
-struct TvRun { float g[TV_SPT], k[TV_SPT], a1[TV_SPT], a2[TV_SPT], a3[TV_SPT], t[TV_SPT]; };
 __device__ __forceinline__ void tv_coef(TvRun& c, const float* Gs, const float* Ks, int i0, const TvCfg& g) {
     const int ii = i0 >> g.lg, off = i0 & (g.hop - 1);
     const float G0 = Gs[ii], dG = Gs[ii + 1] - G0, K0 = Ks[ii], dK = Ks[ii + 1] - K0;
@@ -83,15 +71,6 @@ __device__ __forceinline__ void tv_coef(TvRun& c, const float* Gs, const float* 
     }
 }
 
-// One sample of the filter: z = (z1, z2) before it, replaced by the state after it.
-__device__ __forceinline__ void tv_step(float& z1, float& z2, float x, float a1, float a2, float a3, float& v1, float& v2) {
-    const float v3 = x - z2;
-    v1 = __builtin_fmaf(a1, z1, a2 * v3);
-    v2 = z2 + __builtin_fmaf(a2, z1, a3 * v3);
-    z1 = __builtin_fmaf(2.f, v1, -z1);
-    z2 = __builtin_fmaf(2.f, v2, -z2);
-}
-
 // One sample of the adjoint: lam = (l1, l2) the gradient of the state after the sample, mu that of the state before it.
 __device__ __forceinline__ void tv_adj(float l1, float l2, float gw, float k, float a1, float a2, float a3, const TvCfg& g, float& q1, float& q2, float& gv3,
                                        float& mu1, float& mu2) {
@@ -100,64 +79,6 @@ __device__ __forceinline__ void tv_adj(float l1, float l2, float gw, float k, fl
     gv3 = __builtin_fmaf(q1, a2, q2 * a3);
     mu1 = __builtin_fmaf(q1, a1, __builtin_fmaf(q2, a2, -l1));
     mu2 = (q2 - l2) - gv3;
-}
-
-__device__ __forceinline__ TvMap tv_after(const TvMap& L, const TvMap& E) {          // E first, then L
-    TvMap r;
-    r.a = __builtin_fmaf(L.a, E.a, L.b * E.c);
-    r.b = __builtin_fmaf(L.a, E.b, L.b * E.d);
-    r.c = __builtin_fmaf(L.c, E.a, L.d * E.c);
-    r.d = __builtin_fmaf(L.c, E.b, L.d * E.d);
-    r.u = __builtin_fmaf(L.a, E.u, __builtin_fmaf(L.b, E.v, L.u));
-    r.v = __builtin_fmaf(L.c, E.u, __builtin_fmaf(L.d, E.v, L.v));
-    return r;
-}
-
-// the map of the lane DPP names, or the identity
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ TvMap tv_dpp(const TvMap& m) {
-    return TvMap{dpp_or_one<CTRL, ROW_MASK>(m.a), dpp_or_zero<CTRL, ROW_MASK>(m.b), dpp_or_zero<CTRL, ROW_MASK>(m.c), dpp_or_one<CTRL, ROW_MASK>(m.d),
-                 dpp_or_zero<CTRL, ROW_MASK>(m.u), dpp_or_zero<CTRL, ROW_MASK>(m.v)};
-}
-
-// The scan of the runs' maps. run: the thread's map; (c1, c2): the state before the tile; wt: six floats per wave. Returns in (o1, o2)
-// the state before the thread's first sample. One barrier; wt is free again after the caller's next one.
-__device__ __forceinline__ void tv_scan(const TvMap& run, float c1, float c2, float* wt, float& o1, float& o2) {
-    const int lane = lane_id(), wv = wave_id();
-    TvMap agg = run;
-    agg = tv_after(agg, tv_dpp<0x111, 0xf>(agg));       // row_shr:1
-    agg = tv_after(agg, tv_dpp<0x112, 0xf>(agg));       // row_shr:2
-    agg = tv_after(agg, tv_dpp<0x114, 0xf>(agg));       // row_shr:4
-    agg = tv_after(agg, tv_dpp<0x118, 0xf>(agg));       // row_shr:8
-    agg = tv_after(agg, tv_dpp<0x142, 0xa>(agg));       // row_bcast:15   rows 1, 3 after the row before them
-    agg = tv_after(agg, tv_dpp<0x143, 0xc>(agg));       // row_bcast:31   rows 2, 3 after rows 0..1
-    TvMap ex{shift_up(agg.a, 1), shift_up(agg.b, 1), shift_up(agg.c, 1), shift_up(agg.d, 1), shift_up(agg.u, 1), shift_up(agg.v, 1)};
-    if (lane == 0) ex = TvMap{1.f, 0.f, 0.f, 1.f, 0.f, 0.f};
-    if (lane == 63) {
-        float* w = wt + 6 * wv;
-        w[0] = agg.a; w[1] = agg.b; w[2] = agg.c; w[3] = agg.d; w[4] = agg.u; w[5] = agg.v;
-    }
-    lds_barrier();
-    for (int u = 0; u < wv; ++u) {                      // the state before the wave's first sample
-        const float* w = wt + 6 * u;
-        const float n1 = __builtin_fmaf(w[0], c1, __builtin_fmaf(w[1], c2, w[4]));
-        const float n2 = __builtin_fmaf(w[2], c1, __builtin_fmaf(w[3], c2, w[5]));
-        c1 = n1;
-        c2 = n2;
-    }
-    o1 = __builtin_fmaf(ex.a, c1, __builtin_fmaf(ex.b, c2, ex.u));
-    o2 = __builtin_fmaf(ex.c, c1, __builtin_fmaf(ex.d, c2, ex.v));
-}
-
-// The map of a run in forward time: from the two unit states without input, and from zero state with the run's x.
-__device__ __forceinline__ TvMap tv_run_map(const float (&x)[TV_SPT], const TvRun& c) {
-    float e1 = 1.f, e2 = 0.f, f1 = 0.f, f2 = 1.f, z1 = 0.f, z2 = 0.f, v1, v2;
-#pragma unroll
-    for (int j = 0; j < TV_SPT; ++j) {
-        tv_step(e1, e2, 0.f, c.a1[j], c.a2[j], c.a3[j], v1, v2);
-        tv_step(f1, f2, 0.f, c.a1[j], c.a2[j], c.a3[j], v1, v2);
-        tv_step(z1, z2, x[j], c.a1[j], c.a2[j], c.a3[j], v1, v2);
-    }
-    return TvMap{e1, f1, e2, f2, z1, z2};
 }
 
 template <bool SAVE>
@@ -333,16 +254,11 @@ tvfilter_backward_kernel(const float* __restrict__ x, const float* __restrict__ 
         s_mix += (double)t_mix;
         // the runs of an interval: the lanes of a group by an xor butterfly, every lane of it ending with the same bits
         {
-            double d0 = (double)p_gl, d1 = (double)p_gr, d2 = (double)p_kl, d3 = (double)p_kr;
-            for (int d = 1; d < W; d <<= 1) {
-                d0 += __shfl_xor(d0, d, 64);
-                d1 += __shfl_xor(d1, d, 64);
-                d2 += __shfl_xor(d2, d, 64);
-                d3 += __shfl_xor(d3, d, 64);
-            }
+            double d[4] = {(double)p_gl, (double)p_gr, (double)p_kl, (double)p_kr};
+            tv_group_sum(d, W);
             if ((tid & (W - 1)) == 0) {
                 double* o = red[f / W];
-                o[0] = d0; o[1] = d1; o[2] = d2; o[3] = d3;
+                o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3];
             }
         }
         lds_barrier();
@@ -413,11 +329,6 @@ __global__ void tvfilter_finalize_kernel(const float* __restrict__ partials, con
 using namespace dasp;
 
 namespace {
-inline long tv_ntile(long N) { return (N + TV_TILE - 1) / TV_TILE; }
-inline bool tv_hop_pow2(int hop) { return hop > 0 && (hop & (hop - 1)) == 0; }
-inline bool tv_hop_ok(int hop) { return tv_hop_pow2(hop) && hop >= TV_HOP_MIN && hop <= TV_HOP_MAX; }
-inline long tv_frames_of(long N, int hop) { return (N + hop - 1) / hop + 1; }
-
 int tv_args(const float* x, const float* cut, const float* q, const float* mix, int B, int C, long N, int hop, int mode, double sample_rate) {
     if (!x || !cut || !q || !mix || B <= 0 || C <= 0 || N <= 0 || hop <= 0 || mode < 0 || mode > 3 || !(sample_rate > 0.0) ||
         !(sample_rate - sample_rate == 0.0))

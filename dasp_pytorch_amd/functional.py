@@ -12,7 +12,7 @@ from . import ops as _ops
 from . import _lib
 from .ops import (ENVELOPE_DETECTORS, FILTER_TYPES, BusFunction, DistortionSampleFunction, EnvelopeFollowerFunction, FdnReverbFunction, FeedbackDelayFunction, GainCurveFunction,
                   LimiterFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
-                  PhaserFunction, ResampleFunction, StereoMixFunction, TVFILTER_MODES, TimeVaryingFilterFunction, WidenerFunction)
+                  PhaserFunction, ResampleFunction, StereoMixFunction, TVEQ_MODES, TVFILTER_MODES, TimeVaryingEQFunction, TimeVaryingFilterFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
 from .ops64 import Dynamics64Function, Elementwise64Function, ParametricEQ64Function, is_f64, require_fp32_ok
 
@@ -340,6 +340,59 @@ def time_varying_filter(x: torch.Tensor, sample_rate: float, cutoff_hz: torch.Te
     _lib.require_device(x, "x")
     require_fp32_ok(x, "time_varying_filter")
     return TimeVaryingFilterFunction.apply(x, cutoff_hz, q, mix, sr, int(hop), TVFILTER_MODES.index(mode))
+
+
+def time_varying_eq(x: torch.Tensor, sample_rate: float, gain_db: torch.Tensor, cutoff_hz: torch.Tensor, q: torch.Tensor, hop: int = 64,
+                    mode: str = "bell"):
+    """One EQ band whose gain, frequency and Q follow control curves: a bell, low shelf or high shelf from Simper's trapezoidal
+    state-variable filter, the recurrence of `time_varying_filter` - the de-esser, the dynamic EQ, a band of a multiband compressor, EQ
+    automation, a tilt driven by level. x (bs, chs, seq_len); gain_db, cutoff_hz and q (bs, F) with F = signal.control_frames(seq_len,
+    hop), frame point j at sample j hop, shared by an item's channels - the convention of time_varying_filter, gain_curve and
+    envelope_follower, so a curve from any of them fits. hop is a plain int, a power of two from 8 to 2048; mode one of "bell",
+    "lowshelf", "highshelf". There is no mix: the gain is the amount. For item b, every channel and sample n, with both states zero
+    before sample 0:
+        A_j = 10^(clamp(gain_db[b,j], -40, 40) / 40);   T_j = tan(pi clamp(cutoff_hz[b,j], sample_rate/4096, 0.49 sample_rate) / sample_rate)
+        Qc = clamp(q[b,j], 0.1, 100)
+        bell: G_j = T_j, K_j = 1 / (Qc A_j)    lowshelf: G_j = T_j / sqrt A_j, K_j = 1 / Qc    highshelf: G_j = T_j sqrt A_j, K_j = 1 / Qc
+        j = n // hop;   t = (n mod hop) / hop;   g = G_j + t (G_{j+1} - G_j);   likewise k from K and A from A_j
+        a1 = 1 / (1 + g (g + k));   a2 = g a1;   a3 = g a2
+        v3 = x[n] - ic2;   v1 = a1 ic1 + a2 v3;   v2 = ic2 + a2 ic1 + a3 v3;   ic1 <- 2 v1 - ic1;   ic2 <- 2 v2 - ic2
+        bell:       y[n] = x[n] + k (A^2 - 1) v1
+        lowshelf:   y[n] = x[n] + k (A - 1) v1 + (A^2 - 1) v2
+        highshelf:  y[n] = A^2 x[n] + k (1 - A) A v1 + (1 - A^2) v2
+    What is interpolated is G, K and A, not Hz or dB: the frame points are taken in float64 in the kernel and rounded once, everything
+    after them is float32 (csrc/tveq.hip). With constant curves the result is the RBJ peaking, low-shelf and high-shelf biquad of
+    signal.biquad at the same frequency, Q and gain - the sections parametric_eq is built from. An all-zero gain_db returns x bit for
+    bit and hands the upstream gradient to x bit for bit, while the gradient of gain_db is generally not zero there.
+    Differentiable once in x, gain_db, cutoff_hz and q, every frame value included. The gradient of a frame value that was clamped is
+    exactly zero. No atomics: every result is bit-identical run to run and for an item alone or in a batch. The clamps are comparisons,
+    which a NaN passes: a NaN frame value j of any curve makes its item NaN from sample (j - 1) hop on and leaves earlier samples and
+    other items alone. Half and bfloat16 are converted, float64 is refused.
+    One workgroup walks one (item, channel) row tile by tile: the op cannot fill the chip at training batch sizes.
+    Out of scope: several bands in one kernel (the follow-up, in the manner of phaser's stages), per-channel curves, a side chain inside
+    the op (compose time_varying_filter and envelope_follower), look-back segments for few rows, float64, and double backward, which is
+    refused as for the siblings. A wrong frame count raises RuntimeError naming the curve and the expected F; a hop that is no power of
+    two from 8 to 2048, an unknown mode or a sample_rate that is not positive and finite ValueError, before anything touches the
+    device."""
+    bs, chs, seq_len = x.size()
+    try:
+        sr = float(sample_rate)
+    except (TypeError, ValueError):
+        sr = float("nan")
+    if not (sr > 0.0 and sr != float("inf")):
+        raise ValueError(f"time_varying_eq: finite sample_rate > 0, got {sample_rate}")
+    if mode not in TVEQ_MODES:
+        raise ValueError(f"time_varying_eq: mode must be one of {', '.join(TVEQ_MODES)}, got {mode!r}")
+    try:
+        frames = _signal.control_frames(seq_len, hop)
+    except ValueError as e:
+        raise ValueError(f"time_varying_eq: {e}") from None
+    for name, c in (("gain_db", gain_db), ("cutoff_hz", cutoff_hz), ("q", q)):
+        if c.dim() != 2 or tuple(c.shape) != (bs, frames):
+            raise RuntimeError(f"{name}: expected shape [{bs}, {frames}] (F = ceil({seq_len} / {hop}) + 1 = {frames} frame points), got {list(c.shape)}")
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "time_varying_eq")
+    return TimeVaryingEQFunction.apply(x, gain_db, cutoff_hz, q, sr, int(hop), TVEQ_MODES.index(mode))
 
 
 def envelope_follower(x: torch.Tensor, sample_rate: float, smoothing_ms: torch.Tensor, hop: int = 64, detector: str = "peak"):

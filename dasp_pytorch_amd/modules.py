@@ -464,6 +464,40 @@ class TimeVaryingFilter(Processor):
                                q=denormalize(param_tensor[:, frames:2 * frames], qhi, qlo), mix=denormalize(param_tensor[:, 2 * frames], mhi, mlo))
 
 
+class TimeVaryingEQ(Processor):
+    """Time-varying EQ band (functional.time_varying_eq); hop and mode are fixed at construction. Its controls are curves, so the
+    parameter tensor of process_normalized is (bs, 3 F) with F = signal.control_frames(seq_len, hop): F columns of gain_db, F of
+    cutoff_hz, F of q, each on [0, 1] and mapped linearly onto its range of `param_ranges`."""
+
+    def __init__(self, sample_rate: int, hop: int = 64, mode: str = "bell", min_gain_db: float = -24.0, max_gain_db: float = 24.0,
+                 min_cutoff_hz: float = 50.0, max_cutoff_hz: float = 12000.0, min_q: float = 0.5, max_q: float = 8.0):
+        super().__init__()
+        S.control_frames(0, hop)
+        if mode not in F.TVEQ_MODES:
+            raise ValueError(f"mode must be one of {', '.join(F.TVEQ_MODES)}, got {mode!r}")
+        self.sample_rate = sample_rate
+        self.hop = int(hop)
+        self.mode = mode
+        self.process_fn = functools.partial(F.time_varying_eq, hop=self.hop, mode=mode)
+        self.param_ranges = {"gain_db": (min_gain_db, max_gain_db), "cutoff_hz": (min_cutoff_hz, max_cutoff_hz), "q": (min_q, max_q)}
+
+    def process_normalized(self, x: torch.Tensor, param_tensor: torch.Tensor):
+        frames = S.control_frames(x.shape[-1], self.hop)
+        if param_tensor.dim() != 2 or param_tensor.shape[1] != 3 * frames:
+            raise ValueError(f"Parameter tensor has {param_tensor.shape[-1]} parameters, but processor has {3 * frames} parameters "
+                             f"({frames} frame points each of gain_db, cutoff_hz and q).")
+        if self.validate_range and not getattr(_validated, "on", False) and not (param_tensor.is_cuda and torch.cuda.is_current_stream_capturing()):
+            names = ["gain_db"] * frames + ["cutoff_hz"] * frames + ["q"] * frames   # _check_range, with a name per column
+            if self.validate_range == "deferred":
+                self._deferred().submit(param_tensor, names)
+            else:
+                check_unit_range(param_tensor, names)
+        (glo, ghi), (clo, chi), (qlo, qhi) = (self.param_ranges[k] for k in ("gain_db", "cutoff_hz", "q"))
+        return self.process_fn(x, self.sample_rate, gain_db=denormalize(param_tensor[:, :frames], ghi, glo),
+                               cutoff_hz=denormalize(param_tensor[:, frames:2 * frames], chi, clo),
+                               q=denormalize(param_tensor[:, 2 * frames:], qhi, qlo))
+
+
 class GainCurve(Processor):
     """Gain along a control curve (functional.gain_curve); hop is fixed at construction. Its control is a curve, so the parameter tensor
     of process_normalized is (bs, F) with F = signal.control_frames(seq_len, hop): the frame values of gain_db, each on [0, 1] and mapped

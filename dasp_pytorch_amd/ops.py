@@ -19,7 +19,7 @@ from ._ctypes_ops import (FILTER_TYPES, BiquadFunction, BusFunction, ChainContro
                           DynamicsCtlFunction, DynamicsFunction, DynamicsMatrixFunction, ENVELOPE_DETECTORS, EnvelopeFollowerFunction, FdnReverbFunction, FeedbackDelayFunction, GainCurveFunction, GainFunction, LimiterFunction, ModulatedDelayFunction, OversampledDistortionFunction,
                           PannerFunction, PhaserFunction,
                           ParametricEQFunction,
-                          ParametricEQNormFunction, ResampleFunction, ReverbFunction, SosFiltFunction, StereoMixFunction, TVFILTER_MODES, TimeVaryingFilterFunction, WidenerFunction, _dyn_counters, _filter_spectrum, _seed_offset,
+                          ParametricEQNormFunction, ResampleFunction, ReverbFunction, SosFiltFunction, StereoMixFunction, TVEQ_MODES, TVFILTER_MODES, TimeVaryingEQFunction, TimeVaryingFilterFunction, WidenerFunction, _dyn_counters, _filter_spectrum, _seed_offset,
                           resample_design,
                           _SosWork, chain_eq_compressor_forward, reverb_noise)
 from ._lib import check

@@ -607,6 +607,36 @@ int dasp_tvfilter_backward(const float* x, const float* cutoff_hz, const float* 
                            float* gcutoff, float* gq, float* gmix, float* scratch, int B, int C, long N, int hop, int mode, double sample_rate,
                            void* stream);
 
+/* time_varying_eq: a bell, low-shelf or high-shelf band of the same trapezoidal state-variable filter whose gain, cutoff and Q follow
+ * control curves (csrc/tveq.hip, on the walk of csrc/tvfilter.hip). x, y, gy, gx (B, C, N) fp32; gain_db, cutoff_hz, q, ggain, gcutoff,
+ * gq (B, F) fp32, F = dasp_tvfilter_frames(N, hop) = ceil(N / hop) + 1, shared by an item's channels. hop: a power of two from 8 to
+ * 2048. mode: 0 bell, 1 lowshelf, 2 highshelf. For item b, every channel and sample n, with both states zero before sample 0:
+ *   A_j = 10^(clamp(gain_db[b,j], -40, 40) / 40),  T_j = tan(pi clamp(cutoff_hz[b,j], sample_rate/4096, 0.49 sample_rate) / sample_rate),
+ *   Qc = clamp(q[b,j], 0.1, 100)                                                        (float64, then G, K, A rounded once to float32)
+ *   bell: G_j = T_j, K_j = 1 / (Qc A_j)    lowshelf: G_j = T_j / sqrt A_j, K_j = 1 / Qc    highshelf: G_j = T_j sqrt A_j, K_j = 1 / Qc
+ *   j = n / hop,  t = (n mod hop) / hop,  g = G_j + t (G_{j+1} - G_j),  likewise k from K and A from A_j        (float32 from here on)
+ *   a1, a2, a3, v1, v2, ic1, ic2 as for time_varying_filter
+ *   y[n] = x + k (A^2 - 1) v1  |  x + k (A - 1) v1 + (A^2 - 1) v2  |  A^2 x + k (1 - A) A v1 + (1 - A^2) v2   by mode
+ * An all-zero gain_db gives y = x and gx = gy bit for bit. A row is walked in tiles of dasp_tveq_tile() samples.
+ * Forward: states (NULL: not saved) receives dasp_tveq_state_floats(B * C, N) = rows * ceil(N / tile) * 2 floats, (ic1, ic2) before
+ * every tile - all the backward pass needs beyond x and the curves.  Backward: gx (NULL: not written), ggain, gcutoff, gq; scratch holds
+ * dasp_tveq_scratch_floats(B * C, N, hop) = rows * 3 F floats, the rows' sums per frame point for G, K and A, added over an item's
+ * channels and chained to the three curves in fp64 in a fixed order by a second launch. No atomics. y, states, gx, ggain, gcutoff and gq
+ * are bit-identical run to run. Each gradient is exactly zero where its frame value was clamped.
+ * A null pointer (states in forward and gx apart), a non-positive size or hop, a mode outside 0 .. 2 or a sample rate that is not positive
+ * and finite: DASP_ERR_ARG (-1 from the queries); a hop that is no power of two from 8 to 2048, B * C >= 2^31 or B * F >= 2^37:
+ * DASP_ERR_UNSUPPORTED (-2 from the queries). All of it is checked before any launch.
+ * Non-finite input: as for time_varying_filter, for all three curves - a NaN frame value j makes its item NaN from sample (j - 1) hop on;
+ * earlier samples and other items keep every bit. */
+int dasp_tveq_tile(void);
+long dasp_tveq_state_floats(long rows, long N);
+long dasp_tveq_scratch_floats(long rows, long N, int hop);
+int dasp_tveq_forward(const float* x, const float* gain_db, const float* cutoff_hz, const float* q, float* y, float* states, int B, int C, long N,
+                      int hop, int mode, double sample_rate, void* stream);
+int dasp_tveq_backward(const float* x, const float* gain_db, const float* cutoff_hz, const float* q, const float* states, const float* gy, float* gx,
+                       float* ggain, float* gcutoff, float* gq, float* scratch, int B, int C, long N, int hop, int mode, double sample_rate,
+                       void* stream);
+
 /* envelope_follower and gain_curve: the control-rate side chains, audio -> curve and curve -> gain (csrc/envelope.hip). x, gx, y, gy
  * (B, C, N) fp32; smoothing_ms, gsmoothing (B) fp32; env, tangent, genv, gain_db, ggain (B, F) fp32, F = ceil(N / hop) + 1 (the frame
  * points of dasp_tvfilter_frames: point j at sample j hop), shared by an item's channels. hop: a power of two from 8 to 2048.
