@@ -1295,6 +1295,110 @@ class EnvelopeFollowerFunction(EnvelopeFollowerKernels, torch.autograd.Function)
     this op's contract is checked by the same batteries from tests/test_gpu_envelope.py, which watches EnvelopeFollowerKernels."""
 
 
+class BlockLevelKernels:
+    """The forward / backward pair of block_level as autograd calls it: x (bs, chs, N) -> L (bs, F), the peak or the mean square of
+    every hop (dasp_blocklevel_forward / _backward, csrc/ballistics.hip). hop: an int; detector: an index into ENVELOPE_DETECTORS.
+    Peak saves the winners, one int32 per frame (position in the hop, sign and channel), and not x: its backward pass is write-only.
+    Power saves x."""
+
+    @staticmethod
+    def forward(ctx, x, hop, detector):
+        _lib.require_device(x, "x")
+        B, C, N = x.shape
+        hop, detector = int(hop), int(detector)
+        F = -(-N // hop) + 1
+        ctx.meta = (x.dtype, x.shape)
+        ctx.cfg = (hop, detector)
+        ctx.empty = x.numel() == 0
+        if ctx.empty:
+            return torch.zeros((B, F), dtype=x.dtype, device=x.device)
+        with torch.cuda.device(x.device):
+            x32 = _f32c(x)
+            L = torch.empty((B, F), dtype=torch.float32, device=x.device)
+            need = ctx.needs_input_grad[0]
+            win = torch.empty((B, F), dtype=torch.int32, device=x.device) if need and detector == 0 else None
+            call("dasp_blocklevel_forward", ptr(x32), ptr(L), ptr(win), B, C, N, hop, detector, stream())
+            if need:
+                ctx.save_for_backward(win if detector == 0 else x32)
+        return L.to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gL):
+        xd, xs = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        if ctx.empty:
+            return torch.zeros(xs, dtype=xd, device=gL.device), None, None
+        (hop, detector), (B, C, N) = ctx.cfg, xs
+        (kept,) = ctx.saved_tensors
+        with torch.cuda.device(kept.device):
+            gx = torch.empty(xs, dtype=torch.float32, device=kept.device)
+            g32 = _f32c(gL)
+            call("dasp_blocklevel_backward", ptr(kept if detector else None), ptr(None if detector else kept), ptr(g32), ptr(gx), B, C, N, hop,
+                 detector, stream())
+        return gx.to(xd), None, None
+
+
+class BlockLevelFunction(BlockLevelKernels, torch.autograd.Function):
+    """BlockLevelKernels bound to autograd, a direct Function like EnvelopeFollowerFunction. The pair lives in the plain class and this
+    one defines no forward of its own: the table of tests/autograd_contract_cases.py is closed, and this op's contract is checked by the
+    same batteries from tests/test_gpu_block_level.py, which watches BlockLevelKernels."""
+
+
+class BallisticsKernels:
+    """The forward / backward pair of ballistics as autograd calls it: P (bs, F) -> E (bs, F), the branching attack / release smoother
+    (dasp_ballistics_forward / _backward, csrc/ballistics.hip). attack_ms, release_ms: bs values each; sample_rate: a float; hop: an
+    int. Saves P, both controls, E (float32) and the branch mask as the forward pass decided it (bs, F) uint8."""
+
+    @staticmethod
+    def forward(ctx, curve, attack_ms, release_ms, sample_rate, hop):
+        _lib.require_device(curve, "curve")
+        B, F = curve.shape
+        ctx.meta = (curve.dtype, attack_ms.dtype, attack_ms.shape, release_ms.dtype, release_ms.shape)
+        ctx.cfg = (float(sample_rate), int(hop))
+        ctx.empty = curve.numel() == 0
+        if ctx.empty:
+            return torch.zeros((B, F), dtype=curve.dtype, device=curve.device)
+        with torch.cuda.device(curve.device):
+            p32 = _f32c(curve)
+            a32, r32 = (c.detach().reshape(B).to(device=curve.device, dtype=torch.float32).contiguous() for c in (attack_ms, release_ms))
+            E = torch.empty_like(p32)
+            need = any(ctx.needs_input_grad[:3])
+            up = torch.empty((B, F), dtype=torch.uint8, device=curve.device) if need else None
+            call("dasp_ballistics_forward", ptr(p32), ptr(a32), ptr(r32), ptr(E), ptr(up), B, F, ctx.cfg[1], ctx.cfg[0], stream())
+            if need:
+                ctx.save_for_backward(p32, a32, r32, E, up)
+        return E.to(curve.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gE):
+        pd, ad, ash, rd, rsh = ctx.meta
+        need = ctx.needs_input_grad
+        if not any(need[:3]):
+            return None, None, None, None, None
+        if ctx.empty:
+            return _needed(ctx, (torch.zeros(gE.shape, dtype=pd, device=gE.device), torch.zeros(ash, dtype=ad, device=gE.device),
+                                 torch.zeros(rsh, dtype=rd, device=gE.device), None, None))
+        sample_rate, hop = ctx.cfg
+        p32, a32, r32, E, up = ctx.saved_tensors
+        B, F = p32.shape
+        with torch.cuda.device(p32.device):
+            gP = torch.empty_like(p32) if need[0] else None                       # None: not written
+            ga = torch.empty_like(a32) if need[1] else None
+            gr = torch.empty_like(r32) if need[2] else None
+            g32 = _f32c(gE)
+            call("dasp_ballistics_backward", ptr(p32), ptr(a32), ptr(r32), ptr(E), ptr(up), ptr(g32), ptr(gP), ptr(ga), ptr(gr), B, F, hop,
+                 sample_rate, stream())
+        return (gP.to(pd) if need[0] else None, ga.reshape(ash).to(ad) if need[1] else None, gr.reshape(rsh).to(rd) if need[2] else None, None, None)
+
+
+class BallisticsFunction(BallisticsKernels, torch.autograd.Function):
+    """BallisticsKernels bound to autograd; no forward of its own, as for BlockLevelFunction (tests/test_gpu_ballistics.py watches
+    BallisticsKernels)."""
+
+
 _RESAMPLE_DESIGNS, _RESAMPLE_TABLES = {}, {}
 
 

@@ -128,6 +128,11 @@ SIGNATURES = {
     "dasp_gaincurve_scratch_floats": (_l, [_l, _l, _i]),
     "dasp_gaincurve_forward": (_i, [_p] * 3 + [_i, _i, _l, _i, _p]),
     "dasp_gaincurve_backward": (_i, [_p] * 6 + [_i, _i, _l, _i, _p]),
+    "dasp_ballistics_chunk": (_i, []),
+    "dasp_blocklevel_forward": (_i, [_p] * 3 + [_i, _i, _l, _i, _i, _p]),
+    "dasp_blocklevel_backward": (_i, [_p] * 4 + [_i, _i, _l, _i, _i, _p]),
+    "dasp_ballistics_forward": (_i, [_p] * 5 + [_i, _l, _i, _d, _p]),
+    "dasp_ballistics_backward": (_i, [_p] * 9 + [_i, _l, _i, _d, _p]),
     "dasp_tvfilter_tile": (_i, []),
     "dasp_tvfilter_frames": (_l, [_l, _i]),
     "dasp_tvfilter_state_floats": (_l, [_l, _l]),

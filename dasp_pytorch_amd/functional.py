@@ -10,7 +10,7 @@ from . import signal as _signal
 from . import _mt19937
 from . import ops as _ops
 from . import _lib
-from .ops import (ENVELOPE_DETECTORS, FILTER_TYPES, BusFunction, DistortionSampleFunction, EnvelopeFollowerFunction, FdnReverbFunction, FeedbackDelayFunction, GainCurveFunction,
+from .ops import (ENVELOPE_DETECTORS, FILTER_TYPES, BallisticsFunction, BlockLevelFunction, BusFunction, DistortionSampleFunction, EnvelopeFollowerFunction, FdnReverbFunction, FeedbackDelayFunction, GainCurveFunction,
                   LimiterFunction, ModulatedDelayFunction, OversampledDistortionFunction, PannerFunction,
                   PhaserFunction, ResampleFunction, StereoMixFunction, TVEQ_MODES, TVFILTER_MODES, TimeVaryingEQFunction, TimeVaryingFilterFunction, WidenerFunction)
 from .ops import reverb as _ops_reverb
@@ -459,6 +459,130 @@ def gain_curve(x: torch.Tensor, sample_rate: float, gain_db: torch.Tensor, hop: 
     _lib.require_device(x, "x")
     require_fp32_ok(x, "gain_curve")
     return GainCurveFunction.apply(x, gain_db, float(sample_rate), int(hop))
+
+
+def _finite_rate(sample_rate, who):
+    try:
+        sr = float(sample_rate)
+    except (TypeError, ValueError):
+        sr = float("nan")
+    if not (sr > 0.0 and sr != float("inf")):
+        raise ValueError(f"{who}: finite sample_rate > 0, got {sample_rate}")
+    return sr
+
+
+def block_level(x: torch.Tensor, sample_rate: float, hop: int = 64, detector: str = "peak"):
+    """Block detector: the peak or the mean square of every hop, as a control curve. x (bs, chs, seq_len); hop is a plain int, a power
+    of two from 8 to 2048; detector "peak" or "power"; sample_rate is not used (the common signature of the control-rate layer).
+    Returns L (bs, F), F = signal.control_frames(seq_len, hop), frame point j at sample j hop. With the level of envelope_follower,
+        p[m] = max_c |x[b,c,m]|   ("peak": the lowest channel wins a tie, a NaN channel makes p NaN)   |   mean_c x[b,c,m]^2   ("power")
+    and p = 0 from sample seq_len on:
+        L[b,0] = p[0];   L[b,j] = max_{i=1..hop} p[(j-1) hop + i]   |   (1 / hop) sum_{i=1..hop} p[(j-1) hop + i],   j = 1 .. F-1
+    Unlike a fast envelope_follower read at the frame points, it misses no peak between them. "peak" is exact: the earliest sample of
+    a block that holds the maximum wins, on its lowest winning channel, and the first NaN sample of a block wins it, so a NaN sample
+    m0 reaches frame ceil(m0 / hop) of its item and nothing else. "power" sums in float32 in one fixed order: runs of 8 samples in time
+    order, the runs of a block as a balanced tree, then the division by hop - always by hop, also where the signal ends inside the
+    block. Differentiable once in x: "peak" sends sign(x) gL_j to the winner (sign(0) = 0) and writes zero everywhere else, "power"
+    2 x / (chs hop) gL_j, and 2 x / chs gL_0 for sample 0. "peak" saves the winners, one int32 per frame, and not x - its backward
+    pass only writes; "power" saves x. Independent tiles of 4096 samples fill the chip at any batch size; no atomics: every result
+    is bit-identical run to run and for an item alone or in a batch (csrc/ballistics.hip). Half and bfloat16 are converted, float64 is
+    refused; seq_len = 0 returns the (bs, 1) zero curve.
+    Out of scope: unlinked channels, float64, a torch.ops.dasp registration and a chain.py entry. A hop that is no power of two from 8
+    to 2048 or an unknown detector raises ValueError before anything touches the device."""
+    bs, chs, seq_len = x.size()
+    if detector not in ENVELOPE_DETECTORS:
+        raise ValueError(f"block_level: detector must be one of {', '.join(ENVELOPE_DETECTORS)}, got {detector!r}")
+    try:
+        _signal.control_frames(seq_len, hop)
+    except ValueError as e:
+        raise ValueError(f"block_level: {e}") from None
+    _lib.require_device(x, "x")
+    require_fp32_ok(x, "block_level")
+    return BlockLevelFunction.apply(x, int(hop), ENVELOPE_DETECTORS.index(detector))
+
+
+def ballistics(curve: torch.Tensor, sample_rate: float, attack_ms: torch.Tensor, release_ms: torch.Tensor, hop: int = 64):
+    """Attack / release ballistics at the control rate: the classic branching one-pole smoother on a curve. curve P (bs, F) with any
+    F >= 1 - it is not tied to a signal length; attack_ms and release_ms hold bs values each; hop, a plain int and a power of two
+    from 8 to 2048, is the distance of the frame points in samples. Returns E (bs, F). For item b, with E_{-1} = 0:
+        t_a = clamp(attack_ms, 0.1, 10000);   c_a = -expm1(-ln 9 hop / (sample_rate t_a / 1000));   c_r likewise from release_ms
+        up_j = P_j > E_{j-1};   c_j = c_a if up_j else c_r;   E_j = E_{j-1} + c_j (P_j - E_{j-1})
+    so the 10 - 90 % rise and fall times of a step are attack_ms and release_ms (to within a hop). A tie takes the release branch;
+    a NaN P_j compares false, takes the release branch and makes E NaN from j on in its item only; a NaN control makes its own item
+    NaN and no other. With attack_ms == release_ms it is the linear one-pole. The constants are float64 from the float32 controls,
+    the recurrence is float64 and E is rounded once to float32. The recurrence is walked, not scanned: a composition of these
+    max-of-affine maps has no fixed-size form. One wave per item walks the F values, which is affordable at the frame rate and would
+    not be at the sample rate (csrc/ballistics.hip).
+    Differentiable once in the curve and both times. The branch mask is saved as the forward pass decided it - the gradient is
+    discontinuous across the branches - with P, the controls and E:
+        Lambda_j = gE_j + (1 - c_{j+1}) Lambda_{j+1};   gP_j = c_j Lambda_j
+        g_attack = (dc_a/dt_a) sum_{j: up_j} Lambda_j (P_j - E_{j-1});   g_release likewise over the other frames
+    in float64 in one fixed order; a control gradient is exactly zero where its control was clamped. No atomics: every result is
+    bit-identical run to run and for an item alone or in a batch. Half and bfloat16 are converted, float64 is refused.
+    Out of scope: sample-rate (per-sample) ballistics, a hold time, float64, a torch.ops.dasp registration and a chain.py entry;
+    compressor and expander keep ignoring release_ms. A wrong control count raises RuntimeError naming the control; a hop that is no
+    power of two from 8 to 2048 or a sample_rate that is not positive and finite ValueError, before any launch."""
+    if curve.dim() != 2 or curve.shape[1] < 1:
+        raise RuntimeError(f"curve: expected shape [bs, F] with F >= 1, got {list(curve.shape)}")
+    bs = curve.shape[0]
+    for name, c in (("attack_ms", attack_ms), ("release_ms", release_ms)):
+        if c.numel() != bs:
+            raise RuntimeError(f"{name}: shape '[{bs}]' is invalid for input of size {c.numel()}")
+    sr = _finite_rate(sample_rate, "ballistics")
+    try:
+        _signal.control_frames(0, hop)
+    except ValueError as e:
+        raise ValueError(f"ballistics: {e}") from None
+    _lib.require_device(curve, "curve")
+    require_fp32_ok(curve, "ballistics")
+    return BallisticsFunction.apply(curve, attack_ms, release_ms, sr, int(hop))
+
+
+def _soft_knee_level(l_db, threshold_db, ratio, knee_db):
+    """The static curve of `compressor` on levels in dB (Giannoulis, Massberg & Reiss 2012): the level itself below the knee, the
+    quadratic blend inside it, threshold + (level - threshold) / ratio above. The controls broadcast against l_db. The knee's division
+    is by a width made safe where knee_db == 0 - a branch that is then never taken - so every gradient is finite."""
+    half = 0.5 * knee_db
+    over = l_db - threshold_db
+    wide = torch.where(knee_db > 0, knee_db, torch.ones_like(knee_db))
+    knee = l_db + (1.0 / ratio - 1.0) * (over + half) ** 2 / (2.0 * wide)
+    above = threshold_db + over / ratio
+    in_knee = (knee_db > 0) & (over >= -half) & (over <= half)
+    return torch.where(over > half, above, torch.where(in_knee, knee, l_db))
+
+
+def sidechain_compressor(x: torch.Tensor, sample_rate: float, threshold_db: torch.Tensor, ratio: torch.Tensor, attack_ms: torch.Tensor,
+                         release_ms: torch.Tensor, knee_db: torch.Tensor, makeup_gain_db: torch.Tensor, key: torch.Tensor = None, hop: int = 64,
+                         eps: float = 1e-5):
+    """Feed-forward compressor at the control rate whose release_ms is real, keyed by x itself or by another signal. Plain torch on
+    (bs, F) around three fused ops:
+        L = block_level(key if key is not None else x, sample_rate, hop, "peak")          (the peak of every hop, channels linked)
+        l_db = 20 log10(L + eps)
+        g_db = the soft-knee static curve of `compressor` on l_db                         (Giannoulis, Massberg & Reiss 2012)
+        r = l_db - g_db                                                                   (the gain reduction, >= 0 dB)
+        r_s = ballistics(r, sample_rate, attack_ms, release_ms, hop)                      (reduction rises with attack, falls with release)
+        y = gain_curve(x, sample_rate, makeup_gain_db[:, None] - r_s, hop)
+    x (bs, chs, seq_len); key (bs, chs_k, seq_len) of the same seq_len, any channel count; the six controls hold bs values each; hop is
+    a plain int, a power of two from 8 to 2048. Differentiable in x, key and all six controls; the differentiability of the static curve
+    is torch's, and knee_db == 0 gives finite gradients, as `compressor`'s stated deviation does. With a key, the gradient of x flows
+    through the gain alone. Out of scope: sample-rate ballistics (the gain moves at frame points and is interpolated between them),
+    hold time and look-ahead for the side chain, unlinked channels, float64, a torch.ops.dasp registration and a chain.py entry;
+    `compressor` and `expander` are unchanged and keep ignoring release_ms."""
+    bs, chs, seq_len = x.size()
+    ctls = dict(threshold_db=threshold_db, ratio=ratio, attack_ms=attack_ms, release_ms=release_ms, knee_db=knee_db, makeup_gain_db=makeup_gain_db)
+    for name, c in ctls.items():
+        if c.numel() != bs:
+            raise RuntimeError(f"{name}: shape '[{bs}]' is invalid for input of size {c.numel()}")
+    side = x if key is None else key
+    if side.dim() != 3 or side.shape[0] != bs or side.shape[2] != seq_len:
+        raise RuntimeError(f"key: expected shape [{bs}, chs_k, {seq_len}], got {list(side.shape)}")
+    _finite_rate(sample_rate, "sidechain_compressor")
+    L = block_level(side, sample_rate, hop, "peak")
+    col = lambda c: c.reshape(bs, 1).to(device=L.device, dtype=L.dtype)
+    l_db = 20.0 * torch.log10(L + eps)
+    r = l_db - _soft_knee_level(l_db, col(threshold_db), col(ratio), col(knee_db))
+    r_s = ballistics(r, sample_rate, attack_ms, release_ms, hop)
+    return gain_curve(x, sample_rate, col(makeup_gain_db) - r_s, hop)
 
 
 def resample(x: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,

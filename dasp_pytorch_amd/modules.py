@@ -670,6 +670,22 @@ class Compressor(_Dynamics):
         return _dynamics_process_normalized(self, 0, x, param_tensor)
 
 
+class SidechainCompressor(_Dynamics):
+    """The control-rate compressor with real attack and release (functional.sidechain_compressor); hop is fixed at construction.
+    Compressor's parameter names, order and ranges. process_normalized keys on x itself; process_fn(x, sample_rate, ..., key=...)
+    takes a side-chain signal."""
+
+    def __init__(self, sample_rate: int, hop: int = 64, min_threshold_db: float = -60.0, max_threshold_db: float = 0.0, min_ratio: float = 1.0,
+                 max_ratio: float = 20.0, min_attack_ms: float = 5.0, max_attack_ms: float = 100.0, min_release_ms: float = 5.0,
+                 max_release_ms: float = 100.0, min_knee_db: float = 0.0, max_knee_db: float = 12.0, min_makeup_gain_db: float = 0.0,
+                 max_makeup_gain_db: float = 12.0):
+        S.control_frames(0, hop)
+        self.hop = int(hop)
+        super().__init__(functools.partial(F.sidechain_compressor, hop=self.hop), sample_rate, min_threshold_db, max_threshold_db, min_ratio,
+                         max_ratio, min_attack_ms, max_attack_ms, min_release_ms, max_release_ms, min_knee_db, max_knee_db, min_makeup_gain_db,
+                         max_makeup_gain_db)
+
+
 class Expander(_Dynamics):
     def __init__(self, sample_rate: int, min_threshold_db: float = -60.0, max_threshold_db: float = 0.0, min_ratio: float = 1.0,
                  max_ratio: float = 20.0, min_attack_ms: float = 5.0, max_attack_ms: float = 100.0, min_release_ms: float = 5.0,

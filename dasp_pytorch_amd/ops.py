@@ -15,7 +15,7 @@ import ctypes
 import torch
 
 from . import _lib, config
-from ._ctypes_ops import (FILTER_TYPES, BiquadFunction, BusFunction, ChainControlsFunction, DistortionFunction, DistortionSampleFunction,   # noqa: F401
+from ._ctypes_ops import (FILTER_TYPES, BallisticsFunction, BiquadFunction, BlockLevelFunction, BusFunction, ChainControlsFunction, DistortionFunction, DistortionSampleFunction,   # noqa: F401
                           DynamicsCtlFunction, DynamicsFunction, DynamicsMatrixFunction, ENVELOPE_DETECTORS, EnvelopeFollowerFunction, FdnReverbFunction, FeedbackDelayFunction, GainCurveFunction, GainFunction, LimiterFunction, ModulatedDelayFunction, OversampledDistortionFunction,
                           PannerFunction, PhaserFunction,
                           ParametricEQFunction,

@@ -669,6 +669,40 @@ int dasp_gaincurve_forward(const float* x, const float* gain_db, float* y, int B
 int dasp_gaincurve_backward(const float* x, const float* gain_db, const float* gy, float* gx, float* ggain, float* scratch, int B, int C, long N,
                             int hop, void* stream);
 
+/* block_level and ballistics: the detector and the attack / release smoother of the control-rate layer, audio -> curve and
+ * curve -> curve (csrc/ballistics.hip). The frame points are those of the envelope: F = ceil(N / hop) + 1, point j at sample j hop,
+ * hop a power of two from 8 to 2048. x, gx (B, C, N) fp32; level, glevel (B, F) fp32; winners (B, F) int32; detector: 0 peak, 1 power.
+ * block_level, with p[m] the level of dasp_envelope_forward (p = 0 from sample N on):
+ *   level[b,0] = p[0],   level[b,j] = max_{i=1..hop} p[(j-1) hop + i]  (peak)  |  (1 / hop) sum_{i=1..hop} p[(j-1) hop + i]  (power)
+ * one workgroup per (item, tile of dasp_envelope_tile() samples). Peak: the earliest sample of a block that holds the maximum wins, on
+ * its lowest winning channel, and the first NaN sample of a block wins it; winners (NULL: not written; unused by power) receives per
+ * frame (i - 1) | sign << 11 | channel << 13 for the winning sample (j-1) hop + i, sign 0 zero, 1 positive, 2 negative, 3 NaN.
+ * Backward: peak reads winners and glevel alone (x may be NULL) and writes gx = sign(x_winner) glevel[b,j] at the winner and zero
+ * everywhere else; power reads x (winners may be NULL), gx = 2 x / (C hop) glevel[b,j], and 2 x / C glevel[b,0] for sample 0.
+ * ballistics, for item b over any F >= 1 values of a curve, E_{-1} = 0:
+ *   t_a = clamp(attack_ms, 0.1, 10000),  c_a = -expm1(-ln 9 hop / (sample_rate t_a / 1000)),  c_r likewise from release_ms
+ *   up[b,j] = curve[b,j] > E_{j-1},   c_j = up ? c_a : c_r,   out[b,j] = E_j = E_{j-1} + c_j (curve[b,j] - E_{j-1})
+ * walked in fp64 by one wave per item over chunks of dasp_ballistics_chunk() frames staged through LDS, rounded once to fp32.
+ * curve, out, gout, gcurve (B, F) fp32; up (B, F) bytes (forward: NULL, not written); attack_ms, release_ms, gattack, grelease (B) fp32.
+ * Backward takes the forward's out and up: Lambda_j = gout_j + (1 - c_{j+1}) Lambda_{j+1}, gcurve_j = c_j Lambda_j, gattack =
+ * (dc_a/dt_a) sum over the frames with up of Lambda_j (curve_j - out_{j-1}), grelease over the others; each of the three outputs may be
+ * NULL (not all); a control gradient is exactly zero where its control was clamped.
+ * No atomics: every output is bit-identical run to run and for an item alone or in a batch.
+ * A null pointer (the optional ones apart), a non-positive size or hop, a detector outside 0 .. 1 or a sample rate that is not positive
+ * and finite: DASP_ERR_ARG; a hop that is no power of two from 8 to 2048, more than 2^18 channels, N > 2^40, B * tiles >= 2^31 or
+ * B * F >= 2^37: DASP_ERR_UNSUPPORTED. All of it is checked before any launch.
+ * Non-finite input: a NaN sample m0 reaches frame ceil(m0 / hop) of level; a NaN curve value j makes out NaN from j on in its item; a
+ * NaN attack_ms or release_ms makes out and every gradient of its item NaN. */
+int dasp_ballistics_chunk(void);
+int dasp_blocklevel_forward(const float* x, float* level, int* winners, int B, int C, long N, int hop, int detector, void* stream);
+int dasp_blocklevel_backward(const float* x, const int* winners, const float* glevel, float* gx, int B, int C, long N, int hop, int detector,
+                             void* stream);
+int dasp_ballistics_forward(const float* curve, const float* attack_ms, const float* release_ms, float* out, unsigned char* up, int B, long F,
+                            int hop, double sample_rate, void* stream);
+int dasp_ballistics_backward(const float* curve, const float* attack_ms, const float* release_ms, const float* out, const unsigned char* up,
+                             const float* gout, float* gcurve, float* gattack, float* grelease, int B, long F, int hop, double sample_rate,
+                             void* stream);
+
 /* resample: polyphase windowed-sinc sample-rate conversion by the reduced ratio orig : new_ = o : n, and its adjoint
  * (csrc/resample.hip; the definition is DESIGN.md 3.15, a restatement of torchaudio.functional.resample's published algorithm with
  * the taps exactly zero where the window's argument was clamped). x, gx (rows, N) fp32; y, gy (rows, M) fp32, M = ceil(n N / o):
